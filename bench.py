@@ -11,11 +11,17 @@ so no per-launch duration of that form is reproducible). Per-GPU batch is fixed 
 of N owns `--batch` frames of the N*batch global batch (BASELINE configs 3 and 5: 64 frames per GPU =
 config 5's share at N=8).
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 Without a launcher (WORLD_SIZE unset), `--gpus N` with N > 1 starts N ranks itself: this process runs
 `torch.distributed.run --nproc-per-node N` as a CHILD before touching the GPU and exits with its code
 (it never re-execs). Under a launcher, WORLD_SIZE must equal --gpus (else exit 2).
+A plain run sets up, warms up, times the K steps and prints the headline record (metric, value, unit,
+ms_per_step, dtype, config); `--dump-outputs DIR` also writes the last timed step's occupancy grids
+(what a caller of the step receives) as DIR/grids.npy, float32 — the inputs are seeded, so two builds
+can be compared output for output. Everything else described below (per-stage and per-kernel timing,
+`roofline`, the sub-records of other precisions / stream counts / batch 1 / DeepLab, the agreement
+records, the CPU baseline) takes runs of its own and is measured only with `--full`.
 The headline is the fp32 mode (`--precision fp32`, the default since round 5): the reference's own
 arithmetic (TF fp32 sess.run, models.py:43-44). What the tests enforce: on the default (damped) weights
 the logits lie within 1e-3 absolute of the fp32 oracle, the timed B = 64 configuration included
@@ -142,11 +148,16 @@ def parse():
     p.add_argument("--graph", type=int, default=1,
                    help="1: replay the step (both shards' forwards + BEV on their streams) as one captured HIP "
                         "graph — measured 41.8-41.9k vs 41.7k frames/s eager (round 3); 0: eager launches")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure everything beyond the headline: per-stage and per-kernel "
+                        "timing, the roofline, the sub-records (--extras) and the CPU baseline; off: the headline record only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the occupancy grids of the last timed step (rank 0's own batch) as DIR/grids.npy, float32")
     p.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     p.add_argument("--extras", type=int, default=-1,
-                   help="1: add the other precision modes / batch-1 latency / class-agreement / DeepLab sub-records (measured "
-                        "outside the timed loop); default: on at N = 1, off for N > 1")
+                   help="with --full, 1: add the other precision modes / batch-1 latency / class-agreement / DeepLab sub-records "
+                        "(measured outside the timed loop); default: on at N = 1, off for N > 1")
     p.add_argument("--deeplab-batch", type=int, default=64)
     p.add_argument("--overlap-gather", type=int, default=1,
                    help="N > 1 over RCCL: overlap step k's grid all-gather with step k+1's forward (2: on gloo too)")
@@ -156,7 +167,10 @@ def parse():
     p.add_argument("--launcher-check", action="store_true",
                    help="CPU-only functional check of the N-rank launch and the grid all-gather (gloo; synthetic int8 "
                         "grids, no GPU, no engine): what tests/test_distributed_gloo.py runs without a GPU")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
 
 
 def _free_port():
@@ -648,6 +662,56 @@ def class_agreement(blocks, H, W, nframes, dev, precs=("bf16", "fp16")):
     return res
 
 
+def stage_and_kernel_records(a, pipe, model, bev, grid, frames):
+    """--full: `roofline`, `kernels`, `stages_ms` and `shard_overlap_ms` of the timed configuration,
+    measured after the timed loop (every rank runs them, as every rank ran the step)."""
+    from bugcar_image_segmentation_amd import _native as N
+    B, H, W, dev = frames.shape[0], a.height, a.width, frames.device
+    # ---- per-stage and per-kernel timing with HIP events on the stream the kernels are launched on
+    # (untimed region), at the shard size the timed region launched (shard 0 runs on model.ctx), so every
+    # launch of this command has one shape and rocprof's per-kernel averages describe the same launches
+    stream = torch.cuda.current_stream()
+    Bs = B // a.streams if a.streams > 1 and B >= a.streams else B
+    x, seg, g = pipe._bufs(B, dev)
+    fs, ss, gs = frames[:Bs], seg[:Bs], g[:Bs]
+    reps = max(3, min(20, a.steps))
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    t_fwd = t_bev = 0.0
+    # one untimed pass first (one-time costs of this context / output buffer stay out of the average)
+    model.ctx.forward_bgr(fs, Bs, H, W, N.OUT_CLASS3_U8, ss)
+    bev.create_occupancy_grid_device(ss, *grid, out=gs)
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        # frames are already at the model resolution: preprocess is fused into the initial block
+        ev[0].record(stream)
+        model.ctx.forward_bgr(fs, Bs, H, W, N.OUT_CLASS3_U8, ss)
+        ev[1].record(stream)
+        bev.create_occupancy_grid_device(ss, *grid, out=gs)
+        ev[2].record(stream)
+        ev[2].synchronize()
+        t_fwd += ev[0].elapsed_time(ev[1])
+        t_bev += ev[1].elapsed_time(ev[2])
+    t_fwd, t_bev = t_fwd / reps, t_bev / reps
+    # the laserscan-like occupancy mode (bev.py:216-240) on the same class maps (not in the timed step)
+    bev.laserscan_like_occupancy_grid = True
+    bev.create_occupancy_grid_device(ss, *grid, out=gs)
+    ev[0].record(stream)
+    for _ in range(reps):
+        bev.create_occupancy_grid_device(ss, *grid, out=gs)
+    ev[1].record(stream)
+    ev[1].synchronize()
+    t_ls = ev[0].elapsed_time(ev[1]) / reps
+    bev.laserscan_like_occupancy_grid = False
+    overlap = shard_overlap(pipe, frames, seg, g, bev, grid, H, W, reps) if a.streams > 1 and B >= a.streams else None
+    log("in-step kernel table")
+    instep = instep_kernel_table(pipe, frames, H, W, reps)
+    roof, ktable = roofline_record(model.ctx, Bs, H, W, reps, stream, a.precision, t_fwd, instep)
+    return {"roofline": roof, "kernels": ktable,
+            "stages_ms": {"frames": Bs, "enet_forward": round(t_fwd, 4), "bev_occgrid": round(t_bev, 4),
+                          "bev_occgrid_laserscan": round(t_ls, 4)},
+            "shard_overlap_ms": overlap}
+
+
 def main():
     a = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -677,7 +741,6 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
 
-    from bugcar_image_segmentation_amd import _native as N
     from bugcar_image_segmentation_amd import enet_spec, synthetic
     from bugcar_image_segmentation_amd.distributed import gather_grids
     from bugcar_image_segmentation_amd.models import ENET
@@ -757,57 +820,25 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
     el = time.perf_counter() - t0
     marker.fill_(2)
+    if a.dump_outputs and rank == 0:
+        # what the last timed step returned: this rank's occupancy grids (int8 cells; nothing ran since)
+        # (at most 64 MB: the leading frames of a batch too large for that)
+        keep = max(1, min(B, (64 << 20) // (4 * last[0].numel())))
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "grids.npy"), last[:keep].cpu().numpy().astype(np.float32))
     if dist_on:
         t = torch.tensor([el], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
     log(f"timed loop done: {el:.3f} s")
-    # ---- per-stage and per-kernel timing with HIP events on the stream the kernels are launched on
-    # (untimed region), at the shard size the timed region launched (shard 0 runs on model.ctx), so every
-    # launch of this command has one shape and rocprof's per-kernel averages describe the same launches
-    stream = torch.cuda.current_stream()
-    Bs = B // a.streams if a.streams > 1 and B >= a.streams else B
-    x, seg, g = pipe._bufs(B, dev)
-    fs, ss, gs = frames[:Bs], seg[:Bs], g[:Bs]
-    reps = max(3, min(20, a.steps))
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    t_fwd = t_bev = 0.0
-    # one untimed pass first (one-time costs of this context / output buffer stay out of the average)
-    model.ctx.forward_bgr(fs, Bs, H, W, N.OUT_CLASS3_U8, ss)
-    bev.create_occupancy_grid_device(ss, *grid, out=gs)
-    torch.cuda.synchronize()
-    for _ in range(reps):
-        # frames are already at the model resolution: preprocess is fused into the initial block
-        ev[0].record(stream)
-        model.ctx.forward_bgr(fs, Bs, H, W, N.OUT_CLASS3_U8, ss)
-        ev[1].record(stream)
-        bev.create_occupancy_grid_device(ss, *grid, out=gs)
-        ev[2].record(stream)
-        ev[2].synchronize()
-        t_fwd += ev[0].elapsed_time(ev[1])
-        t_bev += ev[1].elapsed_time(ev[2])
-    t_fwd, t_bev = t_fwd / reps, t_bev / reps
-    # the laserscan-like occupancy mode (bev.py:216-240) on the same class maps (not in the timed step)
-    bev.laserscan_like_occupancy_grid = True
-    bev.create_occupancy_grid_device(ss, *grid, out=gs)
-    ev[0].record(stream)
-    for _ in range(reps):
-        bev.create_occupancy_grid_device(ss, *grid, out=gs)
-    ev[1].record(stream)
-    ev[1].synchronize()
-    t_ls = ev[0].elapsed_time(ev[1]) / reps
-    bev.laserscan_like_occupancy_grid = False
-    overlap = shard_overlap(pipe, frames, seg, g, bev, grid, H, W, reps) if a.streams > 1 and B >= a.streams else None
-    log("in-step kernel table")
-    instep = instep_kernel_table(pipe, frames, H, W, reps)
-    roof, ktable = roofline_record(model.ctx, Bs, H, W, reps, stream, a.precision, t_fwd, instep)
+    detail = stage_and_kernel_records(a, pipe, model, bev, grid, frames) if a.full else {}
 
     if rank == 0:
         frames_total = B * world * a.steps
@@ -828,13 +859,9 @@ def main():
                        "backend": ("rccl" if a.backend == "nccl" else "gloo (functional run, not a timing)") if dist_on
                                   else "none (one process)",
                        **({"gather_check": gather_check} if dist_on else {})},
-            "roofline": roof,
-            "kernels": ktable,
-            "stages_ms": {"frames": Bs, "enet_forward": round(t_fwd, 4), "bev_occgrid": round(t_bev, 4),
-                          "bev_occgrid_laserscan": round(t_ls, 4)},
-            "shard_overlap_ms": overlap,
+            **detail,
         }
-        extras = a.extras if a.extras >= 0 else int(world == 1)
+        extras = (a.extras if a.extras >= 0 else int(world == 1)) if a.full else 0
         if extras:
             if a.streams == 1:
                 # the same step as two frame shards on two streams (more throughput from the kernels' tails
@@ -878,7 +905,7 @@ def main():
             log("deeplab resnet sub-record")
             res["deeplab_resnet"] = bench_deeplab.record(dev, 16, max(5, a.steps // 2), 3, "bf16",
                                                          backbone="resnet_v1_101_beta")
-        if not a.no_cpu_baseline and world == 1:   # the CPU baseline is an N = 1 record (rank 0)
+        if a.full and not a.no_cpu_baseline and world == 1:   # the CPU baseline is an N = 1 record (rank 0)
             res["cpu_baseline"] = cpu_baseline(blocks, bev, grid, H, W, a.cpu_baseline_seconds)
         print(json.dumps(res), flush=True)
     if dist_on:

@@ -8,7 +8,7 @@ T=${1:-prof}; P=${2:-fp32}; shift 2; X="$*"
 O=$GRAFT_REPO_ROOT/gpurun_out/$T
 mkdir -p $O
 export TMPDIR=/tmp
-CMD="$GRAFT_REPO_ROOT/bench.py --precision $P --extras 0 --no-cpu-baseline $X"
+CMD="$PWD/bench.py --full --precision $P --extras 0 --no-cpu-baseline $X"   # (--full: the `kernels` / `roofline` records)
 timeout -k 10 300 python -u $CMD > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -5 $O/bench.err; exit 1; }
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 $CMD > $O/trace.json 2> $O/trace.err || { echo "trace failed"; tail -5 $O/trace.err; exit 1; }

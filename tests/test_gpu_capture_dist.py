@@ -233,7 +233,7 @@ def test_bench_distributed_branch_gloo_one_gpu(gpu, overlap):
     group one GPU can host."""
     cmd = [sys.executable, "bench.py", "--gpus", "2",
            "--backend", "gloo", "--steps", "5", "--warmup", "3", "--batch", "4", "--height", "96", "--width", "128",
-           "--extras", "0", "--no-cpu-baseline", "--overlap-gather", str(overlap)]
+           "--full", "--extras", "0", "--no-cpu-baseline", "--overlap-gather", str(overlap)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
@@ -258,7 +258,7 @@ def test_bench_rccl_branch_one_rank(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "1",
            "--backend", "nccl", "--steps", "3", "--warmup", "1", "--batch", "4", "--height", "96", "--width", "128",
-           "--extras", "0", "--no-cpu-baseline"]
+           "--full", "--extras", "0", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=220, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -267,6 +267,33 @@ def test_bench_rccl_branch_one_rank(gpu):
     assert line["config"]["backend"] == "rccl" and line["config"]["gather_check"] is True
     assert "RCCL all-gather" in line["config"]["parallelism"] and line["config"]["ranks"] == 1
     assert line["n_gpus"] == 1 and line["value"] > 0
+    assert "roofline" in line and "kernels" in line and "stages_ms" in line      # --full's records
+
+
+def test_bench_plain_run_dumps_its_last_step(gpu, blocks, tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline record alone, and --dump-outputs DIR
+    writes the last timed step's occupancy grids as DIR/grids.npy in float32: the grids the same
+    pipeline gives in this process on the bench's seeded frames, cell for cell (int8 values; exact)."""
+    B, H, W = 4, 96, 128
+    out = tmp_path / "dump"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+           "--height", str(H), "--width", str(W), "--dump-outputs", str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID")}
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=220, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["dtype"] == "fp32"
+    assert line["higher_is_better"] is True and abs(line["value"] - B * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+    for k in ("roofline", "kernels", "stages_ms", "cpu_baseline", "two_streams", "deeplab"):
+        assert k not in line, k
+    assert sorted(p.name for p in out.iterdir()) == ["grids.npy"]
+    got = np.load(out / "grids.npy")
+    assert got.dtype == np.float32 and got.shape == (B, 200, 200)
+    bev = synthetic.synthetic_bev(H, W)
+    pipe = OccupancyPipeline(ENET(weights=blocks, precision="fp32"), bev, synthetic.GRID_W_M, synthetic.GRID_H_M,
+                             synthetic.CELL_M, model_hw=(H, W))
+    want = pipe.run(torch.from_numpy(synthetic.uniform_frames(B, H, W, seed=0)).to(gpu)).cpu().numpy()
+    assert np.array_equal(got, want.astype(np.float32))
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
