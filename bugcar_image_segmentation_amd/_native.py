@@ -28,7 +28,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_last_error",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
-            "bugseg_debug_parse_pack", "bugseg_debug_polar_tables", "bugseg_debug_ctx_info", "bugseg_debug_set_spans", "bugseg_debug_pool_indices",
+            "bugseg_debug_parse_pack", "bugseg_debug_polar_tables", "bugseg_debug_ctx_info", "bugseg_debug_tile_walk", "bugseg_debug_set_spans", "bugseg_debug_pool_indices",
             "bugseg_dl_debug_check_plan")
 DL_OP_FIELDS = 32
 
@@ -95,6 +95,7 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_debug_parse_pack": (i, [vp, sz, i, ctypes.POINTER(i)]),
             "bugseg_debug_polar_tables": (i, [i, i, i, vp, sz, vp, sz, ctypes.POINTER(i), ctypes.POINTER(i)]),
             "bugseg_debug_ctx_info": (i, [vp, i, i]),
+            "bugseg_debug_tile_walk": (i, [i, i, i, vp, sz, vp]),
             "bugseg_debug_set_spans": (i, [vp, vp, i]),
             "bugseg_debug_pool_indices": (i, [vp, i, i, i, i, vp, sz, ctypes.POINTER(ctypes.c_int), vp]),
             "bugseg_dl_debug_check_plan": (i, [vp, i, vp, i, i, i, i, i, sz]),
@@ -114,6 +115,19 @@ def check(code: int, ctx=None) -> None:
         if code == EINVAL:
             raise ValueError(msg)
         raise BugsegError(code, msg)
+
+
+def tile_walk(ntiles: int, grid: int, rev: int) -> list[list[int]]:
+    """Test hook (bugseg_debug_tile_walk, host only): per workgroup of a `grid`-workgroup launch over
+    `ntiles` tiles, the tiles it visits, in order (rev 0 ascending, 1 descending)."""
+    lib = load_library()
+    per_max = (ntiles + 7) // 8                 # no workgroup walks more than its XCD group's run
+    seq = (ctypes.c_int32 * (grid * per_max))()
+    count = (ctypes.c_int32 * grid)()
+    per = lib.bugseg_debug_tile_walk(ntiles, grid, rev, seq, len(seq), count)
+    if per < 0:
+        check(per)
+    return [list(seq[b * per:b * per + count[b]]) for b in range(grid)]
 
 
 def require_gpu() -> None:

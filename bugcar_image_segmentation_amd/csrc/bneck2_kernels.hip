@@ -105,11 +105,11 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
     float amo = 0.f;
 
     // XCD-aware tile walk as bneck_kernel's, per HALF: half-slot hs of the workgroup's XCD group takes
-    // tiles grp * CH + hs, + nhs, ...
+    // steps hs, + nhs, ... of the group's run (tile_walk: ascending, or a.rev descending)
     const int G = gridDim.x, grp = blockIdx.x & 7, nhs = (G >> 3) * 2;
-    const int CH = (a.ntiles + 7) >> 3;
+    const int CH = tile_walk_ch(a.ntiles);
     auto ntiles_of = [&](int hs) -> int {
-        const int lim = min(CH, a.ntiles - grp * CH);
+        const int lim = tile_walk_lim(grp, CH, a.ntiles);
         return hs < lim ? (lim - hs + nhs - 1) / nhs : 0;
     };
     const int hs = (int)(blockIdx.x >> 3) * 2 + half;
@@ -303,7 +303,7 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
         if (kk >= 0) {
             const int i = kk >> 1;
             if (i < nmy) {
-                const int tile = grp * CH + hs + i * nhs;
+                const int tile = tile_walk(grp, hs + i * nhs, CH, a.ntiles, a.rev);   // (i < nmy: inside the run)
 #ifndef BNECK2_SKIP
 #define BNECK2_SKIP 0
 #endif
@@ -321,7 +321,7 @@ __global__ void __launch_bounds__(1024, 1) bneck2_f32_kernel(const BneckArgs a) 
     span_enter(a.span);
     {
         // a workgroup without a tile leaves before staging anything
-        const int CH = (a.ntiles + 7) >> 3, lim = min(CH, a.ntiles - (int)(blockIdx.x & 7) * CH);
+        const int CH = tile_walk_ch(a.ntiles), lim = tile_walk_lim((int)(blockIdx.x & 7), CH, a.ntiles);
         if ((int)(blockIdx.x >> 3) * 2 >= lim) {
             span_exit(a.span);
             return;

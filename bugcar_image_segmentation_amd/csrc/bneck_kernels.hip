@@ -200,9 +200,12 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     // output store policy (mfma_common.h): sc1 for C >= 64; the fp32 C = 64 (non-down) form streams its
     // output non-temporally (nt) — round 5, B = 64, one stream: the blocks reading it (down C128, up C16)
     // 14-18 us faster per launch. nt measured worse for the fp32 C16 form (itself +4 us), the down forms
-    // (down C64 +32 us) and the C128 forms (+10%) — A/B knobs BNECK_NT_F32_C64 / _C16 / _DN
+    // (down C64 +32 us) and the C128 forms (+10%) — A/B knobs BNECK_NT_F32_C64 / _C16 / _DN.
+    // Re-measured under the alternating tile order: the consumers now start on the lines this
+    // form wrote last, and the headline is 0.4% higher with the C64 form's stores left in the cache, so
+    // BNECK_NT_F32_C64 is 0; the other constants measured equal or slower when flipped and keep their values
 #ifndef BNECK_NT_F32_C64
-#define BNECK_NT_F32_C64 1
+#define BNECK_NT_F32_C64 0
 #endif
 #ifndef BNECK_NT_F32_C16
 #define BNECK_NT_F32_C16 0
@@ -458,8 +461,8 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     // a workgroup without a tile leaves before staging anything (an LDS-DMA still in flight when
     // its wave ends would land in LDS the next workgroup on the CU already owns)
     {
-        const int ch = (a.ntiles + 7) >> 3, sl = (int)(blockIdx.x >> 3);
-        if (sl >= ch || (int)(blockIdx.x & 7) * ch + sl >= a.ntiles) return true;   // (the tile walk's first tile)
+        // (the tile walk's first tile, in either direction)
+        if (tile_walk((int)(blockIdx.x & 7), (int)(blockIdx.x >> 3), tile_walk_ch(a.ntiles), a.ntiles, a.rev) < 0) return true;
     }
     const int tid = threadIdx.x;
     const int lane = tid & 63, col = lane & 15, kq = lane >> 4;
@@ -682,7 +685,17 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     // XCD-aware tile walk (see conv_kernels.hip): each XCD takes a contiguous run of tiles, so the
     // halo re-reads of neighbouring tiles hit the same L2
     const int G = gridDim.x, grp = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = G >> 3;
-    const int CH = (a.ntiles + 7) >> 3;
+    const int CH = tile_walk_ch(a.ntiles);
+    // The fp32 forms sit at the SGPR limit, so how the walk (tile_walk, either direction) is spelt decides
+    // what spills: the C128 forms take the one-word form (tile_walk_at; with the other, 16 x 16 went 197 ->
+    // 213 VGPRs and the 20 x 16 and asymmetric forms to scratch), every other form the ascending tile
+    // flipped (tile_walk_flip; with the one-word form, fp32 C64 8 x 16 and C16 went to scratch: 139 -> 143 us
+    // and 163 -> 170 us per launch at B = 64). Both are checked against tile_walk on the host.
+    constexpr bool WALK1 = sizeof(T) == 4 && C == 128;
+    // (scripts/kernel_resources.py prints the register table that shows whether the split is still needed)
+    const int lim = tile_walk_lim(grp, CH, a.ntiles);
+    // WALK1: the one-word base; otherwise the mirror of the flip
+    const int wword = WALK1 ? tile_walk_base(grp, CH, a.ntiles, a.rev) : tile_walk_mirror(grp, CH, a.ntiles, a.rev);
     // tile -> frame n and image pixel (oy0, ox0) of tile pixel (0, 0): phase (py, px), tile row /
     // column of that phase's sub-image (scalar math). Tile pixel (i, j) is image (oy0 + dt i, ox0 +
     // dt j), or (oy0 + dt j, ox0 + dt i) transposed
@@ -707,15 +720,21 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #endif
     constexpr bool PREF = BNECK_PREF && KEEP && REG3 && !DN;
     bool pref = false;                                // this tile's kx already loaded (prefetched)
-    for (int it = slot; it < CH; it += nslots) {
-        const int tile = grp * CH + it;
-        if (tile >= a.ntiles) break;
+    for (int it = slot; it < (WALK1 ? lim : CH); it += nslots) {
+        int tile;
+        if constexpr (WALK1) {
+            tile = tile_walk_at(wword, it);
+        } else {
+            tile = grp * CH + it;
+            if (tile >= a.ntiles) break;
+            tile = tile_walk_flip(wword, tile);
+        }
         int n, oy0, ox0;
         tile_geom(tile, n, oy0, ox0);
         float tmo = 0.f;                              // CLS, fp32: this lane's max |out| over the tile
         // the next tile of this workgroup's walk (PREF)
-        const int ntile = grp * CH + it + nslots;
-        const bool has_next = PREF && it + nslots < CH && ntile < a.ntiles;
+        const bool has_next = PREF && it + nslots < lim;
+        const int ntile = !has_next ? -1 : WALK1 ? tile_walk_at(wword, it + nslots) : tile_walk_flip(wword, grp * CH + it + nslots);
         int nn = 0, noy0 = 0, nox0 = 0;
         if (has_next) tile_geom(ntile, nn, noy0, nox0);
         const int dtx = RD ? 1 : dt;                  // column step of the tile

@@ -78,6 +78,7 @@ struct ConvArgs {
     int naff_on;
     int pool_scan;       // init (A/B and tests): 1 = the per-tap pool scan instead of the packed f16 form
     int ntiles;
+    int rev;             // tile walk direction (tile_walk): 0 ascending, 1 descending
     int stg_elems;       // per-wave output staging (elements)
     int stage_ok;        // EPI_SHUFFLE: fragments never straddle an input row (Wg % 16 == 0, M % 16 == 0)
     // derived on the host (finish_conv_args): magic divisors, buffer sizes, staging shifts
@@ -88,6 +89,39 @@ struct ConvArgs {
     RangeArgs rg;        // fp32 mode: the input's measured range, sw[0] = the weights' exponent
     unsigned long long *span;   // launch span (bugseg_debug_set_spans): [min entry, max exit] clock, or null
 };
+
+// ---- XCD-aware tile walk, shared by every ENet kernel that walks tiles. Workgroup b of a grid that is a
+// multiple of 8 belongs to group grp = b % 8 (its XCD), which owns the contiguous run [grp * CH, grp * CH
+// + lim) of tiles, CH = ceil(ntiles / 8); the workgroup visits steps it = b / 8, + grid / 8, ... of that run.
+// tile_walk_lim: tiles in the group's run (<= 0: none). tile_walk: the tile of step `it`, or -1 past the
+// run. rev = 0 walks the run ascending (grp * CH + it), rev = 1 descending (grp * CH + lim - 1 - it): the
+// same tiles per XCD, so halo re-reads still hit its L2; only the time order flips, which lets a launch
+// start on the tensor bytes the launch before it touched last (Plan::tile_order, bugseg_runtime.cpp).
+// A kernel short of scalar registers keeps one word for the walk, tile_walk_base: the run's first tile, or
+// (descending) the complement of its end, so the sign carries the direction; tile_walk_at(base, it) is the
+// tile of step it < lim.
+__host__ __device__ inline int tile_walk_ch(int ntiles) { return (ntiles + 7) >> 3; }
+__host__ __device__ inline int tile_walk_lim(int grp, int CH, int ntiles) {
+    const int rest = ntiles - grp * CH;
+    return rest < CH ? rest : CH;
+}
+__host__ __device__ inline int tile_walk_base(int grp, int CH, int ntiles, int rev) {
+    return rev ? ~(grp * CH + tile_walk_lim(grp, CH, ntiles)) : grp * CH;
+}
+__host__ __device__ inline int tile_walk_at(int base, int it) {
+    const int s = base >> 31;                       // 0 ascending, -1 descending: (it ^ s) = -it - 1
+    return (base ^ s) + (it ^ s);
+}
+__host__ __device__ inline int tile_walk(int grp, int it, int CH, int ntiles, int rev) {
+    if (it >= tile_walk_lim(grp, CH, ntiles)) return -1;
+    return tile_walk_at(tile_walk_base(grp, CH, ntiles, rev), it);
+}
+// The same walk from the ascending tile t = grp * CH + it < ntiles: tile_walk_flip(tile_walk_mirror(..), t)
+// is t ascending (mirror -1) and the run's first + last tile - t descending.
+__host__ __device__ inline int tile_walk_mirror(int grp, int CH, int ntiles, int rev) {
+    return rev ? 2 * grp * CH + tile_walk_lim(grp, CH, ntiles) - 1 : -1;
+}
+__host__ __device__ inline int tile_walk_flip(int mirror, int t) { return mirror < 0 ? t : mirror - t; }
 
 // magic number for fdiv (mfma_common.h): divisor d >= 1
 void fastdiv(uint32_t d, uint32_t &m, int &s);
@@ -126,6 +160,7 @@ struct BneckArgs {
                          // count: dt^2, or dt for row-dilated full-width variants
     int tr;              // transposed tiles: tile rows run along image columns (symmetric blocks only)
     int tiles_x, tiles_y, ntiles;   // tiles per phase sub-image row / column; B * phases * tiles_y * tiles_x
+    int rev;             // tile walk direction (tile_walk): 0 ascending, 1 descending
     const void *w1, *w2, *w2b, *w3;                   // packed [Npad][Kpad] (w2b: asymmetric 1x5)
     const float *b1, *s1, *b2, *s2, *b2b, *s2b, *b3, *s3, *s_out;
     uint32_t x_bytes;                                 // bytes of x (== out)
@@ -176,6 +211,7 @@ struct UpArgs {
     const uint8_t *idx;       // pooling indices of the paired down block (B, h, w, idxCS), byte = window position
     void *out;                // (B, 2h, 2w, Cout)
     int M, h, w, idxCS;       // M = B * h * w input pixels
+    int rev;                  // walk direction of the pixel groups: 0 ascending, 1 descending
     uint32_t mHW, mW; int sHW, sW;                    // fdiv by h * w and by w
     const void *w1, *w2, *w3;                         // [main; e1] pair, tconv (4 phases), expansion
     const float *b1, *s1, *b2, *s2, *b3, *s3, *s_out;

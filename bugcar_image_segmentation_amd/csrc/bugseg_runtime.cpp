@@ -123,6 +123,8 @@ struct Op {
     bool bn_asym = false;
     double bytes = 0, flops = 0;
     double layer_bytes = -1;   // per-layer (unfused) algorithmic bytes of the work; -1: same as bytes
+    int launches = 1;          // kernel launches the op issues (every form today: one)
+    int pos = 0;               // launches the plan issues before this op (build_plan): its walk direction's parity
     Op() {
         std::memset(&a, 0, sizeof(a));
         std::memset(&bn, 0, sizeof(bn));
@@ -145,7 +147,17 @@ struct Plan {
     // with that bottleneck feeding the class kernel), and taken by the last forward (cls_on: a class-map
     // output, both ops in its range). The last op then launches nothing; its plan_op tag is "fused".
     bool cls_ok = false, cls_on = false;
+    // Tile walk direction of the launches (bugseg_internal.h tile_walk), BUGSEG_TILE_ORDER, read per plan
+    // build as BUGSEG_NO_FUSE is: 0 every launch ascending, 1 alternating from ascending, 2 every launch
+    // descending (a control). Alternating, a launch starts on the frames the launch before it finished
+    // with, whose lines are the likeliest to still be in the last-level cache.
+    int tile_order = 0;
 };
+
+// default of BUGSEG_TILE_ORDER (the measurement that chose it)
+#ifndef BUGSEG_TILE_ORDER_DEFAULT
+#define BUGSEG_TILE_ORDER_DEFAULT 1
+#endif
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline int pow2_nr(int npad) {   // 16-row fragments, rounded up to 1, 2, 4 or 8
@@ -1268,6 +1280,11 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
         if (!finish_conv_args(op.a, op.epi, w.es)) { why = "batch too large for 32-bit tensor offsets"; return false; }
     }
     pl.ops = std::move(w.ops);
+    int issued = 0;
+    for (Op &op : pl.ops) { op.pos = issued; issued += op.launches; }
+    pl.tile_order = BUGSEG_TILE_ORDER_DEFAULT;
+    if (const char *to = std::getenv("BUGSEG_TILE_ORDER"))
+        if (*to >= '0' && *to <= '2' && !to[1]) pl.tile_order = *to - '0';
     pl.cls_ok = false;
     pl.cls_on = false;
     if (pl.ops.size() >= 2) {
@@ -1558,17 +1575,22 @@ static BneckArgs cls_fused_args(const Plan &pl) {
     return a;
 }
 
-// one plan op, with its launch-span slots when bugseg_debug_set_spans armed them
+// one plan op, with its launch-span slots when bugseg_debug_set_spans armed them. Its walk direction
+// (Plan::tile_order) follows the number of launches the plan issues before it (Op::pos, counted at plan
+// build from Op::launches), so a single op (bugseg_plan_launch_op) and an op range walk as they do in the
+// whole forward. The last op of a class-fused plan issues nothing; nothing follows it.
 static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s) {
     const Plan &pl = ctx->plan;
     const Op &o = pl.ops[(size_t)i];
+    const int rev = pl.tile_order == 2 ? 1 : pl.tile_order == 1 ? (o.pos & 1) : 0;
     unsigned long long *sp = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;   // (mfma_common.h: 64 slots x 64 B)
-    if (pl.cls_on && i + 2 == (int)pl.ops.size()) { BneckArgs q = cls_fused_args(pl); q.span = sp; return launch_bneck_cls(ctx->prec, q, s); }
+    if (pl.cls_on && i + 2 == (int)pl.ops.size()) { BneckArgs q = cls_fused_args(pl); q.span = sp; q.rev = rev; return launch_bneck_cls(ctx->prec, q, s); }
     if (pl.cls_on && i + 1 == (int)pl.ops.size()) return hipSuccess;   // (ran within op i - 1)
-    if (o.kind == 1) { BneckArgs q = o.bn; q.span = sp; return launch_bneck(ctx->prec, o.bn_c, o.bn_asym, o.bn_var, q, s, o.bn_cin); }
-    if (o.kind == 2) { UpArgs q = o.up; q.span = sp; return launch_up(ctx->prec, o.up_cin, o.up_it, o.up_cout, q, s); }
+    if (o.kind == 1) { BneckArgs q = o.bn; q.span = sp; q.rev = rev; return launch_bneck(ctx->prec, o.bn_c, o.bn_asym, o.bn_var, q, s, o.bn_cin); }
+    if (o.kind == 2) { UpArgs q = o.up; q.span = sp; q.rev = rev; return launch_up(ctx->prec, o.up_cin, o.up_it, o.up_cout, q, s); }
     ConvArgs q = o.a;
     q.span = sp;
+    q.rev = rev;
     return launch_conv(ctx->prec, o.nr, o.epi, q, s);
 }
 
@@ -1980,6 +2002,31 @@ int bugseg_debug_pool_indices(bugseg_ctx *ctx, int B, int H, int W, int block, v
     hipError_t e = hipMemcpyAsync(dst, pl.idx[(size_t)block], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("pool indices copy: ") + hipGetErrorString(e));
     return BUGSEG_OK;
+}
+
+int bugseg_debug_tile_walk(int ntiles, int grid, int rev, int32_t *seq, size_t seq_n, int32_t *count) {
+    if (!seq || !count) return fail(nullptr, BUGSEG_EINVAL, "NULL argument");
+    if (ntiles <= 0 || grid <= 0 || grid % 8 || (rev != 0 && rev != 1))
+        return fail(nullptr, BUGSEG_EINVAL, "tile walk: ntiles > 0, grid a positive multiple of 8, rev 0 or 1");
+    // the kernels' loop (bneck_kernels.hip, conv_kernels.hip, init_kernels.hip): steps slot, + nslots, ...
+    const int nslots = grid >> 3, CH = tile_walk_ch(ntiles), per = (CH + nslots - 1) / nslots;
+    if (seq_n < (size_t)grid * per) return fail(nullptr, BUGSEG_EINVAL, "tile walk: seq too small");
+    for (int b = 0; b < grid; ++b) {
+        const int grp = b & 7, slot = b >> 3;
+        int n = 0;
+        for (int it = slot; it < CH; it += nslots) {
+            const int tile = tile_walk(grp, it, CH, ntiles, rev);
+            if (tile < 0) break;
+            // the two spellings the kernels use where scalar registers are short (bneck_kernels.hip)
+            if (tile_walk_at(tile_walk_base(grp, CH, ntiles, rev), it) != tile ||
+                tile_walk_flip(tile_walk_mirror(grp, CH, ntiles, rev), grp * CH + it) != tile)
+                return fail(nullptr, BUGSEG_ESTATE, "tile walk: the kernels' forms disagree with tile_walk");
+            seq[(size_t)b * per + n++] = tile;
+        }
+        count[b] = n;
+        for (int k = n; k < per; ++k) seq[(size_t)b * per + k] = -1;
+    }
+    return per;
 }
 
 int bugseg_debug_ctx_info(const bugseg_ctx *ctx, int what, int arg) {

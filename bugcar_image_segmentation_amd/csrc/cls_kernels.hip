@@ -123,6 +123,9 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
     // waves interleaved over it
     const int xcd = blockIdx.x & 7, nw = (gridDim.x >> 3) * 4, wi = (blockIdx.x >> 3) * 4 + wave;
     const int C = (groups + 7) >> 3, g0 = xcd * C, g1 = g0 + C < groups ? g0 + C : groups;
+    // step k of the XCD's run -> its group: ascending, or (a.rev) descending; past the run an out-of-range
+    // group when descending (ascending, g0 + k is a neighbour's group or out of range: harmless either way)
+    auto grp_of = [&](int k) -> int { return !a.rev ? g0 + k : k < g1 - g0 ? g1 - 1 - k : groups; };
     // tap s is a wave-uniform byte delta (the buffer load's scalar offset) from the lane's pixel,
     // valid where x + dx < Win and y + dy < Hin
     const uint32_t pixB = (uint32_t)(a.CinS * ES), rowB = (uint32_t)a.Win * pixB;
@@ -180,12 +183,12 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
     // one group: MFMAs, argmax, stores; `nxt` first receives the next group's loads (they fly during
     // this one; the two buffers alternate by unrolling, never by a runtime index).
     const auto rcls = mkbuf(a.cls_out, (uint32_t)((size_t)a.B * plane));
-    auto step = [&](int g, const Raw (&cur)[CLS_TAPS], Raw (&nxt)[CLS_TAPS], const Px &q, Px &qn) {
+    auto step = [&](int k, const Raw (&cur)[CLS_TAPS], Raw (&nxt)[CLS_TAPS], const Px &q, Px &qn) {
         // unconditional: past the last group the loads are harmless (an out-of-range group reads
         // zeros, a neighbour's group is read and dropped), and a static count of loads in flight
         // lets the waits before the MFMAs name only this group's loads (a conditional prefetch
         // made the compiler wait vmcnt(3), i.e. for the next group's first load as well).
-        load(g + nw, nxt, qn);
+        load(grp_of(k + nw), nxt, qn);
         // CLS_SPLIT1 (fp32): the four taps' hi / lo parts, scaled first when the launch scales (the same
         // parts the per-block split would make: bit-identical)
         constexpr bool S1 = F32 && CLS_SPLIT1;
@@ -262,14 +265,14 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
     };
     Raw xa[CLS_TAPS], xb[CLS_TAPS];
     Px qa, qb;
-    int g = g0 + wi;
-    if (g < g1) load(g, xa, qa);
-    while (g < g1) {
-        step(g, xa, xb, qa, qb);
-        g += nw;
-        if (g >= g1) break;
-        step(g, xb, xa, qb, qa);
-        g += nw;
+    int k = wi;
+    if (k < g1 - g0) load(grp_of(k), xa, qa);
+    while (k < g1 - g0) {
+        step(k, xa, xb, qa, qb);
+        k += nw;
+        if (k >= g1 - g0) break;
+        step(k, xb, xa, qb, qa);
+        k += nw;
     }
     span_exit(a.span);
 }

@@ -123,11 +123,11 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? (NR == 8 ? 3 : 4) : 1) c
     // XCD-aware tile walk: gridDim.x is a multiple of 8; group x = blockIdx%8 owns the contiguous
     // chunk [x*C, (x+1)*C) of tiles (speed only; any placement is correct).
     const int G = gridDim.x, grp = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = G >> 3;
-    const int C = (a.ntiles + 7) >> 3;
+    const int C = tile_walk_ch(a.ntiles);
 
     for (int i = slot; i < C; i += nslots) {
-        const int tile = grp * C + i;
-        if (tile >= a.ntiles) break;
+        const int tile = tile_walk(grp, i, C, a.ntiles, a.rev);
+        if (tile < 0) break;
         // per-lane GEMM pixel of each fragment: (frame, row, col), input-window origin and byte base
         int pn[MR], py[MR], px[MR], y0[MR], x0[MR];
         uint32_t boff[MR];

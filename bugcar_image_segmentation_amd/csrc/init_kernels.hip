@@ -146,7 +146,9 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? INIT_OCC2 : 1) init_kern
     const int dslot = qok ? dpatch : IP_RS - 1;
     // XCD-aware tile walk (see conv_kernels.hip)
     const int G = gridDim.x, grp = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = G >> 3;
-    const int CH = (ntiles + 7) >> 3;
+    const int CH = tile_walk_ch(ntiles);
+    // the tile of step `it` of this workgroup's walk, or -1 past its end (either direction: a.rev)
+    auto walk = [&](int it) { return tile_walk(grp, it, CH, ntiles, a.rev); };
     // tile -> (frame, tile row, tile column): magic-number divisions (launch_init), no scalar loops
     struct Tile { int n, ty0, tx0, iy0, ix0; };
     auto geom = [&](int tile) {
@@ -209,28 +211,28 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? INIT_OCC2 : 1) init_kern
         if (t.iy0 >= 0 && t.iy0 + IP_H <= a.Hin) store_rows(std::true_type());
         else store_rows(std::false_type());
     };
-    if (slot < CH && grp * CH + slot < ntiles) load_raw(geom(grp * CH + slot));
+    if (walk(slot) >= 0) load_raw(geom(walk(slot)));
     if constexpr (INIT_DB) {
         // prologue: the first tile's patch into buffer 0, the second tile's loads in flight
         __syncthreads();   // lut staged
-        if (slot < CH && grp * CH + slot < ntiles) {
-            store_patch(geom(grp * CH + slot), patch_buf);
-            if (slot + nslots < CH && grp * CH + slot + nslots < ntiles) load_raw(geom(grp * CH + slot + nslots));
+        if (walk(slot) >= 0) {
+            store_patch(geom(walk(slot)), patch_buf);
+            if (walk(slot + nslots) >= 0) load_raw(geom(walk(slot + nslots)));
         }
     }
     int pbuf = 0;
     for (int it = slot; it < CH; it += nslots) {
-        const int tile = grp * CH + it;
-        if (tile >= ntiles) break;
+        const int tile = walk(it);
+        if (tile < 0) break;
         const Tile tg = geom(tile);
         const int n = tg.n, ty0 = tg.ty0, tx0 = tg.tx0, iy0 = tg.iy0, ix0 = tg.ix0;
         const T *patch = patch_buf + pbuf * IP_PATCH;
         if constexpr (INIT_DB) {
             __syncthreads();   // this tile's patch complete; the other buffer's last reader (the previous tile) done
-            const int tn = tile + nslots;   // (the walk's next tile: same XCD group, next slot round)
-            if (it + nslots < CH && tn < ntiles) {
+            const int tn = walk(it + nslots);   // (the walk's next tile: same XCD group, next slot round)
+            if (tn >= 0) {
                 store_patch(geom(tn), patch_buf + (pbuf ^ 1) * IP_PATCH);
-                if (it + 2 * nslots < CH && tn + nslots < ntiles) load_raw(geom(tn + nslots));
+                if (walk(it + 2 * nslots) >= 0) load_raw(geom(walk(it + 2 * nslots)));
             }
             pbuf ^= 1;
         } else {
@@ -238,8 +240,8 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? INIT_OCC2 : 1) init_kern
             __syncthreads();   // lut staged / previous tile done with the patch
             store_patch(tg, patch_buf);
             if (INIT_PF) {
-                const int tn = tile + nslots;   // (the walk's next tile: same XCD group, next slot round)
-                if (it + nslots < CH && tn < ntiles) load_raw(geom(tn));
+                const int tn = walk(it + nslots);   // (the walk's next tile: same XCD group, next slot round)
+                if (tn >= 0) load_raw(geom(tn));
             }
             __syncthreads();
         }

@@ -170,8 +170,11 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
         for (int r = 0; r < NM; ++r)
             idn[r] = __builtin_amdgcn_raw_buffer_load_b32(ri, pv ? (int)(p * a.idxCS + r * 16 + kq * 4) : (int)OOB, 0, 0);
     };
-    if (gw < nfrag) load(gw);
-    for (int f = gw; f < nfrag; f += nw) {
+    // step k of the wave's walk -> its fragment: ascending, or (a.rev) descending from the last frame
+    auto frag_of = [&](int k) -> int { return a.rev ? nfrag - 1 - k : k; };
+    if (gw < nfrag) load(frag_of(gw));
+    for (int k = gw; k < nfrag; k += nw) {
+        const int f = frag_of(k);
         // an opaque per-fragment offset keeps the weight fragments' LDS reads inside the loop for the
         // CIN = 128 form (hoisted, all 24 of GEMM 1's A fragments sat in registers: 226 VGPRs, 2 waves
         // per SIMD; in the loop 96 VGPRs, 3 per SIMD by LDS): up C64 37.8 -> 36.5 us per 32-frame
@@ -192,7 +195,7 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
         for (int s = 0; s < KS1; ++s) xf[s] = xn[s];
 #pragma unroll
         for (int r = 0; r < NM; ++r) id[r] = idn[r];
-        if (f + nw < nfrag) load(f + nw);
+        if (k + nw < nfrag) load(frag_of(k + nw));
         f32x4 acc1[NR1];
         static_assert(B1ACC, "GEMM 1 starts from the bias");
 #pragma unroll

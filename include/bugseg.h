@@ -204,6 +204,12 @@ const char *bugseg_last_error(const bugseg_ctx *ctx);
 int bugseg_debug_parse_pack(const void *blob, size_t bytes, int precision, int *ncls);
 int bugseg_debug_polar_tables(int w, int h, int variant, int32_t *fmap, size_t fmap_n, int32_t *imap, size_t imap_n,
                               int *pw, int *ph);
+/* Test hook (host only): the tile walk of the ENet kernels (csrc/bugseg_internal.h tile_walk) for a launch
+ * of `grid` workgroups (a positive multiple of 8) over ntiles > 0 tiles, rev = 0 ascending / 1 descending.
+ * Returns per = the most tiles one workgroup walks (or a negative error code) and fills, for workgroup b,
+ * count[b] = its number of tiles and seq[b * per ..] = those tiles in the order it visits them, padded
+ * with -1. seq holds seq_n >= grid * per words, count holds grid words. */
+int bugseg_debug_tile_walk(int ntiles, int grid, int rev, int32_t *seq, size_t seq_n, int32_t *count);
 /* Test hook: a context fact. what = 0: the fused initial block normalises bytes with the exact affine
  * form (bf16 / fp16; 0 = the table), 1: fp32 range scaling switched off (BUGSEG_F32_RANGE=0 at load),
  * 2: the weights' exponent of packed convolution `arg` (fp32 range scaling; -1000 if no such conv).

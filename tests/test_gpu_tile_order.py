@@ -1,0 +1,97 @@
+"""BUGSEG_TILE_ORDER (the walk direction of the ENet launches: 0 every launch ascending, 1 alternating, 2
+every launch descending) changes the order in which tiles run and nothing else: logits and class maps are
+byte-identical under all three, in every precision, with few tiles, tile counts that are no multiple of
+8, and workgroups that walk several tiles (BUGSEG_BNECK_GRID=8). The fp32 range words are a maximum over
+the launch, so they do not depend on the order either."""
+import numpy as np
+import pytest
+import torch
+
+from bugcar_image_segmentation_amd import _native as N
+from bugcar_image_segmentation_amd import enet_spec, synthetic
+from bugcar_image_segmentation_amd.models import ENET
+from bugcar_image_segmentation_amd.pipeline import OccupancyPipeline
+
+pytestmark = pytest.mark.gpu
+
+# (2, 72, 104) and (2, 480, 640): test_fused_bottlenecks_multi_tile_walks' shapes; (3, 128, 128): the C128
+# map is one 16 x 16 tile per frame, 3 tiles for 8 XCD groups; (3, 120, 160): 15 x 20 / 30 x 40 / 60 x 80
+# maps, 3, 18 and 60 or 72 tiles per launch, no multiple of 8
+SHAPES = [(2, 72, 104), (2, 480, 640), (3, 128, 128), (3, 120, 160)]
+
+
+def _forward(weights, prec, bgr, order, monkeypatch, gpu):
+    """logits and 3-class map of a fresh context (the order is read when its plan is built). The context
+    first runs another input, and the outputs start poisoned: a tile the walk skipped would keep those
+    values, not an earlier context's correct ones that the allocator handed back."""
+    B, H, W = bgr.shape[:3]
+    monkeypatch.setenv("BUGSEG_TILE_ORDER", order)
+    m = ENET(weights=weights, precision=prec)
+    logits = torch.empty((B, m.num_classes, H, W), dtype=torch.float32, device=gpu)
+    seg = torch.empty((B, H, W), dtype=torch.uint8, device=gpu)
+    other = (255 - bgr).flip(0).contiguous()
+    m.ctx.forward_bgr(other, B, H, W, N.OUT_LOGITS_F32, logits)
+    m.ctx.forward_bgr(other, B, H, W, N.OUT_CLASS3_U8, seg)
+    torch.cuda.synchronize()
+    logits.fill_(float("nan"))
+    seg.fill_(255)
+    m.ctx.forward_bgr(bgr, B, H, W, N.OUT_LOGITS_F32, logits)
+    m.ctx.forward_bgr(bgr, B, H, W, N.OUT_CLASS3_U8, seg)
+    torch.cuda.synchronize()
+    assert not torch.isnan(logits).any() and int(seg.max()) < 255, "a pixel was never written"
+    return logits, seg
+
+
+def _same_bytes(a, b):
+    return torch.equal(a.view(torch.uint8), b.view(torch.uint8))
+
+
+@pytest.mark.parametrize("grid", [None, "8"])
+@pytest.mark.parametrize("prec", ["fp32", "fp16", "bf16"])
+@pytest.mark.parametrize("B,H,W", SHAPES)
+def test_orders_are_bit_identical(gpu, blocks, B, H, W, prec, grid, monkeypatch):
+    bgr = torch.from_numpy(synthetic.road_frames(B, H, W, seed=H + 5)).cuda()
+    if grid is not None:
+        monkeypatch.setenv("BUGSEG_BNECK_GRID", grid)
+    l0, s0 = _forward(blocks, prec, bgr, "0", monkeypatch, gpu)
+    for order in ("1", "2"):
+        l, s = _forward(blocks, prec, bgr, order, monkeypatch, gpu)
+        assert _same_bytes(l, l0), f"logits differ under order {order}"
+        assert torch.equal(s, s0), f"class map differs under order {order}"
+
+
+@pytest.mark.parametrize("grid", [None, "8"])
+def test_orders_are_bit_identical_on_the_undamped_draw(gpu, grid, monkeypatch):
+    """fp32 on the undamped draw: the range-scaled kernel bodies and their per-launch max words, reversed"""
+    und = enet_spec.build_enet(res_gamma=(0.5, 1.5))
+    B, H, W = 2, 72, 104
+    bgr = torch.from_numpy(synthetic.road_frames(B, H, W, seed=9)).cuda()
+    if grid is not None:
+        monkeypatch.setenv("BUGSEG_BNECK_GRID", grid)
+    l0, s0 = _forward(und, "fp32", bgr, "0", monkeypatch, gpu)
+    assert float(l0.abs().max()) > 65504.0, "the draw no longer leaves the f16 range: nothing is scaled"
+    for order in ("1", "2"):
+        l, s = _forward(und, "fp32", bgr, order, monkeypatch, gpu)
+        assert _same_bytes(l, l0) and torch.equal(s, s0), f"order {order}"
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16"])
+def test_unfused_plan_alternating_equals_ascending(gpu, blocks, prec, monkeypatch):
+    B, H, W = 2, 72, 104
+    bgr = torch.from_numpy(synthetic.road_frames(B, H, W, seed=11)).cuda()
+    monkeypatch.setenv("BUGSEG_NO_FUSE", "1")
+    l0, s0 = _forward(blocks, prec, bgr, "0", monkeypatch, gpu)
+    l1, s1 = _forward(blocks, prec, bgr, "1", monkeypatch, gpu)
+    assert _same_bytes(l1, l0) and torch.equal(s1, s0)
+
+
+def test_occupancy_grids_equal_under_alternating_order(gpu, blocks, monkeypatch):
+    H, W, B = 96, 128, 4
+    bev = synthetic.synthetic_bev(H, W, 200, 200)
+    frames = torch.from_numpy(synthetic.road_frames(B, H, W, seed=13)).to(gpu)
+    grids = []
+    for order in ("0", "1"):
+        monkeypatch.setenv("BUGSEG_TILE_ORDER", order)
+        pipe = OccupancyPipeline(ENET(weights=blocks, precision="fp32"), bev, 4.0, 4.0, 0.05, model_hw=(H, W))
+        grids.append(pipe.run(frames).cpu().numpy())
+    assert np.array_equal(grids[0], grids[1])
