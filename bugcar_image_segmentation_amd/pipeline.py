@@ -11,6 +11,7 @@ loop the reference's (absent) ROS node runs per frame (README.md:19; SURVEY.md Â
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -152,6 +153,31 @@ class OccupancyPipeline:
         with torch.cuda.graph(graph):
             res = self.run(frames_bgr, out)
         return graph.replay, res
+
+    def host_stream(self, batch: int, frame_hw: tuple[int, int] | None = None, depth: int = 2, graph: bool = True):
+        """A hostio.HostStream over this pipeline: pinned host frames in, pinned host grids out, the
+        copies of `depth` steps in flight beside the step itself (the reference's host-to-host loop,
+        models.py:42-44 -> bev.py:244-246, at the device path's speed)."""
+        from .hostio import HostStream
+        return HostStream(self, batch, frame_hw=frame_hw, depth=depth, graph=graph)
+
+    def run_host(self, frames_np) -> np.ndarray:
+        """One batch of host frames, (B, H0, W0, 3) uint8, -> its grids as an owned int8 array, through
+        a depth-1 HostStream kept per (B, H0, W0) (rebuilt when the calibration or the grid changed,
+        which a captured step would not see)."""
+        f = np.asarray(frames_np)
+        if f.ndim != 4 or f.shape[3] != 3 or f.dtype != np.uint8:
+            raise ValueError("frames must be a (B, H0, W0, 3) uint8 array")
+        if not hasattr(self, "_host"):
+            self._host = {}
+        key, stamp = tuple(f.shape[:3]), bytes(self._params())
+        hit = self._host.get(key)
+        if hit is None or hit[0] != stamp:
+            if hit is not None:
+                hit[1].close()
+            hit = self._host[key] = (stamp, self.host_stream(f.shape[0], frame_hw=f.shape[1:3], depth=1))
+        hit[1].put(f)
+        return hit[1].get(copy=True)
 
     def _run_forward(self, ctx, frames, x, seg, stream, split=0):
         B, H0, W0 = frames.shape[:3]
