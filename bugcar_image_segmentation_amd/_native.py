@@ -23,7 +23,8 @@ PRE_ENGINE, PRE_NCHW_F64, PRE_NCHW_F32, PRE_BGR_U8 = 0, 1, 2, 3
 
 EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_weights", "bugseg_num_classes",
             "bugseg_input_bytes", "bugseg_preprocess", "bugseg_nchw_to_input", "bugseg_enet_forward",
-            "bugseg_enet_forward_bgr", "bugseg_enet_forward_bgr_ops",
+            "bugseg_enet_forward_bgr", "bugseg_enet_forward_bgr_ops", "bugseg_enet_forward_bgr_rows",
+            "bugseg_bev_source_rows", "bugseg_debug_row_windows", "bugseg_debug_poison_arena",
             "bugseg_bev_occgrid", "bugseg_bev_workspace_bytes", "bugseg_bev_occgrid_ws", "bugseg_plan_info", "bugseg_plan_op", "bugseg_plan_launch_op",
             "bugseg_last_error",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
@@ -75,6 +76,10 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_enet_forward": (i, [vp, vp, i, i, i, i, vp, vp]),
             "bugseg_enet_forward_bgr": (i, [vp, vp, i, i, i, i, vp, vp]),
             "bugseg_enet_forward_bgr_ops": (i, [vp, vp, i, i, i, i, vp, i, i, vp]),
+            "bugseg_enet_forward_bgr_rows": (i, [vp, vp, i, i, i, i, vp, i, i, i, i, vp]),
+            "bugseg_bev_source_rows": (i, [vp, ctypes.POINTER(BevParams), i, i, ctypes.POINTER(i), ctypes.POINTER(i)]),
+            "bugseg_debug_row_windows": (i, [i, i, i, i, i, i, vp]),
+            "bugseg_debug_poison_arena": (i, [vp, i, vp]),
             "bugseg_bev_occgrid": (i, [vp, vp, i, ctypes.POINTER(BevParams), vp, vp]),
             "bugseg_bev_workspace_bytes": (sz, [ctypes.POINTER(BevParams), i]),
             "bugseg_bev_occgrid_ws": (i, [vp, vp, i, ctypes.POINTER(BevParams), vp, vp, sz, vp]),
@@ -128,6 +133,15 @@ def tile_walk(ntiles: int, grid: int, rev: int) -> list[list[int]]:
     if per < 0:
         check(per)
     return [list(seq[b * per:b * per + count[b]]) for b in range(grid)]
+
+
+def row_windows(H: int, W: int, row0: int, row1: int, tile_rows_c64: int = 8, tile_rows_c16: int = 16) -> list[tuple[int, int]]:
+    """Test hook (bugseg_debug_row_windows, host only): the half-open rows each of the forward's last six
+    launches runs for class rows [row0, row1) of an H x W frame, on the launch's own grid (include/bugseg.h)."""
+    lib = load_library()
+    win = (ctypes.c_int32 * 12)()
+    check(lib.bugseg_debug_row_windows(H, W, row0, row1, tile_rows_c64, tile_rows_c16, win))
+    return [(win[2 * k], win[2 * k + 1]) for k in range(6)]
 
 
 def require_gpu() -> None:
@@ -194,6 +208,26 @@ class Context:
         """Launches [first_op, last_op) of forward_bgr's plan only (last_op = -1: to the end)."""
         check(self.lib.bugseg_enet_forward_bgr_ops(self.h, bgr.data_ptr(), B, H, W, out_kind, out.data_ptr(),
                                                    first_op, last_op, stream_handle(stream)), self.h)
+
+    def forward_bgr_rows(self, bgr, B, H, W, out_kind, out, rows, first_op=0, last_op=-1, stream=None):
+        """forward_bgr_ops writing only output rows rows = (row0, row1) of every frame: the decoder's last
+        six launches run just the tiles those rows need (bugseg_enet_forward_bgr_rows); the other rows of
+        `out` are not written."""
+        check(self.lib.bugseg_enet_forward_bgr_rows(self.h, bgr.data_ptr(), B, H, W, out_kind, out.data_ptr(),
+                                                    int(rows[0]), int(rows[1]), first_op, last_op,
+                                                    stream_handle(stream)), self.h)
+
+    def bev_source_rows(self, params: BevParams, rows: int, cols: int) -> tuple[int, int]:
+        """The half-open class-map rows the rasteriser's result depends on for these parameters
+        (bugseg_bev_source_rows; builds the geometry's tap table if it is missing). (0, 0): none."""
+        r0, r1 = ctypes.c_int(0), ctypes.c_int(0)
+        check(self.lib.bugseg_bev_source_rows(self.h, ctypes.byref(params), rows, cols, ctypes.byref(r0),
+                                              ctypes.byref(r1)), self.h)
+        return r0.value, r1.value
+
+    def poison_arena(self, byte: int, stream=None) -> None:
+        """Test hook (bugseg_debug_poison_arena): fill the activation arena and pooling indices with `byte`."""
+        check(self.lib.bugseg_debug_poison_arena(self.h, int(byte), ctypes.c_void_p(stream_handle(stream))), self.h)
 
     def bev(self, seg, B, params: BevParams, out, stream=None):
         """bugseg_bev_occgrid_ws: the laserscan scratch comes from torch's caching allocator on the

@@ -445,7 +445,7 @@ __global__ void __launch_bounds__(256, 4) bev_occgrid_lds_kernel(const BevArgs a
 // 4 grid rows: ~1,600 workgroups at 32 frames, all resident at once (16 KB of LDS each); 8 rows (40 KB,
 // 3 per CU) left a second round of workgroups: 58.5 vs 62 us for the gather kernel
 constexpr int BEV_BAND_CAP = 16384, BEV_BAND_PF = BEV_BAND_CAP / 16 / 256;
-// per band BEV_BOXREC int4 records: (P, rows per part, 0, 0), then the box of each of its P row parts.
+// per band BEV_BOXREC int4 records: (P, rows per part, source-row span lo, hi), then the box of each of its P row parts.
 // A band whose box would exceed BEV_BAND_CAP is split into 2 or 4 row parts (the nearest bands of a
 // forward camera span many image rows), each staged and evaluated in turn by the same workgroup;
 // only a part whose single-row box still exceeds the cap gathers from global memory.
@@ -469,6 +469,7 @@ __global__ void __launch_bounds__(256) bev_bandbox_kernel(const BevArgs a, int4 
     __shared__ int red[BEV_BAND][4];
     __shared__ int4 pbox[BEV_BAND];
     __shared__ int np_rpp[2];
+    __shared__ int sred[2];
     const long cells = (long)a.occ_h * a.occ_w;
     const int band = blockIdx.x, r0 = band * BEV_BAND, r1 = min(a.occ_h, r0 + BEV_BAND);
     const int nr = r1 - r0, n = nr * a.occ_w;
@@ -476,6 +477,10 @@ __global__ void __launch_bounds__(256) bev_bandbox_kernel(const BevArgs a, int4 
     int ylo[BEV_BAND], yhi[BEV_BAND], xlo[BEV_BAND], xhi[BEV_BAND];
 #pragma unroll
     for (int k = 0; k < BEV_BAND; ++k) { ylo[k] = xlo[k] = 1 << 30; yhi[k] = xhi[k] = -(1 << 30); }
+    // the band's source-row span (bugseg_bev_source_rows): the class-map rows whose values reach a template
+    // pixel, i.e. the rows of its valid taps that carry a non-zero bilinear weight (the row sy + 1 of a
+    // tap with ay = 0 and the column sx + 1 of one with ax = 0 weigh nothing)
+    int slo = 1 << 30, shi = -(1 << 30);
     for (int i = threadIdx.x; i < n * BEV_WIN; i += 256) {
         const int c = i / BEV_WIN, k = i - c * BEV_WIN, ri = c / a.occ_w;
         const long rem = (long)r0 * a.occ_w + c;
@@ -487,12 +492,20 @@ __global__ void __launch_bounds__(256) bev_bandbox_kernel(const BevArgs a, int4 
         if (v & 12) { y_lo = min(y_lo, sy + 1); y_hi = max(y_hi, sy + 1); }
         if (v & 5) { x_lo = min(x_lo, sx); x_hi = max(x_hi, sx); }
         if (v & 10) { x_lo = min(x_lo, sx + 1); x_hi = max(x_hi, sx + 1); }
+        {
+            const bool ax = (e.y & 31u) != 0, ay = ((e.y >> 5) & 31u) != 0;
+            if ((v & 1) || ((v & 2) && ax)) { slo = min(slo, sy); shi = max(shi, sy); }
+            if (ay && ((v & 4) || ((v & 8) && ax))) { slo = min(slo, sy + 1); shi = max(shi, sy + 1); }
+        }
 #pragma unroll
         for (int q = 0; q < BEV_BAND; ++q)
             if (q == ri) { ylo[q] = min(ylo[q], y_lo); yhi[q] = max(yhi[q], y_hi); xlo[q] = min(xlo[q], x_lo); xhi[q] = max(xhi[q], x_hi); }
     }
     if (threadIdx.x < 4 * BEV_BAND) red[threadIdx.x >> 2][threadIdx.x & 3] = threadIdx.x & 1 ? -(1 << 30) : (1 << 30);
+    if (threadIdx.x < 2) sred[threadIdx.x] = threadIdx.x ? -(1 << 30) : (1 << 30);
     __syncthreads();
+    atomicMin(&sred[0], slo);
+    atomicMax(&sred[1], shi);
 #pragma unroll
     for (int q = 0; q < BEV_BAND; ++q) {
         atomicMin(&red[q][0], ylo[q]); atomicMax(&red[q][1], yhi[q]); atomicMin(&red[q][2], xlo[q]); atomicMax(&red[q][3], xhi[q]);
@@ -529,7 +542,8 @@ __global__ void __launch_bounds__(256) bev_bandbox_kernel(const BevArgs a, int4 
             pbox[0].z = -1;
         }
         np_rpp[0] = P; np_rpp[1] = rpp;
-        bbox[(size_t)band * BEV_BOXREC] = make_int4(P, rpp, 0, 0);
+        // (.z, .w: the band's source-row span [lo, hi], lo > hi when no tap carries weight; host only)
+        bbox[(size_t)band * BEV_BOXREC] = make_int4(P, rpp, sred[0], sred[1]);
         for (int k = 0; k < BEV_BAND; ++k) bbox[(size_t)band * BEV_BOXREC + 1 + k] = pbox[k];
     }
     __syncthreads();

@@ -707,6 +707,8 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
         n = t / a.phases;
         const int py = RD ? ph : ph / dt, px = RD ? 0 : ph - py * dt;   // RD: phases = row phases
         oy0 = py + dt * tyi * (tr ? TW : TH) - (CLS ? tyi : 0);    // (CLS: tiles 15 apart)
+        // row window (BneckArgs::oy_base; the decoder's regular blocks): the first tile row's image row
+        if constexpr (C != 128 && !DN && !CLS) oy0 += a.oy_base;
         ox0 = RD ? 0 : px + dt * txi * (tr ? TH : TW) - (CLS ? txi : 0);
     };
     Raw kx[KEEP ? NF2 : 1][KS1];                      // KEEP: this wave's interior fragments of x

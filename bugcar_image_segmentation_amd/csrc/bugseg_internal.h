@@ -88,6 +88,10 @@ struct ConvArgs {
     int slopes_le1;      // every slope1 / slope2 <= 1: PReLU as max(v, s*v)
     RangeArgs rg;        // fp32 mode: the input's measured range, sw[0] = the weights' exponent
     unsigned long long *span;   // launch span (bugseg_debug_set_spans): [min entry, max exit] clock, or null
+    // class kernel (cls_kernels.hip) row window: the launch covers input rows [wy0, wy0 + wrows) of every
+    // frame (M = B * wrows * Wg, mHWg divides by wrows * Wg) and writes only output rows [orow0, orow1).
+    // The full frame (finish_conv_args): wy0 = 0, wrows = Hg, [0, Hout)
+    int wy0, wrows, orow0, orow1;
 };
 
 // ---- XCD-aware tile walk, shared by every ENet kernel that walks tiles. Workgroup b of a grid that is a
@@ -183,6 +187,10 @@ struct BneckArgs {
     uint32_t cls_bytes;
     const uint8_t *lut;
     int lut_kind, ncls, csw;
+    // row window (regular C = 64 / C = 16 forms only; the C = 128, down and class-fused forms ignore it): the
+    // launch's tile row 0 starts at image row oy_base (any row: the window's first) and tiles_y / ntiles
+    // count the window's tile rows. The full frame: 0
+    int oy_base;
 };
 // tile-shape variants of the fused kernel for C channels: 0 .. bneck_variants(C) - 1
 int bneck_variants(int C);
@@ -219,6 +227,9 @@ struct UpArgs {
     int slopes_le1;
     RangeArgs rg;             // fp32 mode: sw = {pair, tconv, expansion}; n / c: e1 output, tconv output
     unsigned long long *span; // launch span (bugseg_debug_set_spans), or null
+    // row window: the launch covers input rows [y0, y0 + hwin) of every frame (output rows [2 y0, 2 (y0 +
+    // hwin))); M = B * hwin * w and mHW divides by hwin * w. The full frame: y0 = 0, hwin = h
+    int y0, hwin;
 };
 bool up_supported(int cin, int it, int cout);
 hipError_t launch_up(int prec, int cin, int it, int cout, const UpArgs &a, hipStream_t s);
@@ -285,7 +296,7 @@ constexpr int BEV_BAND = 4;
 __host__ __device__ inline int bev_bands(int occ_h) { return (occ_h + BEV_BAND - 1) / BEV_BAND; }
 constexpr int BEV_WIN = 25, BEV_SLOTS = 13;
 // table layout (bytes from its start): tap table [BEV_SLOTS][cells] uint4; the band records (per band
-// BEV_BOXREC int4: (P, rows per part, 0, 0), then its BEV_BAND row-part boxes); the compact table
+// BEV_BOXREC int4: (P, rows per part, source-row span lo, hi), then its BEV_BAND row-part boxes); the compact table
 // [BEV_WIN][cells] u32 + the outside-template mask plane [cells] u32; the work items (int2 (band,
 // part), at most BEV_BAND per band)
 constexpr int BEV_BOXREC = 5;

@@ -132,9 +132,21 @@ struct Op {
     }
 };
 
+// Row-windowed decoder (bugseg_enet_forward_bgr_rows): the rows each of the plan's last WIN_OPS ops runs
+// when only class rows [row0, row1) are wanted — in plan order the 128 -> 64 upsampling block, the two
+// stage-4 bottlenecks, the 64 -> 16 upsampling block, the stage-5 bottleneck and the class layer. y0, y1:
+// rows of the op's own grid, input rows for the upsampling blocks and the class layer (pointwise in their
+// input grid), output rows for the bottlenecks; a bottleneck also carries the tile form picked for its
+// window (pick_bneck_variant over the window's rows).
+constexpr int WIN_OPS = 6;
+struct WinOp { int y0 = 0, y1 = 0, var = 0, tr = 0, te = 1, tiles_x = 0; };   // te: image rows per tile row
+struct WinPlan { int row0 = 0, row1 = 0; WinOp op[WIN_OPS]; };
+
 struct Plan {
     int B = 0, H = 0, W = 0;
     std::vector<Op> ops;
+    std::vector<WinPlan> wins;   // windowed forms of this plan, by window (window_plan); dropped with the plan
+    size_t act_bytes = 0;        // the arena's activation and pool-index part (before the range words)
     float *words = nullptr;  // fp32 mode: RNG_SLOTS range words per measured tensor (block 0: the engine input)
     size_t words_bytes = 0;
     void *arena = nullptr;
@@ -210,7 +222,8 @@ struct bugseg_ctx {
     // BEV warp-tap tables (bev_kernels.hip bev_table_kernel), one per recent geometry (read-only
     // once built, shared by every stream); key = the geometry fields of BevArgs. pinned: used by a
     // call that was captured into a graph — never evicted while the context lives.
-    struct BevTab { std::vector<unsigned char> key; uint4 *tab = nullptr; bool pinned = false; int nitems = 0; };
+    // row0, row1: the class-map rows [row0, row1) that carry weight in some tap (bugseg_bev_source_rows)
+    struct BevTab { std::vector<unsigned char> key; uint4 *tab = nullptr; bool pinned = false; int nitems = 0; int row0 = 0, row1 = 0; };
     std::vector<BevTab> bev_tabs;
     // memory retired while a stream was capturing (a graph may reference it): freed at destroy
     std::vector<void *> graveyard;
@@ -1129,6 +1142,7 @@ struct Walker {
                         const Packed &p1 = P(4), &p2 = P(2), &p3 = P(3);
                         q.x = curp; q.idx = idx[ref]; q.out = dst;
                         q.M = B * cur.H * cur.W; q.h = cur.H; q.w = cur.W;
+                        q.y0 = 0; q.hwin = cur.H;                 // the full frame (window_plan narrows them)
                         q.idxCS = cstore(ctx->blocks[ref].attrs[0]);
                         fastdiv((uint32_t)(cur.H * cur.W), q.mHW, q.sHW);
                         fastdiv((uint32_t)cur.W, q.mW, q.sW);
@@ -1221,6 +1235,7 @@ struct Walker {
 bool finish_conv_args(ConvArgs &a, int epi, size_t es) {
     fastdiv((uint32_t)(a.Hg * a.Wg), a.mHWg, a.sHWg);
     fastdiv((uint32_t)a.Wg, a.mWg, a.sWg);
+    a.wy0 = 0; a.wrows = a.Hg; a.orow0 = 0; a.orow1 = a.Hout;   // class kernel: the full frame
     const double in_b = (double)a.B * a.Hin * a.Win * a.CinS * es;
     const double out_b = epi == EPI_CLASSES ? 0.0 : (double)a.B * a.Hout * a.Wout * a.outC * es;
     const double res_b = a.res ? (double)a.B * a.resH * a.resW * a.resCS * es : 0.0;
@@ -1301,7 +1316,84 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
     pl.words_bytes = words_bytes;
     pl.B = B; pl.H = H; pl.W = W;
     pl.arena_bytes = total;
+    pl.act_bytes = total - al(words_bytes);
+    pl.wins.clear();
     return true;
+}
+
+// ---------------------------------------------------------------- row windows of the decoder
+// Class rows [row0, row1) of an H-row frame (0 <= row0 < row1 <= H, H % 8 == 0) -> the rows each of the
+// last WIN_OPS ops must run, walked back from the class layer through the kernels' read footprints:
+//   class layer (cls_kernels.hip): input pixel (y, x) makes output rows 2y, 2y + 1 from input rows y, y + 1;
+//   bottlenecks (bneck_kernels.hip): whole tile rows, counted from the first row needed, reading one row
+//   above and below (the 3x3 middle conv);
+//   upsampling blocks (up_kernels.hip): input pixel (y, x) makes output rows 2y, 2y + 1 from input row y and
+//   the pooling indices of row y alone.
+// Coordinates are absolute and clamped to the image only. tile_rows(k, need0, need1) gives the image rows
+// per tile row of bottleneck k for the rows it must produce. win[k] = [y0, y1) (WinOp).
+template <typename F>
+void row_windows(int H, int row0, int row1, F tile_rows, int (*win)[2]) {
+    const int h2 = H / 2, h4 = H / 4, h8 = H / 8;
+    int a = row0, b = row1;
+    auto set = [&](int k) { win[k][0] = a; win[k][1] = b; };
+    auto halve = [&](int h) { a >>= 1; b = std::min((b + 1) >> 1, h); };
+    auto grow = [&](int h) { a = std::max(a - 1, 0); b = std::min(b + 1, h); };
+    auto tiles = [&](int k, int h) {
+        // whole tile rows from the first needed row on (the tile grid starts there, BneckArgs::oy_base): the
+        // fewest tiles, and every row a tile computes has its inputs inside the producer's window
+        const int t = std::max(1, tile_rows(k, a, b));
+        b = std::min(a + (b - a + t - 1) / t * t, h);
+    };
+    halve(h2); set(5);
+    b = std::min(b + 1, h2);                  // the class layer's dy = 1 taps
+    tiles(4, h2); set(4); grow(h2);
+    halve(h4); set(3);
+    tiles(2, h4); set(2); grow(h4);
+    tiles(1, h4); set(1); grow(h4);
+    halve(h8); set(0);
+}
+
+// The windowed form of the current plan for class rows [row0, row1), cached by window; nullptr = run the
+// full-frame plan: the window is the whole frame or out of range, or the plan does not end in the six
+// fused launches the windows are defined for (BUGSEG_NO_FUSE, BUGSEG_CLS_CONV, BUGSEG_CLS_FUSE, a class
+// layer the class kernel does not take).
+const WinPlan *window_plan(bugseg_ctx *ctx, int row0, int row1) {
+    Plan &pl = ctx->plan;
+    if (row0 < 0 || row1 > pl.H || row0 >= row1 || (row0 == 0 && row1 == pl.H)) return nullptr;
+    for (const WinPlan &w : pl.wins)
+        if (w.row0 == row0 && w.row1 == row1) return &w;
+    const int n = (int)pl.ops.size();
+    if (n < WIN_OPS + 1 || pl.cls_ok || std::getenv("BUGSEG_CLS_CONV")) return nullptr;
+    const Op *o = &pl.ops[(size_t)(n - WIN_OPS)];
+    auto reg = [&](const Op &q, int C, int h) {
+        return q.kind == 1 && q.bn_c == C && !q.bn_asym && q.bn_cin == 0 && q.bn.dt == 1 && q.bn.phases == 1 && q.bn.H == h;
+    };
+    const int H = pl.H;
+    if (!(o[0].kind == 2 && o[0].up.h == H / 8 && reg(o[1], 64, H / 4) && reg(o[2], 64, H / 4) && o[3].kind == 2 &&
+          o[3].up.h == H / 4 && reg(o[4], 16, H / 2) && o[5].kind == 0 && o[5].epi == EPI_CLASSES && cls_supported(o[5].a) &&
+          o[5].a.Hg == H / 2))
+        return nullptr;
+    WinPlan w;
+    w.row0 = row0; w.row1 = row1;
+    int win[WIN_OPS][2];
+    row_windows(H, row0, row1, [&](int k, int need0, int need1) {
+        // the tile form for the rows the block must produce; none efficient enough (a thin window): the full frame's
+        const Op &q = o[k];
+        WinOp &r = w.op[k];
+        int ty = 0, tx = 0, tr = 0, rd = 0;
+        int v = pick_bneck_variant(ctx, q.bn_c, false, 1, pl.B, need1 - need0, q.bn.W, ty, tx, tr, rd);
+        if (v < 0 || rd) { v = q.bn_var; tr = q.bn.tr; }
+        int th, tw, nw;
+        bneck_shape(q.bn_c, v, th, tw, nw, nullptr);
+        r.var = v; r.tr = tr;
+        r.te = tr ? tw : th;
+        r.tiles_x = tr ? (q.bn.W + th - 1) / th : (q.bn.W + tw - 1) / tw;
+        return r.te;
+    }, win);
+    for (int k = 0; k < WIN_OPS; ++k) { w.op[k].y0 = win[k][0]; w.op[k].y1 = win[k][1]; }
+    if (pl.wins.size() >= 8) pl.wins.erase(pl.wins.begin());
+    pl.wins.push_back(w);
+    return &pl.wins.back();
 }
 
 // ---------------------------------------------------------------- preprocess tables
@@ -1579,11 +1671,43 @@ static BneckArgs cls_fused_args(const Plan &pl) {
 // (Plan::tile_order) follows the number of launches the plan issues before it (Op::pos, counted at plan
 // build from Op::launches), so a single op (bugseg_plan_launch_op) and an op range walk as they do in the
 // whole forward. The last op of a class-fused plan issues nothing; nothing follows it.
-static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s) {
+// wp (a row-windowed forward, window_plan): the last WIN_OPS ops run their windows — the same arguments with
+// the per-frame extent narrowed to the window's rows and the first row as an offset; walk direction, XCD
+// grouping and range words as in the full launch, over the smaller count.
+static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const WinPlan *wp = nullptr) {
     const Plan &pl = ctx->plan;
     const Op &o = pl.ops[(size_t)i];
     const int rev = pl.tile_order == 2 ? 1 : pl.tile_order == 1 ? (o.pos & 1) : 0;
     unsigned long long *sp = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;   // (mfma_common.h: 64 slots x 64 B)
+    const int wk = i - ((int)pl.ops.size() - WIN_OPS);
+    if (wp && wk >= 0) {
+        const WinOp &w = wp->op[wk];
+        const int rows = w.y1 - w.y0;
+        if (o.kind == 1) {
+            BneckArgs q = o.bn;
+            q.span = sp; q.rev = rev;
+            q.tr = w.tr; q.tiles_x = w.tiles_x;
+            q.tiles_y = (rows + w.te - 1) / w.te;
+            q.ntiles = q.B * q.tiles_y * q.tiles_x;
+            q.oy_base = w.y0;
+            return launch_bneck(ctx->prec, o.bn_c, false, w.var, q, s, 0);
+        }
+        if (o.kind == 2) {
+            UpArgs q = o.up;
+            q.span = sp; q.rev = rev;
+            q.y0 = w.y0; q.hwin = rows;
+            q.M = (q.M / q.h) * rows;                  // B * rows * w
+            fastdiv((uint32_t)(rows * q.w), q.mHW, q.sHW);
+            return launch_up(ctx->prec, o.up_cin, o.up_it, o.up_cout, q, s);
+        }
+        ConvArgs q = o.a;
+        q.span = sp; q.rev = rev;
+        q.wy0 = w.y0; q.wrows = rows;
+        q.M = q.B * rows * q.Wg;
+        fastdiv((uint32_t)(rows * q.Wg), q.mHWg, q.sHWg);
+        q.orow0 = wp->row0; q.orow1 = wp->row1;
+        return launch_conv(ctx->prec, o.nr, o.epi, q, s);
+    }
     if (pl.cls_on && i + 2 == (int)pl.ops.size()) { BneckArgs q = cls_fused_args(pl); q.span = sp; q.rev = rev; return launch_bneck_cls(ctx->prec, q, s); }
     if (pl.cls_on && i + 1 == (int)pl.ops.size()) return hipSuccess;   // (ran within op i - 1)
     if (o.kind == 1) { BneckArgs q = o.bn; q.span = sp; q.rev = rev; return launch_bneck(ctx->prec, o.bn_c, o.bn_asym, o.bn_var, q, s, o.bn_cin); }
@@ -1595,7 +1719,7 @@ static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s) {
 }
 
 static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H, int W, int out_kind, void *out,
-                        void *stream, int first_op = 0, int last_op = -1) {
+                        void *stream, int first_op = 0, int last_op = -1, int row0 = 0, int row1 = 0) {
     if (!ctx || !in || !out) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     if (!ctx->loaded) return fail(ctx, BUGSEG_ESTATE, "no weights loaded");
     if (out_kind < BUGSEG_OUT_LOGITS_F32 || out_kind > BUGSEG_OUT_BINARY_U8) return fail(ctx, BUGSEG_EINVAL, "bad out_kind");
@@ -1633,8 +1757,10 @@ static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H,
         if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("range words: ") + hipGetErrorString(e));
     }
     pl.cls_on = pl.cls_ok && out_kind != BUGSEG_OUT_LOGITS_F32 && first_op <= nops - 2 && last_op == nops;
+    // class rows [row0, row1) only (bugseg_enet_forward_bgr_rows); null: the full-frame launches
+    const WinPlan *wp = window_plan(ctx, row0, row1);
     for (int i = first_op; i < last_op; ++i) {
-        hipError_t e = launch_op(ctx, i, (hipStream_t)stream);
+        hipError_t e = launch_op(ctx, i, (hipStream_t)stream, wp);
         if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, "conv launch " + std::to_string(i) + ": " + hipGetErrorString(e));
     }
     return BUGSEG_OK;
@@ -1652,6 +1778,11 @@ int bugseg_enet_forward_bgr(bugseg_ctx *ctx, const uint8_t *bgr, int B, int H, i
 int bugseg_enet_forward_bgr_ops(bugseg_ctx *ctx, const uint8_t *bgr, int B, int H, int W, int out_kind, void *out,
                                 int first_op, int last_op, void *stream) {
     return enet_forward(ctx, bgr, true, B, H, W, out_kind, out, stream, first_op, last_op);
+}
+
+int bugseg_enet_forward_bgr_rows(bugseg_ctx *ctx, const uint8_t *bgr, int B, int H, int W, int out_kind, void *out,
+                                 int row0, int row1, int first_op, int last_op, void *stream) {
+    return enet_forward(ctx, bgr, true, B, H, W, out_kind, out, stream, first_op, last_op, row0, row1);
 }
 
 }  // extern "C"
@@ -1816,18 +1947,15 @@ int internal_scratch(bugseg_ctx *ctx, void *stream, size_t need, bool cap, void 
     return BUGSEG_OK;
 }
 
-int bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_params *p, int8_t *out, bool own_ws,
-                void *ws, size_t ws_bytes, void *stream) {
-    if (!ctx || !seg || !p || !out) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
-    if (B <= 0 || p->in_rows <= 0 || p->in_cols <= 0 || p->warp_w <= 0 || p->warp_h <= 0 || p->occ_w <= 0 ||
+// the geometry fields of the rasteriser's arguments from the caller's parameters (checked)
+int bev_geometry(bugseg_ctx *ctx, const bugseg_bev_params *p, BevArgs &a) {
+    if (p->in_rows <= 0 || p->in_cols <= 0 || p->warp_w <= 0 || p->warp_h <= 0 || p->occ_w <= 0 ||
         p->occ_h <= 0 || p->occ_w_px <= 0 || p->occ_h_px <= 0)
         return fail(ctx, BUGSEG_EINVAL, "bad BEV geometry");
     if (p->variant != 0 && p->variant != 1) return fail(ctx, BUGSEG_EINVAL, "variant must be 0 or 1");
     if (p->laserscan != 0 && p->laserscan != 1) return fail(ctx, BUGSEG_EINVAL, "laserscan must be 0 or 1");
-    DeviceGuard g(ctx->device);
-    BevArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.seg = seg; a.B = B; a.in_rows = p->in_rows; a.in_cols = p->in_cols;
+    a.in_rows = p->in_rows; a.in_cols = p->in_cols;
     {
         // cv::invert(M) closed-form 3x3 branch (DECOMP_LU), as warpPerspective does without WARP_INVERSE_MAP
 #pragma clang fp contract(off)
@@ -1855,18 +1983,14 @@ int bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_par
     a.ify = 1.0 / ((double)p->occ_h / p->occ_h_px);
     a.ros_layout = p->ros_layout;
     a.variant = p->variant;
-    a.out = out;
-    if (p->laserscan) {
-        // check the workspace before anything is built or enqueued
-        int pw, ph;
-        if (!polar_dims(p, pw, ph)) return fail(ctx, BUGSEG_EINVAL, "laserscan grid too large for the polar tables");
-        if (!own_ws && (!ws || ws_bytes < ls_workspace_bytes(B, p, ph)))
-            return fail(ctx, BUGSEG_EINVAL, "laserscan workspace missing or smaller than bugseg_bev_workspace_bytes()");
-    }
-    const bool cap = stream_capturing(stream);
+    return BUGSEG_OK;
+}
+
+// The geometry's warp-tap table: built once on the setup stream and waited for there, then shared
+// read-only by every call on any stream. cap: the caller's stream is being captured (nothing synchronises
+// the device, and with pin the table is never evicted while the context lives).
+int bev_table(bugseg_ctx *ctx, BevArgs &a, bool cap, bugseg_ctx::BevTab *&hit, bool pin = true) {
     {
-        // the geometry's warp-tap table: built once on the setup stream and waited for there, then
-        // shared read-only by every call on any stream
         std::vector<unsigned char> key(sizeof(double) * 11 + sizeof(int) * 12);
         unsigned char *kp = key.data();
         auto put = [&](const void *v, size_t n) { std::memcpy(kp, v, n); kp += n; };
@@ -1874,7 +1998,7 @@ int bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_par
         const int ik[12] = {a.in_rows, a.in_cols, a.bw0, a.warp_w, a.warp_h, a.occ_w_px, a.occ_h_px, a.occ_w, a.occ_h,
                             a.left_x, a.top_y, 0};
         put(ik, sizeof(ik));
-        bugseg_ctx::BevTab *hit = nullptr;
+        hit = nullptr;
         for (auto &t : ctx->bev_tabs) if (t.key == key) hit = &t;
         if (!hit) {
             const size_t cells = (size_t)a.occ_h * a.occ_w;
@@ -1916,6 +2040,15 @@ int bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_par
                     const int b = near_first ? nb - 1 - i : i;
                     for (int k = 0; k < std::max(1, std::min(BEV_BAND, rec[(size_t)b * BEV_BOXREC].x)); ++k) items.push_back(make_int2(b, k));
                 }
+                // the class-map rows the rasteriser's result depends on (bugseg_bev_source_rows): the union
+                // of the bands' spans (header .z, .w; lo > hi: no tap of the band carries weight)
+                int lo = 1 << 30, hi = -(1 << 30);
+                for (int b = 0; b < nb; ++b) {
+                    const int4 h = rec[(size_t)b * BEV_BOXREC];
+                    if (h.z <= h.w) { lo = std::min(lo, h.z); hi = std::max(hi, h.w); }
+                }
+                t.row0 = lo <= hi ? std::max(lo, 0) : 0;
+                t.row1 = lo <= hi ? std::min(hi + 1, a.in_rows) : 0;
                 e = hipMemcpyAsync((unsigned char *)t.tab + bev_items_offset(a.occ_w, a.occ_h), items.data(),
                                    items.size() * sizeof(int2), hipMemcpyHostToDevice, s);
             }
@@ -1929,10 +2062,34 @@ int bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_par
             ctx->bev_tabs.push_back(std::move(t));
             hit = &ctx->bev_tabs.back();
         }
-        if (cap) hit->pinned = true;
+        if (cap && pin) hit->pinned = true;
         a.wtab = hit->tab;
         a.nitems = hit->nitems;
     }
+    return BUGSEG_OK;
+}
+
+int bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_params *p, int8_t *out, bool own_ws,
+                void *ws, size_t ws_bytes, void *stream) {
+    if (!ctx || !seg || !p || !out) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
+    if (B <= 0) return fail(ctx, BUGSEG_EINVAL, "bad BEV geometry");
+    BevArgs a;
+    int rc0 = bev_geometry(ctx, p, a);
+    if (rc0 != BUGSEG_OK) return rc0;
+    DeviceGuard g(ctx->device);
+    a.seg = seg; a.B = B;
+    a.out = out;
+    if (p->laserscan) {
+        // check the workspace before anything is built or enqueued
+        int pw, ph;
+        if (!polar_dims(p, pw, ph)) return fail(ctx, BUGSEG_EINVAL, "laserscan grid too large for the polar tables");
+        if (!own_ws && (!ws || ws_bytes < ls_workspace_bytes(B, p, ph)))
+            return fail(ctx, BUGSEG_EINVAL, "laserscan workspace missing or smaller than bugseg_bev_workspace_bytes()");
+    }
+    const bool cap = stream_capturing(stream);
+    bugseg_ctx::BevTab *hit = nullptr;
+    rc0 = bev_table(ctx, a, cap, hit);
+    if (rc0 != BUGSEG_OK) return rc0;
     if (p->laserscan) {
         int rc = prepare_polar(ctx, p, a, cap);
         if (rc != BUGSEG_OK) return rc;
@@ -1954,6 +2111,25 @@ extern "C" {
 
 int bugseg_bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_params *p, int8_t *out, void *stream) {
     return bev_occgrid(ctx, seg, B, p, out, true, nullptr, 0, stream);
+}
+
+int bugseg_bev_source_rows(bugseg_ctx *ctx, const bugseg_bev_params *p, int in_rows, int in_cols, int *row0, int *row1) {
+    if (!ctx || !p || !row0 || !row1) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
+    if (in_rows != p->in_rows || in_cols != p->in_cols)
+        return fail(ctx, BUGSEG_EINVAL, "source rows: the class map is not the size the parameters name");
+    BevArgs a;
+    int rc = bev_geometry(ctx, p, a);
+    if (rc != BUGSEG_OK) return rc;
+    DeviceGuard g(ctx->device);
+    // (the entry takes no stream, so it behaves as under a capture: the build runs and is waited for on the
+    // setup stream and an evicted table is kept until destroy, never freed behind a device sync; the table
+    // is pinned by the first captured bugseg_bev_occgrid call that uses it)
+    bugseg_ctx::BevTab *hit = nullptr;
+    rc = bev_table(ctx, a, true, hit, false);
+    if (rc != BUGSEG_OK) return rc;
+    *row0 = hit->row0;
+    *row1 = hit->row1;
+    return BUGSEG_OK;
 }
 
 size_t bugseg_bev_workspace_bytes(const bugseg_bev_params *p, int B) {
@@ -2027,6 +2203,29 @@ int bugseg_debug_tile_walk(int ntiles, int grid, int rev, int32_t *seq, size_t s
         for (int k = n; k < per; ++k) seq[(size_t)b * per + k] = -1;
     }
     return per;
+}
+
+int bugseg_debug_row_windows(int H, int W, int row0, int row1, int tile_rows_c64, int tile_rows_c16, int32_t *win) {
+    (void)W;                                          // (the windows are whole rows: the width plays no part)
+    if (!win) return fail(nullptr, BUGSEG_EINVAL, "NULL argument");
+    if (H <= 0 || H % 8 || W <= 0 || W % 8) return fail(nullptr, BUGSEG_EINVAL, "H and W must be positive multiples of 8");
+    if (row0 < 0 || row1 > H || row0 >= row1) return fail(nullptr, BUGSEG_EINVAL, "row windows: 0 <= row0 < row1 <= H");
+    if (tile_rows_c64 <= 0 || tile_rows_c16 <= 0) return fail(nullptr, BUGSEG_EINVAL, "row windows: tile rows must be positive");
+    int w[WIN_OPS][2];
+    row_windows(H, row0, row1, [&](int k, int, int) { return k == 4 ? tile_rows_c16 : tile_rows_c64; }, w);
+    for (int k = 0; k < WIN_OPS; ++k) { win[2 * k] = w[k][0]; win[2 * k + 1] = w[k][1]; }
+    return BUGSEG_OK;
+}
+
+int bugseg_debug_poison_arena(bugseg_ctx *ctx, int byte, void *stream) {
+    if (!ctx) return fail(ctx, BUGSEG_EINVAL, "NULL ctx");
+    Plan &pl = ctx->plan;
+    if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
+    DeviceGuard g(ctx->device);
+    // activations and pooling indices; the range words after them are cleared by every forward
+    hipError_t e = hipMemsetAsync(pl.arena, byte & 255, pl.act_bytes, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("poison arena: ") + hipGetErrorString(e));
+    return BUGSEG_OK;
 }
 
 int bugseg_debug_ctx_info(const bugseg_ctx *ctx, int what, int arg) {

@@ -116,7 +116,10 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
         }
     }
     const auto rin = mkbuf(a.in, a.in_bytes);
-    const int HWg = a.Hg * a.Wg;
+    // row window (ConvArgs::wy0, wrows): the walk covers input rows [wy0, wy0 + wrows) of every frame; a
+    // window pixel p of frame n is pixel p + n * wskip + woff of the tensor (the full frame: both 0)
+    const int HWg = a.wrows * a.Wg;
+    const uint32_t wskip = (uint32_t)((a.Hg - a.wrows) * a.Wg), woff = (uint32_t)(a.wy0 * a.Wg);
     const size_t plane = (size_t)a.Hout * a.Wout;
     const int groups = (a.M + 31) >> 5;
     // XCD-aware: XCD x = blockIdx % 8 walks the contiguous run [x*C, (x+1)*C) of 32-pixel groups, its
@@ -147,9 +150,10 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
         const bool wrap = q.x >= a.Wg;
         q.x = wrap ? q.x - a.Wg : q.x;
         q.y = y0 + (wrap ? 1 : 0);
-        const bool wrapn = q.y >= a.Hg;
-        q.y = wrapn ? 0 : q.y;
-        q.n = n0 + (wrapn ? 1 : 0);          // (the logits path only)
+        const bool wrapn = q.y >= a.wrows;
+        q.y = (wrapn ? 0 : q.y) + a.wy0;     // the row in the whole frame
+        q.n = n0 + (wrapn ? 1 : 0);
+        q.p += (uint32_t)q.n * wskip + woff; // the pixel in the whole tensor
         return q;
     };
     // (the group's pixel is computed once, with its loads, and handed to the step that consumes them)
@@ -238,7 +242,7 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
                 }
             }
             if (!done) taps(b, acc, std::false_type());
-            if (LOGITS && q.ok) {
+            if (LOGITS && q.ok && 2 * q.y + b >= a.orow0 && 2 * q.y + b < a.orow1) {
                 float *lo = a.logits_out + (size_t)q.n * a.ncls * plane + (size_t)(2 * q.y + b) * a.Wout + 2 * q.x + h;
 #pragma unroll
                 for (int c = 0; c < 16; ++c)
@@ -259,8 +263,10 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
             pl32swap(c0, c1);
             // (32-bit offsets through a buffer descriptor: a masked lane's store is dropped)
             const uint32_t o = 4u * q.p - 2u * (uint32_t)q.x + (uint32_t)(2 * h * a.Wg);
+            // (a row window's first / last output row may be the other row of its input row: not written)
+            const bool wr = q.ok && 2 * q.y + h >= a.orow0 && 2 * q.y + h < a.orow1;
             if (!(CLS_ABL & 4) || c0 == 77)
-                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(c0 | (c1 << 8)), rcls, q.ok ? (int)o : (int)OOB, 0, CLS_AUX);
+                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(c0 | (c1 << 8)), rcls, wr ? (int)o : (int)OOB, 0, CLS_AUX);
         }
     };
     Raw xa[CLS_TAPS], xb[CLS_TAPS];

@@ -126,7 +126,10 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
     const auto rx = mkbuf(a.x, a.x_bytes);
     const auto ri = mkbuf(a.idx, a.idx_bytes);
     const auto ro = mkbuf(a.out, a.out_bytes);
-    const int hw = a.h * a.w;
+    // row window (UpArgs::y0, hwin): the walk covers input rows [y0, y0 + hwin) of every frame; a window
+    // pixel p of frame n is pixel p + n * skip + off0 of the tensor (the full frame: skip = off0 = 0)
+    const int hw = a.hwin * a.w;
+    const int skip = (a.h - a.hwin) * a.w, off0 = a.y0 * a.w;
     const int nfrag = (a.M + 15) >> 4;
     const int gw = blockIdx.x * (NT / 64) + __builtin_amdgcn_readfirstlane(tid >> 6), nw = gridDim.x * (NT / 64);
     // fp32 mode range scaling (bugseg_internal.h RangeArgs): x measured by its producer, e1's output and
@@ -161,8 +164,9 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
     Raw xn[KS1];
     uint32_t idn[NM];
     auto load = [&](int f) {
-        const int p = f * 16 + col;
-        const bool pv = p < a.M;
+        const int pw = f * 16 + col;
+        const bool pv = pw < a.M;
+        const int p = pw + (int)fdiv(pv ? (uint32_t)pw : 0u, a.mHW, a.sHW) * skip + off0;
 #pragma unroll
         for (int s = 0; s < KS1; ++s) bld8(xn[s], rx, pv ? (uint32_t)(p * CIN + s * 32 + kq * 8) * ES : OOB);
         // pooling indices of this pixel's main channels (one byte per channel: window position)
@@ -185,7 +189,7 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
         const int p = f * 16 + col;
         const bool pv = p < a.M;
         const uint32_t pp = pv ? (uint32_t)p : 0u;
-        const int n = (int)fdiv(pp, a.mHW, a.sHW), rr = (int)pp - n * hw;
+        const int n = (int)fdiv(pp, a.mHW, a.sHW), rr = (int)pp - n * hw + off0;   // rr: pixel of the whole frame
         const int y = (int)fdiv((uint32_t)rr, a.mW, a.sW), x = rr - y * a.w;
 
         // ---- GEMM 1: [main; e1] = W1 . x  (the block input read once, 16 B per lane per k-step)
@@ -236,7 +240,7 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
             const int po = f * 16 + (col ^ 8);
             pv_o = po < a.M;
             const uint32_t ppo = pv_o ? (uint32_t)po : 0u;
-            const int no = (int)fdiv(ppo, a.mHW, a.sHW), rro = (int)ppo - no * hw;
+            const int no = (int)fdiv(ppo, a.mHW, a.sHW), rro = (int)ppo - no * hw + off0;
             const int yo = (int)fdiv((uint32_t)rro, a.mW, a.sW), xo = rro - yo * a.w;
             obase_o = pv_o ? (uint32_t)((no * 2 * a.h + 2 * yo) * (2 * a.w) + 2 * xo) : 0u;
         }

@@ -26,7 +26,8 @@ class OccupancyPipeline:
 
     def __init__(self, model: ENET, bev: bev_transform_tools, grid_w_m: float, grid_h_m: float, cell_m: float,
                  model_hw: tuple[int, int] | None = None, ros_layout: bool = False, streams: int = 1,
-                 binary: bool = False, stream_priority: int = 0, chain_forwards: bool = False, shard_offset: int = 0):
+                 binary: bool = False, stream_priority: int = 0, chain_forwards: bool = False, shard_offset: int = 0,
+                 window_rows: bool = True):
         """binary=True is the predict_binary + create_occupancy_grid_binary pairing (models.py:70-82,
         bev.py:97-165): class maps through the binary LUT, the binary rasteriser; in the laserscan-like
         mode its output is the reference's pair, (2, B, ...) (bev.py:164). stream_priority is the HIP
@@ -36,7 +37,12 @@ class OccupancyPipeline:
         instead of all shards' forwards running together and their BEVs together at the end.
         shard_offset=k > 0 starts shard i+1 when shard i has reached its k-th launch (an
         event between launches k-1 and k of its forward), so the shards run different layers side by
-        side instead of the same layer at the same time."""
+        side instead of the same layer at the same time.
+        window_rows=True computes only the class-map rows the rasteriser reads for this calibration
+        (Context.bev_source_rows: for a forward-looking camera, the rows below the horizon): the decoder's
+        last six launches run just the tiles those rows need (Context.forward_bgr_rows). The grids are the
+        same; the rows of the internal class map that nothing samples are not computed. A calibration
+        that samples the whole image, or window_rows=False, makes the full-frame calls."""
         self.model = model
         self.binary = binary
         self.bev = bev
@@ -54,8 +60,12 @@ class OccupancyPipeline:
         self.shard_offset = int(shard_offset)
         self._ctxs = [model.ctx]
         self._streams = []
+        self.window_rows = bool(window_rows)
+        self._windowed = False       # the forwards of the run in progress are windowed
+        self._spans = {}             # (context, calibration) -> the class-map rows the rasteriser reads
         self._x = None
-        self._seg = None
+        self._seg_raw = None         # the class maps as the last run left them (windowed: its rows only)
+        self._seg_partial = None     # the last run was windowed: (frames, shard bounds) to complete _seg from
         self._grid = None
 
     def _shard_ctxs(self, dev: torch.device):
@@ -69,9 +79,25 @@ class OccupancyPipeline:
     def _bufs(self, B: int, dev: torch.device):
         if self._x is None or self._x.shape[0] != B or self._x.device != dev:
             self._x = torch.empty((B, self.H, self.W, 3), dtype=torch.uint8, device=dev)   # resized BGR
-            self._seg = torch.empty((B, self.H, self.W), dtype=torch.uint8, device=dev)
+            # (zeros: the rows a windowed forward never writes are deterministic)
+            self._seg_raw = torch.zeros((B, self.H, self.W), dtype=torch.uint8, device=dev)
+            self._seg_partial = None
             self._grid = torch.empty(self._grid_shape(B), dtype=torch.int8, device=dev)
-        return self._x, self._seg, self._grid
+        return self._x, self._seg_raw, self._grid
+
+    @property
+    def _seg(self):
+        """The whole class maps of the last run. After a windowed run the rows outside the window are
+        computed first: the full forward on that run's frames, shard by shard on the contexts that ran
+        them, on the current stream."""
+        part, self._seg_partial = self._seg_partial, None
+        if part is not None:
+            frames, bounds = part
+            st = torch.cuda.current_stream(frames.device)
+            for i in range(len(bounds) - 1):
+                s, e = bounds[i], bounds[i + 1]
+                self._run_forward(self._ctxs[i], frames[s:e], self._x[s:e], self._seg_raw[s:e], st, window=False)
+        return self._seg_raw
 
     def _params(self):
         return self.bev.occupancy_params(*self.grid, ros_layout=self.ros_layout, binary=self.binary)
@@ -93,8 +119,11 @@ class OccupancyPipeline:
         if tuple(out.shape) != tuple(grid.shape) or out.dtype != torch.int8 or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous int8 tensor of shape {tuple(grid.shape)}")
         p = self._params()
+        self._seg_partial = None
         if self.streams == 1 or B < self.streams:
             self._run_shard(self.model.ctx, frames, x, seg, out, p, None)
+            if self._windowed:
+                self._seg_partial = (frames, [0, B])
             return out
         pair = self.binary and bool(p.laserscan)
         ctxs, streams = self._shard_ctxs(frames.device)
@@ -125,6 +154,8 @@ class OccupancyPipeline:
                     self._run_shard(ctxs[i], frames[s:e], x[s:e], seg[s:e], out[s:e], p, st, forward=not split_done)
         for st in streams[: self.streams - 1]:
             main.wait_stream(st)
+        if self._windowed:
+            self._seg_partial = (frames, bounds)
         return out
 
     def _pair_buf(self, i, shape, dev):
@@ -179,21 +210,45 @@ class OccupancyPipeline:
         hit[1].put(f)
         return hit[1].get(copy=True)
 
-    def _run_forward(self, ctx, frames, x, seg, stream, split=0):
+    def _source_rows(self, ctx):
+        """The class-map rows the rasteriser reads for the current calibration, or None for the whole
+        frame (window_rows off, or nothing to skip); asked of the library once per context and calibration."""
+        if not self.window_rows:
+            return None
+        p = self._params()
+        key = (id(ctx), bytes(p))
+        if key not in self._spans:
+            r0, r1 = ctx.bev_source_rows(p, self.H, self.W)
+            self._spans[key] = None if (r0 <= 0 and r1 >= self.H) or r0 >= r1 else (r0, r1)
+        return self._spans[key]
+
+    def _run_forward(self, ctx, frames, x, seg, stream, split=0, window=True):
         B, H0, W0 = frames.shape[:3]
         if (H0, W0) != (self.H, self.W):
             # resize only (models.py:87); colour swap + normalisation are fused into the initial block
             ctx.preprocess(frames, B, H0, W0, self.H, self.W, N.PRE_BGR_U8, x, stream)
             frames = x
         kind = N.OUT_BINARY_U8 if self.binary else N.OUT_CLASS3_U8
+        rows = self._source_rows(ctx) if window else None
+        if window:
+            self._windowed = rows is not None
+
+        def ops(first, last):
+            if rows is not None:
+                ctx.forward_bgr_rows(frames, B, self.H, self.W, kind, seg, rows, first, last, stream)
+            elif (first, last) == (0, -1):
+                ctx.forward_bgr(frames, B, self.H, self.W, kind, seg, stream)
+            else:
+                ctx.forward_bgr_ops(frames, B, self.H, self.W, kind, seg, first, last, stream)
+
         if split <= 0:
-            ctx.forward_bgr(frames, B, self.H, self.W, kind, seg, stream)
+            ops(0, -1)
             return
         # launches [0, split), an event (the next shard starts there), then the rest
-        ctx.forward_bgr_ops(frames, B, self.H, self.W, kind, seg, 0, split, stream)
+        ops(0, split)
         self._split_event = torch.cuda.Event()
         self._split_event.record(stream)
-        ctx.forward_bgr_ops(frames, B, self.H, self.W, kind, seg, split, -1, stream)
+        ops(split, -1)
 
     def _run_shard(self, ctx, frames, x, seg, out, p, stream, forward=True):
         if forward:

@@ -156,6 +156,35 @@ int bugseg_enet_forward_bgr(bugseg_ctx *ctx, const uint8_t *bgr_dev, int B, int 
 int bugseg_enet_forward_bgr_ops(bugseg_ctx *ctx, const uint8_t *bgr_dev, int B, int H, int W, int out_kind,
                                 void *out_dev, int first_op, int last_op, void *stream);
 
+/* bugseg_enet_forward_bgr_ops computing only output rows [row0, row1) of every frame. The plan is the
+ * same except for its last six launches (the 128 -> 64 upsampling block, the two stage-4 bottlenecks,
+ * the 64 -> 16 upsampling block, the stage-5 bottleneck and the class layer), which run only the tiles /
+ * pixel groups the window needs: each launch's window is the rows its consumer reads (class layer: input
+ * rows y, y + 1 for output rows 2y, 2y + 1; bottlenecks: whole tile rows counted from the first row
+ * needed, reading one row above and below; upsampling blocks: input row y for output rows 2y, 2y + 1).
+ * The encoder and stage 3 run whole
+ * frames (their dilations span the frame). Output rows outside [row0, row1) are NOT written: out_dev keeps
+ * what it held. Every out_kind is supported. [0, H), or a window that is empty or leaves [0, H), runs
+ * exactly bugseg_enet_forward_bgr_ops; so does a plan that does not end in those six fused launches
+ * (BUGSEG_NO_FUSE, BUGSEG_CLS_CONV, BUGSEG_CLS_FUSE).
+ * Rows inside the window are bit-identical to the full forward's in the bf16 / f16 modes, and in the fp32
+ * mode whenever every range exponent is 0 (the default weights): a windowed launch folds into the range
+ * words only the maxima of the tiles it runs, so where an exponent is non-zero a windowed and a full
+ * forward may pick different exponents and differ within the fp32 mode's parity bar.
+ * Meant for a consumer that reads part of the class map (bugseg_bev_source_rows). */
+int bugseg_enet_forward_bgr_rows(bugseg_ctx *ctx, const uint8_t *bgr_dev, int B, int H, int W, int out_kind,
+                                 void *out_dev, int row0, int row1, int first_op, int last_op, void *stream);
+
+/* The class-map rows [*row0, *row1) (half-open) that bugseg_bev_occgrid's result depends on for these
+ * parameters, any mode: the smallest and largest row of a warp tap that lies inside the class map and
+ * carries a non-zero bilinear weight, over the 5x5 template window of every grid cell (BORDER_CONSTANT
+ * taps read no row). Rows outside it may hold anything. in_rows / in_cols must equal p's. A property of
+ * the geometry, recorded when its warp-tap table is built; the call builds the table if it is missing, as
+ * the first bugseg_bev_occgrid call would (on the context's setup stream, waited for there: legal while a
+ * stream of the caller's is being captured). No valid tap at all: the empty window (0, 0). */
+int bugseg_bev_source_rows(bugseg_ctx *ctx, const bugseg_bev_params *p, int in_rows, int in_cols, int *row0,
+                           int *row1);
+
 /* Fused BEV rasteriser over a batch of class maps: seg_dev (B, in_rows, in_cols) u8
  * -> out_dev (B, occ_h, occ_w) int8 (or the ROS layout, see ros_layout).
  * Replaces bev_transform_tools.create_occupancy_grid (bev.py:166-246) or, with variant = 1,
@@ -210,6 +239,17 @@ int bugseg_debug_polar_tables(int w, int h, int variant, int32_t *fmap, size_t f
  * count[b] = its number of tiles and seq[b * per ..] = those tiles in the order it visits them, padded
  * with -1. seq holds seq_n >= grid * per words, count holds grid words. */
 int bugseg_debug_tile_walk(int ntiles, int grid, int rev, int32_t *seq, size_t seq_n, int32_t *count);
+/* Test hook (host only): the row windows of bugseg_enet_forward_bgr_rows for class rows [row0, row1) of an
+ * H x W frame (0 <= row0 < row1 <= H), with tiles of tile_rows_c64 / tile_rows_c16 image rows in the
+ * stage-4 / stage-5 bottlenecks (the device's plan picks its own). win[2k], win[2k + 1] = the half-open
+ * rows op k of the last six runs, on its own grid: k = 0 up 128 -> 64 (input rows, H / 8), 1, 2 the stage-4
+ * bottlenecks (output rows, H / 4), 3 up 64 -> 16 (input rows, H / 4), 4 the stage-5 bottleneck (output
+ * rows, H / 2), 5 the class layer (input rows, H / 2). */
+int bugseg_debug_row_windows(int H, int W, int row0, int row1, int tile_rows_c64, int tile_rows_c16, int32_t *win);
+/* Test hook (tests/test_gpu_row_window.py): fill the activation arena and the pooling-index tensors of the
+ * current plan with `byte`, on `stream`, so that a launch reading a row its producer did not write this
+ * forward sees the fill and not a correct row left by an earlier one. */
+int bugseg_debug_poison_arena(bugseg_ctx *ctx, int byte, void *stream);
 /* Test hook: a context fact. what = 0: the fused initial block normalises bytes with the exact affine
  * form (bf16 / fp16; 0 = the table), 1: fp32 range scaling switched off (BUGSEG_F32_RANGE=0 at load),
  * 2: the weights' exponent of packed convolution `arg` (fp32 range scaling; -1000 if no such conv).
