@@ -25,6 +25,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_input_bytes", "bugseg_preprocess", "bugseg_nchw_to_input", "bugseg_enet_forward",
             "bugseg_enet_forward_bgr", "bugseg_enet_forward_bgr_ops", "bugseg_enet_forward_bgr_rows",
             "bugseg_bev_source_rows", "bugseg_debug_row_windows", "bugseg_debug_poison_arena",
+            "bugseg_debug_stage3_windows", "bugseg_debug_plan_windows", "bugseg_debug_read_block_output",
             "bugseg_bev_occgrid", "bugseg_bev_workspace_bytes", "bugseg_bev_occgrid_ws", "bugseg_plan_info", "bugseg_plan_op", "bugseg_plan_launch_op",
             "bugseg_last_error",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
@@ -80,6 +81,9 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_bev_source_rows": (i, [vp, ctypes.POINTER(BevParams), i, i, ctypes.POINTER(i), ctypes.POINTER(i)]),
             "bugseg_debug_row_windows": (i, [i, i, i, i, i, i, vp]),
             "bugseg_debug_poison_arena": (i, [vp, i, vp]),
+            "bugseg_debug_stage3_windows": (i, [i, i, i, i, vp, vp]),
+            "bugseg_debug_plan_windows": (i, [vp, i, i, vp]),
+            "bugseg_debug_read_block_output": (i, [vp, i, vp, sz, vp]),
             "bugseg_bev_occgrid": (i, [vp, vp, i, ctypes.POINTER(BevParams), vp, vp]),
             "bugseg_bev_workspace_bytes": (sz, [ctypes.POINTER(BevParams), i]),
             "bugseg_bev_occgrid_ws": (i, [vp, vp, i, ctypes.POINTER(BevParams), vp, vp, sz, vp]),
@@ -142,6 +146,21 @@ def row_windows(H: int, W: int, row0: int, row1: int, tile_rows_c64: int = 8, ti
     win = (ctypes.c_int32 * 12)()
     check(lib.bugseg_debug_row_windows(H, W, row0, row1, tile_rows_c64, tile_rows_c16, win))
     return [(win[2 * k], win[2 * k + 1]) for k in range(6)]
+
+
+def stage3_windows(h: int, y0: int, y1: int, blocks) -> list[tuple[int, int]]:
+    """Test hook (bugseg_debug_stage3_windows, host only): the output rows each stage-3 block runs when the
+    128 -> 64 block reads rows [y0, y1) of the h-row stage-3 output. blocks: per block, nearest the decoder
+    first, (asymmetric, dilation, row-dilated tiles, rows of its full-frame launch, rows per windowed tile row).
+    The list ends where the walk stops (include/bugseg.h)."""
+    lib = load_library()
+    flat = [int(v) for b in blocks for v in b]
+    blk = (ctypes.c_int32 * max(1, len(flat)))(*flat)
+    win = (ctypes.c_int32 * max(1, 2 * len(blocks)))()
+    m = lib.bugseg_debug_stage3_windows(h, y0, y1, len(blocks), blk, win)
+    if m < 0:
+        check(m)
+    return [(win[2 * k], win[2 * k + 1]) for k in range(m)]
 
 
 def require_gpu() -> None:
@@ -228,6 +247,20 @@ class Context:
     def poison_arena(self, byte: int, stream=None) -> None:
         """Test hook (bugseg_debug_poison_arena): fill the activation arena and pooling indices with `byte`."""
         check(self.lib.bugseg_debug_poison_arena(self.h, int(byte), ctypes.c_void_p(stream_handle(stream))), self.h)
+
+    def plan_windows(self, rows) -> list[tuple[int, int, int, int, int]]:
+        """Test hook (bugseg_debug_plan_windows): the stage-3 windows the current plan runs for class rows
+        rows = (row0, row1), nearest the decoder first: (plan op, first row, end row, tile variant, tiles per frame)."""
+        win = (ctypes.c_int32 * 10)()
+        m = self.lib.bugseg_debug_plan_windows(self.h, int(rows[0]), int(rows[1]), win)
+        if m < 0:
+            check(m, self.h)
+        return [tuple(win[5 * k:5 * k + 5]) for k in range(m)]
+
+    def read_block_output(self, op: int, out, stream=None) -> None:
+        """Test hook (bugseg_debug_read_block_output): the output of fused bottleneck launch `op` into `out`."""
+        check(self.lib.bugseg_debug_read_block_output(self.h, op, out.data_ptr(), out.numel() * out.element_size(),
+                                                      ctypes.c_void_p(stream_handle(stream))), self.h)
 
     def bev(self, seg, B, params: BevParams, out, stream=None):
         """bugseg_bev_occgrid_ws: the laserscan scratch comes from torch's caching allocator on the

@@ -187,7 +187,9 @@ void bneck_shape(int C, int v, int &th, int &tw, int &nw, int *rd) {
 // tile's loads are in flight (a wait for the range words alone at kernel start cost the C128 launches
 // ~4 us) and, if some exponent is non-zero, drains its loads and returns before computing anything —
 // the kernel then runs the scaled body from the start.
-template <typename T, int C, bool ASYM, int V, bool TR, int CI, bool SCL, int FC = -1>
+// WIN: the row-windowed fp32 C = 128 forms (BneckArgs::oy_base / oy_end; bneck_win_kernel below). Every line it
+// adds is under `if constexpr (WIN ...)`, so the unwindowed instantiations compile to the code they had.
+template <typename T, int C, bool ASYM, int V, bool TR, int CI, bool SCL, int FC = -1, bool WIN = false>
 __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     using Raw = typename Tr<T>::Raw;
     using WRaw = typename WTr<T>::Raw;   // weight operand (fp32 mode: split-f16 parts)
@@ -235,6 +237,9 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     constexpr int G3 = IS / 8;                        // expand k groups (<= 4: one step)
     constexpr bool RD = BShape<C, V>::RD;
     static_assert(!(RD && ASYM), "row-dilated tiles are for 3x3 blocks");
+    static_assert(!WIN || (sizeof(T) == 4 && C == 128 && CI == 0 && FC < 0 && !TR && (ASYM || (RD && TW % 16 == 0))),
+                  "windowed C128 forms: fp32, asymmetric plain tiles or row-dilated tiles");
+    constexpr bool WRD = WIN && RD;                   // row-dilated window: fragments past its last row are skipped
     constexpr int RY = ASYM ? 2 : 1;                  // halo rows / columns of the middle conv (tile coordinates)
     constexpr int RX = RD ? 0 : RY;                   // row-dilated tiles span the width: no column halo
     constexpr int HWW = TW + 2 * RX, HR = (TH + 2 * RY) * HWW;
@@ -709,6 +714,10 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
         oy0 = py + dt * tyi * (tr ? TW : TH) - (CLS ? tyi : 0);    // (CLS: tiles 15 apart)
         // row window (BneckArgs::oy_base; the decoder's regular blocks): the first tile row's image row
         if constexpr (C != 128 && !DN && !CLS) oy0 += a.oy_base;
+        // windowed C128 forms: plain tiles as above; row-dilated tiles start at the phase's first row >= oy_base
+        // (dt a power of two: the runtime plans no other window)
+        if constexpr (WIN && !RD) oy0 += a.oy_base;
+        if constexpr (WRD) oy0 += a.oy_base - py + ((py - a.oy_base) & (dt - 1));
         ox0 = RD ? 0 : px + dt * txi * (tr ? TH : TW) - (CLS ? txi : 0);
     };
     Raw kx[KEEP ? NF2 : 1][KS1];                      // KEEP: this wave's interior fragments of x
@@ -733,6 +742,19 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
         }
         int n, oy0, ox0;
         tile_geom(tile, n, oy0, ox0);
+        // WRD: the tile's first nlive rows lie inside the window (all three phases run for their fragments); row
+        // nlive is only the t0 halo of the row above it (phase 1); later rows are skipped. A fragment's row is
+        // wave-uniform, so these are scalar branches
+        int nlive = TH;
+        if constexpr (WRD) {
+            nlive = 0;
+#pragma unroll
+            for (int i = 0; i < TH; ++i) nlive += oy0 + dt * i < a.oy_end ? 1 : 0;
+        }
+        auto live = [&](int f) -> bool { return !WRD || (f * 16) / TW < nlive; };
+        auto need1 = [&](int f) -> bool { return !WRD || (nlive > 0 && (f * 16) / TW <= nlive); };
+        // border fragment fb: the halo row above the tile (needed with any live row), or the one below (with the last)
+        auto needb = [&](int fb) -> bool { return !WRD || (fb * 16 < HWW ? nlive > 0 : nlive == TH); };
         float tmo = 0.f;                              // CLS, fp32: this lane's max |out| over the tile
         // the next tile of this workgroup's walk (PREF)
         const bool has_next = PREF && it + nslots < lim;
@@ -955,7 +977,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             if (!pref) {
 #pragma unroll
                 for (int j = 0; j < NF2; ++j)
-                    if (wave + NW * j < NFT) kok[j] = load_h(int_h(wave + NW * j), true, kx[j]);   // wave-uniform
+                    if (wave + NW * j < NFT && need1(wave + NW * j)) kok[j] = load_h(int_h(wave + NW * j), true, kx[j]);   // wave-uniform
             }
             auto load_b = [&](int k) {
                 const int b = (wb + NW * k) * 16 + col;
@@ -968,7 +990,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             constexpr int NBE = BNECK_NBE >= 0 ? BNECK_NBE : C == 128 && !RD && !ASYM && sizeof(T) == 2 ? 1 : 0;
 #pragma unroll
             for (int k = 0; k < NBE && k < NBW; ++k)
-                if (wb + NW * k < NFB) load_b(k);     // wave-uniform
+                if (wb + NW * k < NFB && needb(wb + NW * k)) load_b(k);     // wave-uniform
             // (x loads touch no LDS, so they go ahead of the barrier that frees ts). The first tile
             // waits for the weight LDS-DMA only: it was issued before this wave's x loads, and vmcnt
             // retires in order, so "at most nld outstanding" leaves the x loads in flight for the
@@ -977,9 +999,9 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 int nld = 0;
                 constexpr int LPS = sizeof(T) == 4 ? 2 : 1;   // 16-B loads per k-step chunk (fp32: two)
 #pragma unroll
-                for (int j = 0; j < NF2; ++j) nld += wave + NW * j < NFT ? KS1 * LPS : 0;
+                for (int j = 0; j < NF2; ++j) nld += wave + NW * j < NFT && need1(wave + NW * j) ? KS1 * LPS : 0;
 #pragma unroll
-                for (int k = 0; k < NBE && k < NBW; ++k) nld += wb + NW * k < NFB ? KS1 * LPS : 0;
+                for (int k = 0; k < NBE && k < NBW; ++k) nld += wb + NW * k < NFB && needb(wb + NW * k) ? KS1 * LPS : 0;
                 vm_wait_upto(BNECK_GLDS_PARTIAL ? (nld < 24 ? nld & ~1 : 24) : 0);   // (fewer outstanding: still after the weights)
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -995,11 +1017,13 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             }
 #pragma unroll
             for (int j = 0; j < NF2; ++j)
-                if (wave + NW * j < NFT) proj(int_h(wave + NW * j), true, kok[j], kx[j]);
+                if (wave + NW * j < NFT && need1(wave + NW * j)) proj(int_h(wave + NW * j), true, kok[j], kx[j]);
 #pragma unroll
             for (int k = 0; k < NBW; ++k) {
                 const int fb = wb + NW * k;
                 if (fb >= NFB) break;
+                if constexpr (WRD)
+                    if (!needb(fb)) continue;
                 if (k >= NBE) load_b(k);
                 proj(bh[k], fb * 16 + col < NBD, bok[k], bx[k]);
             }
@@ -1225,6 +1249,8 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #pragma unroll
                 for (int j = 0; j < NF2; ++j) {
                     if (wave + NW * j >= NFT) continue;       // wave-uniform
+                    if constexpr (WRD)
+                        if (!live(wave + NW * j)) continue;
                     int p = (wave + NW * j) * 16 + col;
                     if constexpr (NPX % 16 != 0) p = p < NPX ? p : 0;   // partial fragment: read anything, discarded
                     const int oy = p / TW, ox = p - oy * TW;
@@ -1471,6 +1497,8 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #pragma unroll
         for (int j = 0; j < NF2; ++j) {
             if (wave + NW * j >= NFT) break;              // wave-uniform
+            if constexpr (WRD)
+                if (!live(wave + NW * j)) continue;
             const uint32_t po = pix_base(wave + NW * j, col);
             // kept fp32 x (KEEPF) / pooled fp32 main branch (DKEEP) -> residual quads in place: chunk s
             // (lane kq: channels 32 s + 8 kq .. + 7) becomes .a = row 2 s, .b = row 2 s + 1
@@ -1748,6 +1776,15 @@ __global__ void __launch_bounds__((BShape<C, V>::NW * 64), (sizeof(T) == 2 ? BSh
     }
 }
 
+// The row-windowed fp32 C = 128 forms (bneck_body WIN): their own kernels, so the unwindowed ones keep their
+// symbols and code
+template <typename T, int C, bool ASYM, int V>
+__global__ void __launch_bounds__((BShape<C, V>::NW * 64), BNECK_F32_OCC128) bneck_win_kernel(const BneckArgs a) {
+    static_assert(sizeof(T) == 4 && C == 128, "windowed forms: fp32 C = 128");
+    const float rl = rng_lane(a.rg);
+    if (!bneck_body<T, C, ASYM, V, false, 0, false, -1, true>(a, rl)) bneck_body<T, C, ASYM, V, false, 0, true, -1, true>(a, rl);
+}
+
 // C = 16 with the class layer fused (FC = the class map's LUT kind); launch bounds as the C = 16 form
 template <typename T, int FC>
 __global__ void __launch_bounds__(256, (sizeof(T) == 2 ? BShape<16, 0>::OCC : BNECK_F32_OCC16)) bneck_cls_kernel(const BneckArgs a) {
@@ -1815,7 +1852,15 @@ static const void *kfun_down(int C, int v, int cin) {
     return nullptr;
 }
 
-static const void *bneck_fun(int prec, int C, bool asym, int v, bool tr, int cin) {
+static const void *bneck_fun(int prec, int C, bool asym, int v, bool tr, int cin, bool win = false) {
+    if (win) {
+        if (prec != PREC_F32 || C != 128 || tr || cin > 0) return nullptr;
+        if (asym && v == 0) return (const void *)bneck_win_kernel<float, 128, true, 0>;
+        if (asym && v == 1) return (const void *)bneck_win_kernel<float, 128, true, 1>;
+        if (asym && v == 4) return (const void *)bneck_win_kernel<float, 128, true, 4>;   // (the small-batch form)
+        if (!asym && v == 2) return (const void *)bneck_win_kernel<float, 128, false, 2>;
+        return nullptr;
+    }
     if (cin > 0)
         return asym || tr ? nullptr
                : prec == PREC_BF16 ? kfun_down<__bf16>(C, v, cin)
@@ -1825,25 +1870,26 @@ static const void *bneck_fun(int prec, int C, bool asym, int v, bool tr, int cin
                                                             : kfun<float>(C, asym, v, tr);
 }
 
-int bneck_slots_per_cu(int prec, int C, bool asym, int v, bool tr, int cin) {
+int bneck_slots_per_cu(int prec, int C, bool asym, int v, bool tr, int cin, bool win) {
     if (C == 128 && v == BNECK2_V) {
+        if (win) return 0;
         // planned only with BUGSEG_BNECK2=1: measured slower (round 6, B = 64, A/B on one box: 103 vs 87 us
         // per launch; bneck2_kernels.hip says why)
         const char *on = std::getenv("BUGSEG_BNECK2");
         return prec == PREC_F32 && !asym && !tr && cin == 0 && on && *on == '1' ? bneck2_slots_per_cu() : 0;
     }
     // (cached per device and form: launch_bneck asks on every launch; bugseg_runtime.cpp occupancy_per_cu)
-    const void *f = bneck_fun(prec, C, asym, v, tr, cin);
+    const void *f = bneck_fun(prec, C, asym, v, tr, cin, win);
     int th, tw, nw;
     bneck_shape(C, v, th, tw, nw, nullptr);
     if (!f || allow_dynamic_lds(f) != hipSuccess) return 0;
     return occupancy_per_cu(f, nw * 64, bneck_lds_bytes(prec, C, asym, v, cin));
 }
 
-hipError_t launch_bneck(int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin) {
+hipError_t launch_bneck(int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin, bool win) {
     if (C == 128 && v == BNECK2_V)
-        return prec == PREC_F32 && !asym && !a.tr && cin == 0 ? launch_bneck2(a, s) : hipErrorInvalidValue;
-    const void *f = bneck_fun(prec, C, asym, v, a.tr != 0, cin);
+        return prec == PREC_F32 && !asym && !a.tr && cin == 0 && !win ? launch_bneck2(a, s) : hipErrorInvalidValue;
+    const void *f = bneck_fun(prec, C, asym, v, a.tr != 0, cin, win);
     if (!f) return hipErrorInvalidValue;
     int th, tw, nw;
     bneck_shape(C, v, th, tw, nw, nullptr);
@@ -1862,7 +1908,7 @@ hipError_t launch_bneck(int prec, int C, bool asym, int v, const BneckArgs &a, h
     if (cap <= 0) {
         // (BUGSEG_BNECK_GRID=-k: 1/k of the resident slots, at least one per CU — leaves room for a
         // concurrent shard's launch on another stream; A/B knob)
-        const int spc = bneck_slots_per_cu(prec, C, asym, v, a.tr != 0, cin);
+        const int spc = bneck_slots_per_cu(prec, C, asym, v, a.tr != 0, cin, win);
         const int per = grid_cap < 0 ? std::max(1, spc / -grid_cap) : spc;
         cap = spc > 0 && n_cu > 0 ? per * n_cu : 2048;
     }

@@ -187,10 +187,15 @@ struct BneckArgs {
     uint32_t cls_bytes;
     const uint8_t *lut;
     int lut_kind, ncls, csw;
-    // row window (regular C = 64 / C = 16 forms only; the C = 128, down and class-fused forms ignore it): the
+    // row window (regular C = 64 / C = 16 forms; the unwindowed C = 128, down and class-fused forms ignore it): the
     // launch's tile row 0 starts at image row oy_base (any row: the window's first) and tiles_y / ntiles
     // count the window's tile rows. The full frame: 0
     int oy_base;
+    // the windowed fp32 C = 128 forms (launch_bneck win = true: the last stage-3 blocks): oy_base as above for
+    // the asymmetric forms. The row-dilated form covers output rows [oy_base, oy_end) (oy_end <= H, dt a power
+    // of two): each row phase's tiles start at its first row >= oy_base, tiles_y counts the tile rows of the
+    // longest phase, and a fragment whose row is >= oy_end is skipped, not computed and masked
+    int oy_end;
 };
 // tile-shape variants of the fused kernel for C channels: 0 .. bneck_variants(C) - 1
 int bneck_variants(int C);
@@ -201,8 +206,10 @@ void bneck_shape(int C, int v, int &th, int &tw, int &nw, int *rd = nullptr);
 // cin 16) and (128, v1, cin 64)
 size_t bneck_lds_bytes(int prec, int C, bool asym, int v, int cin = 0, bool cls = false);
 // resident workgroups per CU (occupancy API); 0 if (C, asym, v, tr, cin) is not built
-int bneck_slots_per_cu(int prec, int C, bool asym, int v, bool tr, int cin = 0);
-hipError_t launch_bneck(int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin = 0);
+// win: the row-windowed form (BneckArgs::oy_end), built for fp32 C = 128 asymmetric 16 x 16 / 20 x 16 / 8 x 16
+// and row-dilated 4 x 80 tiles; the C = 64 / 16 regular forms take their window in the plain form
+int bneck_slots_per_cu(int prec, int C, bool asym, int v, bool tr, int cin = 0, bool win = false);
+hipError_t launch_bneck(int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin = 0, bool win = false);
 // the C = 16 block with the class layer fused (variant 0, untransposed; tiles 15 apart: tiles_x =
 // ceil(W / 15), tiles_y = ceil(H / 15)); bneck_lds_bytes(..., cls = true) its LDS
 hipError_t launch_bneck_cls(int prec, const BneckArgs &a, hipStream_t s);

@@ -139,8 +139,12 @@ struct Op {
 // input grid), output rows for the bottlenecks; a bottleneck also carries the tile form picked for its
 // window (pick_bneck_variant over the window's rows).
 constexpr int WIN_OPS = 6;
-struct WinOp { int y0 = 0, y1 = 0, var = 0, tr = 0, te = 1, tiles_x = 0; };   // te: image rows per tile row
-struct WinPlan { int row0 = 0, row1 = 0; WinOp op[WIN_OPS]; };
+struct WinOp { int y0 = 0, y1 = 0, var = 0, tr = 0, te = 1, tiles_x = 0, tiles_y = 0; };   // te: image rows per tile row
+// The walk goes on into stage 3 (stage3_windows): s3[k] is the window of the (k + 1)-th op before those six, a
+// fused fp32 C = 128 bottleneck in its windowed form (launch_bneck win = true), for k < ns3 <= S3_OPS. y0, y1:
+// output rows; tiles_y: tile rows per frame (a row-dilated form: of its longest row phase).
+constexpr int S3_OPS = 2;
+struct WinPlan { int row0 = 0, row1 = 0; WinOp op[WIN_OPS]; int ns3 = 0; WinOp s3[S3_OPS]; };
 
 struct Plan {
     int B = 0, H = 0, W = 0;
@@ -1353,6 +1357,46 @@ void row_windows(int H, int row0, int row1, F tile_rows, int (*win)[2]) {
     halve(h8); set(0);
 }
 
+// The walk continued into stage 3, from the rows [y0, y1) of the h-row stage-3 output that the 128 -> 64
+// upsampling block reads, back through the blocks before it: blk[0] writes that output, blk[1] feeds blk[0], ...
+// A block's output window is the rows its consumer reads; what it reads itself reaches `reach` rows further
+// either way, clamped to the image: the dilation of a 3x3 block, 2 for the asymmetric block's 5x1 conv.
+//   plain tiles (d = 1, untransposed): whole tile rows from the first needed row, as in the decoder;
+//   tile_rows(k, need0, need1) gives the image rows per tile row of the form picked for those rows (0: none built);
+//   row-dilated tiles (d a power of two): exactly the needed rows — every row phase starts its tiles at its
+//   first needed row, and the kernel skips the fragments of rows past the window (BneckArgs::oy_end).
+// The walk stops at the first block whose window is the whole frame, whose form has no windowed kernel, or whose
+// window runs no fewer rows than its full-frame launch computes per frame (rows_full: tile rows x rows per
+// tile row; a row-dilated form: phases x tiles_y x tile rows — the rows it runs MFMAs for, in the image or not).
+// Every block before that runs the full frame, so every row a windowed tile reads was written by its producer's
+// window or by a full launch. Returns the number of windowed blocks; win[k] = [y0, y1) for k below it.
+struct S3Desc { int asym = 0, d = 1, rd = 0, rows_full = 0; };
+template <typename F>
+int stage3_windows(int h, int y0, int y1, int n, const S3Desc *blk, F tile_rows, int (*win)[2]) {
+    int a = std::max(y0, 0), b = std::min(y1, h), k = 0;
+    for (; k < n; ++k) {
+        const S3Desc &q = blk[k];
+        if (a >= b || (a == 0 && b == h) || q.d < 1) break;
+        int e = b, run;
+        if (q.rd) {
+            if (q.asym || (q.d & (q.d - 1))) break;
+            run = b - a;
+        } else {
+            if (q.d != 1) break;
+            const int t = tile_rows(k, a, b);
+            if (t <= 0) break;
+            run = (b - a + t - 1) / t * t;
+            e = std::min(a + run, h);
+        }
+        if (run >= q.rows_full) break;
+        win[k][0] = a; win[k][1] = e;
+        const int reach = q.asym ? 2 : q.d;
+        a = std::max(a - reach, 0);
+        b = std::min(e + reach, h);
+    }
+    return k;
+}
+
 // The windowed form of the current plan for class rows [row0, row1), cached by window; nullptr = run the
 // full-frame plan: the window is the whole frame or out of range, or the plan does not end in the six
 // fused launches the windows are defined for (BUGSEG_NO_FUSE, BUGSEG_CLS_CONV, BUGSEG_CLS_FUSE, a class
@@ -1391,6 +1435,51 @@ const WinPlan *window_plan(bugseg_ctx *ctx, int row0, int row1) {
         return r.te;
     }, win);
     for (int k = 0; k < WIN_OPS; ++k) { w.op[k].y0 = win[k][0]; w.op[k].y1 = win[k][1]; }
+    // on into stage 3: the ops before the 128 -> 64 block, while they are fused C = 128 bottlenecks on its input
+    // grid whose form has a windowed kernel (fp32). BUGSEG_ROW_WINDOW_S3=0: the decoder's windows only (A/B)
+    const char *s3e = std::getenv("BUGSEG_ROW_WINDOW_S3");
+    if (!(s3e && *s3e == '0')) {
+        S3Desc blk[S3_OPS];
+        int nb = 0;
+        for (; nb < S3_OPS && n - WIN_OPS - 1 - nb >= 0; ++nb) {
+            const Op &q = pl.ops[(size_t)(n - WIN_OPS - 1 - nb)];
+            if (!(q.kind == 1 && q.bn_c == 128 && q.bn_cin == 0 && q.bn.H == H / 8 && q.bn.W == o[0].up.w)) break;
+            int th, tw, nw, rd;
+            bneck_shape(128, q.bn_var, th, tw, nw, &rd);
+            blk[nb].asym = q.bn_asym; blk[nb].d = q.bn.dt; blk[nb].rd = rd;
+            blk[nb].rows_full = rd ? q.bn.phases * q.bn.tiles_y * th : q.bn.tr ? 0 : q.bn.tiles_y * th;
+            if (rd && bneck_slots_per_cu(ctx->prec, 128, false, q.bn_var, false, 0, true) <= 0) blk[nb].rows_full = 0;
+        }
+        int w3[S3_OPS][2];
+        w.ns3 = stage3_windows(H / 8, w.op[0].y0, w.op[0].y1, nb, blk, [&](int k, int need0, int need1) {
+            // the form for the rows the block must produce, among those with a windowed kernel: the picker's
+            // choice for the window, else the full frame's
+            const Op &q = pl.ops[(size_t)(n - WIN_OPS - 1 - k)];
+            WinOp &r = w.s3[k];
+            int ty = 0, tx = 0, tr = 0, rd = 0;
+            int v = pick_bneck_variant(ctx, 128, q.bn_asym, 1, pl.B, need1 - need0, q.bn.W, ty, tx, tr, rd);
+            if (v < 0 || rd || tr || bneck_slots_per_cu(ctx->prec, 128, q.bn_asym, v, false, 0, true) <= 0) v = q.bn_var;
+            if (bneck_slots_per_cu(ctx->prec, 128, q.bn_asym, v, false, 0, true) <= 0) return 0;
+            int th, tw, nw;
+            bneck_shape(128, v, th, tw, nw, nullptr);
+            r.var = v; r.tr = 0; r.te = th;
+            r.tiles_x = (q.bn.W + tw - 1) / tw;
+            return th;
+        }, w3);
+        for (int k = 0; k < w.ns3; ++k) {
+            const Op &q = pl.ops[(size_t)(n - WIN_OPS - 1 - k)];
+            WinOp &r = w.s3[k];
+            r.y0 = w3[k][0]; r.y1 = w3[k][1];
+            if (blk[k].rd) {
+                int th, tw, nw;
+                bneck_shape(128, q.bn_var, th, tw, nw, nullptr);
+                r.var = q.bn_var; r.tr = 0; r.te = th; r.tiles_x = 1;
+                r.tiles_y = ((r.y1 - r.y0 + q.bn.dt - 1) / q.bn.dt + th - 1) / th;   // the longest row phase
+            } else {
+                r.tiles_y = (r.y1 - r.y0 + r.te - 1) / r.te;
+            }
+        }
+    }
     if (pl.wins.size() >= 8) pl.wins.erase(pl.wins.begin());
     pl.wins.push_back(w);
     return &pl.wins.back();
@@ -1680,6 +1769,16 @@ static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const W
     const int rev = pl.tile_order == 2 ? 1 : pl.tile_order == 1 ? (o.pos & 1) : 0;
     unsigned long long *sp = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;   // (mfma_common.h: 64 slots x 64 B)
     const int wk = i - ((int)pl.ops.size() - WIN_OPS);
+    if (wp && wk < 0 && -wk - 1 < wp->ns3) {
+        // a stage-3 block in its windowed form (WinPlan::s3)
+        const WinOp &w = wp->s3[-wk - 1];
+        BneckArgs q = o.bn;
+        q.span = sp; q.rev = rev;
+        q.tr = 0; q.tiles_x = w.tiles_x; q.tiles_y = w.tiles_y;
+        q.ntiles = q.B * q.phases * q.tiles_y * q.tiles_x;
+        q.oy_base = w.y0; q.oy_end = w.y1;
+        return launch_bneck(ctx->prec, o.bn_c, o.bn_asym, w.var, q, s, 0, true);
+    }
     if (wp && wk >= 0) {
         const WinOp &w = wp->op[wk];
         const int rows = w.y1 - w.y0;
@@ -2225,6 +2324,47 @@ int bugseg_debug_poison_arena(bugseg_ctx *ctx, int byte, void *stream) {
     // activations and pooling indices; the range words after them are cleared by every forward
     hipError_t e = hipMemsetAsync(pl.arena, byte & 255, pl.act_bytes, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("poison arena: ") + hipGetErrorString(e));
+    return BUGSEG_OK;
+}
+
+int bugseg_debug_stage3_windows(int h, int y0, int y1, int n, const int32_t *blk, int32_t *win) {
+    if (h <= 0 || y0 < 0 || y0 >= y1 || y1 > h || n < 0 || n > 16 || (n && (!blk || !win)))
+        return fail(nullptr, BUGSEG_EINVAL, "bad stage-3 walk");
+    S3Desc d[16];
+    int te[16], w[16][2];
+    for (int k = 0; k < n; ++k) {
+        d[k].asym = blk[5 * k]; d[k].d = blk[5 * k + 1]; d[k].rd = blk[5 * k + 2]; d[k].rows_full = blk[5 * k + 3];
+        te[k] = blk[5 * k + 4];
+    }
+    const int m = stage3_windows(h, y0, y1, n, d, [&](int k, int, int) { return te[k]; }, w);
+    for (int k = 0; k < m; ++k) { win[2 * k] = w[k][0]; win[2 * k + 1] = w[k][1]; }
+    return m;
+}
+
+int bugseg_debug_plan_windows(bugseg_ctx *ctx, int row0, int row1, int32_t *win) {
+    if (!ctx || !win) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
+    if (!ctx->plan.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
+    DeviceGuard g(ctx->device);
+    const WinPlan *wp = window_plan(ctx, row0, row1);
+    if (!wp) return 0;
+    const int n = (int)ctx->plan.ops.size();
+    for (int k = 0; k < wp->ns3; ++k) {
+        const WinOp &r = wp->s3[k];
+        const int32_t v[5] = {n - WIN_OPS - 1 - k, r.y0, r.y1, r.var, r.tiles_y * r.tiles_x * ctx->plan.ops[(size_t)(n - WIN_OPS - 1 - k)].bn.phases};
+        std::memcpy(win + 5 * k, v, sizeof(v));
+    }
+    return wp->ns3;
+}
+
+int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_t bytes, void *stream) {
+    if (!ctx || !dst_dev) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
+    const Plan &pl = ctx->plan;
+    if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
+    if (op < 0 || op >= (int)pl.ops.size() || pl.ops[(size_t)op].kind != 1 || bytes != pl.ops[(size_t)op].bn.x_bytes)
+        return fail(ctx, BUGSEG_EINVAL, "not a fused bottleneck launch, or not its output's size");
+    DeviceGuard g(ctx->device);
+    hipError_t e = hipMemcpyAsync(dst_dev, pl.ops[(size_t)op].bn.out, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("read block output: ") + hipGetErrorString(e));
     return BUGSEG_OK;
 }
 

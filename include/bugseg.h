@@ -162,8 +162,15 @@ int bugseg_enet_forward_bgr_ops(bugseg_ctx *ctx, const uint8_t *bgr_dev, int B, 
  * pixel groups the window needs: each launch's window is the rows its consumer reads (class layer: input
  * rows y, y + 1 for output rows 2y, 2y + 1; bottlenecks: whole tile rows counted from the first row
  * needed, reading one row above and below; upsampling blocks: input row y for output rows 2y, 2y + 1).
- * The encoder and stage 3 run whole
- * frames (their dilations span the frame). Output rows outside [row0, row1) are NOT written: out_dev keeps
+ * In the fp32 mode the walk goes on into stage 3 through the (at most two) fused C = 128 bottlenecks that feed
+ * the 128 -> 64 block, each with its own vertical reach — its dilation for a 3x3 block, 2 for the asymmetric
+ * block's 5x1 conv: a row-dilated block (4 x 80 tiles of one row phase) runs exactly the rows its consumer
+ * reads, every row phase starting at its first needed row and skipping the fragments of rows past the window;
+ * an asymmetric block runs whole tile rows from its first needed row, in the tile form picked for those rows.
+ * The walk stops at the first block whose window is the whole frame, whose form has no windowed kernel, or
+ * whose window runs no fewer rows than its full-frame launch; BUGSEG_ROW_WINDOW_S3=0 keeps it
+ * to the six launches above. For a span in the lower half of a 480-row frame that is ENet's blocks 3.7
+ * (dilation 16) and 3.6 (asymmetric). The encoder and the other stage-3 blocks run whole frames. Output rows outside [row0, row1) are NOT written: out_dev keeps
  * what it held. Every out_kind is supported. [0, H), or a window that is empty or leaves [0, H), runs
  * exactly bugseg_enet_forward_bgr_ops; so does a plan that does not end in those six fused launches
  * (BUGSEG_NO_FUSE, BUGSEG_CLS_CONV, BUGSEG_CLS_FUSE).
@@ -246,6 +253,19 @@ int bugseg_debug_tile_walk(int ntiles, int grid, int rev, int32_t *seq, size_t s
  * bottlenecks (output rows, H / 4), 3 up 64 -> 16 (input rows, H / 4), 4 the stage-5 bottleneck (output
  * rows, H / 2), 5 the class layer (input rows, H / 2). */
 int bugseg_debug_row_windows(int H, int W, int row0, int row1, int tile_rows_c64, int tile_rows_c16, int32_t *win);
+/* Test hook (host only): the walk of bugseg_enet_forward_bgr_rows on into stage 3, from the rows [y0, y1) of
+ * the h-row stage-3 output that the 128 -> 64 block reads, back through n blocks: blk[5k ..] = (asymmetric,
+ * dilation, row-dilated tiles, rows its full-frame launch computes per frame, image rows per tile row of its
+ * windowed form) of the k-th block before the 128 -> 64 block. Returns the number m of windowed blocks (or a
+ * negative error code); win[2k], win[2k + 1] = the half-open output rows block k < m runs. */
+int bugseg_debug_stage3_windows(int h, int y0, int y1, int n, const int32_t *blk, int32_t *win);
+/* Test hooks (tests/test_gpu_row_window_stage3.py). bugseg_debug_plan_windows: the stage-3 windows the current
+ * plan runs for class rows [row0, row1): returns their number m (0: none, or the full forward) and fills
+ * win[5k ..] = (plan op, first row, end row, tile variant, tiles per frame) for k < m, nearest the decoder
+ * first. bugseg_debug_read_block_output: copy the output tensor of fused bottleneck launch `op` of the
+ * current plan, as the last forward left it, to dst_dev (`bytes` = its size, B * H * W * C elements). */
+int bugseg_debug_plan_windows(bugseg_ctx *ctx, int row0, int row1, int32_t *win);
+int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_t bytes, void *stream);
 /* Test hook (tests/test_gpu_row_window.py): fill the activation arena and the pooling-index tensors of the
  * current plan with `byte`, on `stream`, so that a launch reading a row its producer did not write this
  * forward sees the fill and not a correct row left by an earlier one. */

@@ -36,6 +36,11 @@ def short(name):
     if m:
         asym = m.group(3) in ("1", "true")
         return f"bneck C{m.group(2)}{' asym' if asym else ''} {BNECK_SHAPES.get((int(m.group(2)), int(m.group(4))), '?')}{sfx}"
+    m = re.search(r"bneck_win_kernel<float, (\d+), (false|true), (\d+)>", name) or \
+        re.search(r"bneck_win_kernelIfLi(\d+)ELb(\d)ELi(\d+)E", name)
+    if m:   # the row-windowed stage-3 forms (bneck_kernels.hip WIN)
+        asym = m.group(2) in ("1", "true")
+        return f"bneck C{m.group(1)}{' asym' if asym else ''} {BNECK_SHAPES.get((int(m.group(1)), int(m.group(3))), '?')} windowed"
     if "bneck_cls_kernel" in name:
         return "bneck C16+classes 16x16"
     if "bneck2_f32_kernel" in name:
