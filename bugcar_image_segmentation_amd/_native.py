@@ -30,6 +30,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_last_error",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
+            "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
             "bugseg_debug_parse_pack", "bugseg_debug_polar_tables", "bugseg_debug_ctx_info", "bugseg_debug_tile_walk", "bugseg_debug_set_spans", "bugseg_debug_pool_indices",
             "bugseg_dl_debug_check_plan")
 DL_OP_FIELDS = 32
@@ -98,6 +99,9 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_dl_load_weights": (i, [vp, vp, sz]),
             "bugseg_dl_set_plan": (i, [vp, vp, i, vp, i, i, i, i]),
             "bugseg_dl_forward": (i, [vp, vp, i, i, i, vp, vp]),
+            "bugseg_dl_set_class_lut": (i, [vp, vp, i]),
+            "bugseg_dl_forward_classes": (i, [vp, vp, i, i, i, i, vp, i, i, vp]),
+            "bugseg_dl_classes_from_logits": (i, [vp, i, i, i, vp, i, i, vp]),
             "bugseg_dl_launch_op": (i, [vp, i, vp]),
             "bugseg_dl_read_buffer": (i, [vp, i, vp, sz, vp]),
             "bugseg_dl_last_error": (cp, [vp]),
@@ -388,6 +392,30 @@ class DeepLabContext:
     def forward(self, rgb, B, H, W, out, stream=None):
         self._check(self.lib.bugseg_dl_forward(self.h, rgb.data_ptr(), B, H, W, out.data_ptr(), stream_handle(stream)),
                     self.h)
+
+    def set_class_lut(self, lut) -> None:
+        """bugseg_dl_set_class_lut: the byte the u8 forms store per class id (a sequence of the plan's
+        class count, at most 256 entries, each 0..255), or None for the identity. Uploaded here, once;
+        synchronises the device, so never inside a stream capture."""
+        if lut is None:
+            self._check(self.lib.bugseg_dl_set_class_lut(self.h, None, 0), self.h)
+            return
+        b = bytes(bytearray(int(v) for v in lut))
+        buf = ctypes.create_string_buffer(b, len(b))
+        self._check(self.lib.bugseg_dl_set_class_lut(self.h, buf, len(b)), self.h)
+
+    def forward_classes(self, img, bgr, B, H, W, seg, rows=None, stream=None):
+        """bugseg_dl_forward_classes: (B, H, W, 3) u8 frames (bgr: their byte order is B, G, R) -> rows
+        rows = (row0, row1) (None: all) of the (B, H, W) u8 map lut[class id]; other rows are not written."""
+        r0, r1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+        self._check(self.lib.bugseg_dl_forward_classes(self.h, img.data_ptr(), int(bool(bgr)), B, H, W, seg.data_ptr(),
+                                                       r0, r1, stream_handle(stream)), self.h)
+
+    def classes_from_logits(self, B, H, W, seg, rows=None, stream=None):
+        """bugseg_dl_classes_from_logits: the final op alone on the last forward's logits, rows as above."""
+        r0, r1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+        self._check(self.lib.bugseg_dl_classes_from_logits(self.h, B, H, W, seg.data_ptr(), r0, r1,
+                                                           stream_handle(stream)), self.h)
 
     def launch_op(self, op, stream=None):
         self._check(self.lib.bugseg_dl_launch_op(self.h, op, ctypes.c_void_p(stream_handle(stream))), self.h)

@@ -11,6 +11,7 @@ struct DlPrepArgs {
     int B, H, W;         // H <= Hc, W <= Wc
     int Hc, Wc;          // crop size (513): the padded engine input
     void *out;           // (B, Hc, Wc, 8) T
+    int bgr;             // the bytes are B, G, R: channel c reads byte 2 - c (same values, same arithmetic)
 };
 
 struct DlConvArgs {
@@ -43,6 +44,7 @@ struct DlConvArgs {
     // the (B, Hin, Win, 8) operand is formed on load (dl_prep_kernel's padding and normalisation)
     const uint8_t *rgb;
     int img_h, img_w;
+    int bgr;             // with rgb: the bytes are B, G, R (channel c reads byte 2 - c)
     const void *zero;    // >= 16 zero bytes (after the weight blob): the implicit-GEMM conv's padding taps
 };
 
@@ -99,6 +101,10 @@ struct DlArgmaxArgs {
     int Ho, Wo;          // output rows / cols (the un-padded image)
     int Hout, Wout;      // output tensor dims (== Ho, Wo)
     int64_t *out;        // (B, Hout, Wout)
+    // the u8 form (dl_launch_argmax_u8): lut[class id] as one byte per pixel, output rows [row0, row1) only
+    uint8_t *out8;       // (B, Hout, Wout) u8
+    const uint8_t *lut;  // ncls bytes of device memory
+    int row0, row1;
 };
 
 // Max pooling, TF 'SAME' / 'VALID' geometry given as pads (taps outside the input are skipped, i.e. -inf
@@ -117,6 +123,7 @@ hipError_t dl_launch_conv(int prec, bool out_f32, const DlConvArgs &a, hipStream
 hipError_t dl_launch_dw(int prec, const DlDwArgs &a, hipStream_t s);
 hipError_t dl_launch_pool(int prec, const DlPoolArgs &a, hipStream_t s);
 hipError_t dl_launch_argmax(const DlArgmaxArgs &a, hipStream_t s);
+hipError_t dl_launch_argmax_u8(const DlArgmaxArgs &a, hipStream_t s);   // out8 / lut / [row0, row1) within [0, Ho)
 hipError_t dl_launch_resize(int prec, const DlResizeArgs &a, hipStream_t s);
 
 }  // namespace bugseg

@@ -51,6 +51,7 @@ __global__ void __launch_bounds__(256) dl_prep_kernel(const DlPrepArgs a) {
     if (y < a.H && x < a.W) {
         const uint8_t *p = a.rgb + ((size_t)(b * a.H + y) * a.W + x) * 3;
         for (int c = 0; c < 3; ++c) v[c] = scale * (float)p[c] - 1.0f;
+        if (a.bgr) { const float t = v[0]; v[0] = v[2]; v[2] = t; }   // the bytes were B, G, R: same values, swapped
     } else {
         for (int c = 0; c < 3; ++c) v[c] = scale * 127.5f - 1.0f;
     }
@@ -68,13 +69,15 @@ __global__ void __launch_bounds__(256) dl_prep_kernel(const DlPrepArgs a) {
 // dl_prep_kernel stores it (inside the image: f32(2/255) x - 1; padding: the mean pixel 127.5
 // normalised), for the stem's fused-preprocessing operand loads. Caller: (iy, ix) inside the crop.
 template <typename T>
-__device__ __forceinline__ void prep_px(typename Tr<T>::Raw &r, const uint8_t *rgb, int b, int H, int W, int iy, int ix) {
+__device__ __forceinline__ void prep_px(typename Tr<T>::Raw &r, const uint8_t *rgb, int bgr, int b, int H, int W, int iy,
+                                        int ix) {
 #pragma clang fp contract(off)
     const float scale = 2.0f / 255.0f;
     float v[3];
     if (iy < H && ix < W) {
         const uint8_t *p = rgb + ((size_t)(b * H + iy) * W + ix) * 3;
         for (int c = 0; c < 3; ++c) v[c] = scale * (float)p[c] - 1.0f;
+        if (bgr) { const float t = v[0]; v[0] = v[2]; v[2] = t; }   // the bytes were B, G, R: same values, swapped
     } else {
         for (int c = 0; c < 3; ++c) v[c] = scale * 127.5f - 1.0f;
     }
@@ -210,7 +213,7 @@ __global__ void __launch_bounds__(256) dl_conv_kernel(const DlConvArgs a) {
                 const int iy = piy[j] + ky * a.dil, ix = pix[j] + kx * a.dil;
                 const bool ok = t < a.taps && pv[j] && (unsigned)iy < (unsigned)a.Hin && (unsigned)ix < (unsigned)a.Win;
                 if (a.rgb) {
-                    if (ok) prep_px<T>(bx[j], a.rgb, pb[j], a.img_h, a.img_w, iy, ix);
+                    if (ok) prep_px<T>(bx[j], a.rgb, a.bgr, pb[j], a.img_h, a.img_w, iy, ix);
                     else zero(bx[j]);
                 } else {
                     bld8(bx[j], rin, ok ? (uint32_t)(((pb[j] * a.Hin + iy) * a.Win + ix) * a.CS) * esz : OOB);
@@ -1003,9 +1006,34 @@ constexpr int AM_PX = 8, AM_PY = 1, AM_C = 24;   // classes held in registers (L
 // per 8 pixels of a row). Class ids of a run go out as 16-B stores (two int64) where the address
 // allows (46 -> 44 us). Measured at B = 64: AM_PY = 2 167 us, AM_PY = 4 (B = 16) 66 vs 44 us, AM_PX = 4
 // 149 vs 148 us — fewer threads cost more than the L2 corner reads they save.
+//
+// U8 (bugseg_dl_forward_classes): the same lerp chain and tie rule, lut[class id] as one byte per pixel,
+// output rows [row0, row1) only: the thread grid covers the window's rows, and a run's 8 bytes go out
+// through st_bytes. Every difference from the int64 form (U8 = false) sits behind `U8` at compile time.
+
+// n <= 8 bytes of v (lowest byte first) to p: one 8-byte store where p allows it, else the widest
+// naturally aligned pieces (a row of odd width starts at any byte offset). Writes [p, p + n) only.
+__device__ __forceinline__ void st_bytes(uint8_t *p, uint64_t v, int n) {
+    const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
+    if (n == 8 && (ad & 7) == 0) {
+        *reinterpret_cast<uint64_t *>(p) = v;
+        return;
+    }
+    int k = 0;
+    if ((ad & 1) && n >= 1) { p[0] = (uint8_t)v; k = 1; }
+    if (((ad + k) & 2) && k + 2 <= n) { *reinterpret_cast<uint16_t *>(p + k) = (uint16_t)(v >> (8 * k)); k += 2; }
+    // p + k is 4-byte aligned here whenever 4 more bytes remain
+    if (k + 4 <= n) { *reinterpret_cast<uint32_t *>(p + k) = (uint32_t)(v >> (8 * k)); k += 4; }
+    if (k + 4 <= n) { *reinterpret_cast<uint32_t *>(p + k) = (uint32_t)(v >> (8 * k)); k += 4; }
+    if (k + 2 <= n) { *reinterpret_cast<uint16_t *>(p + k) = (uint16_t)(v >> (8 * k)); k += 2; }
+    if (k < n) p[k] = (uint8_t)(v >> (8 * k));
+}
+
+template <bool U8>
 __global__ void __launch_bounds__(256) dl_resize_argmax_kernel(const DlArgmaxArgs a) {
 #pragma clang fp contract(off)
-    const int qx = (a.Wo + AM_PX - 1) / AM_PX, qy = (a.Ho + AM_PY - 1) / AM_PY;
+    const int yb = U8 ? a.row0 : 0, ye = U8 ? a.row1 : a.Ho;   // the output rows this launch covers
+    const int qx = (a.Wo + AM_PX - 1) / AM_PX, qy = (ye - yb + AM_PY - 1) / AM_PY;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.B * qy * qx) return;
     const int xq = i % qx, t = i / qx, yq = t % qy, b = t / qy;
@@ -1014,8 +1042,8 @@ __global__ void __launch_bounds__(256) dl_resize_argmax_kernel(const DlArgmaxArg
     int curx = -1, cury = -1;
     const int xb = xq * AM_PX, nx = min(AM_PX, a.Wo - xb);
     for (int r = 0; r < AM_PY; ++r) {
-        const int y = yq * AM_PY + r;
-        if (y >= a.Ho) break;
+        const int y = yb + yq * AM_PY + r;
+        if (y >= ye) break;
         const float in_y = (float)y * a.sy;
         const int y0 = (int)floorf(in_y), y1 = min(y0 + 1, a.h - 1);
         const float ly = in_y - (float)y0;
@@ -1081,6 +1109,14 @@ __global__ void __launch_bounds__(256) dl_resize_argmax_kernel(const DlArgmaxArg
             if (j < 4) packed[0] |= (uint32_t)bi << (8 * j);
             else packed[1] |= (uint32_t)bi << (8 * (j - 4));
         }
+        if constexpr (U8) {
+            uint64_t v = 0;
+#pragma unroll
+            for (int j = 0; j < AM_PX; ++j)
+                if (j < nx) v |= (uint64_t)a.lut[(packed[j >> 2] >> (8 * (j & 3))) & 0xffu] << (8 * j);
+            st_bytes(a.out8 + ((size_t)b * a.Hout + y) * a.Wout + xb, v, nx);
+            continue;
+        }
         int res[AM_PX];
 #pragma unroll
         for (int j = 0; j < AM_PX; ++j) res[j] = (int)((packed[j >> 2] >> (8 * (j & 3))) & 0xffu);
@@ -1108,12 +1144,9 @@ __global__ void __launch_bounds__(256) dl_resize_argmax_kernel(const DlArgmaxArg
     }
 }
 
-// Any class count: one thread per output pixel, float4 corner loads.
-__global__ void __launch_bounds__(256) dl_resize_argmax_generic(const DlArgmaxArgs a) {
+// The class id (first maximum) of output pixel (y, x) of image b: the generic kernels' per-pixel chain.
+__device__ __forceinline__ int am_pixel(const DlArgmaxArgs &a, int b, int y, int x) {
 #pragma clang fp contract(off)
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.B * a.Ho * a.Wo) return;
-    const int x = i % a.Wo, t = i / a.Wo, y = t % a.Ho, b = t / a.Ho;
     const float in_y = (float)y * a.sy, in_x = (float)x * a.sx;
     const int y0 = (int)floorf(in_y), x0 = (int)floorf(in_x);
     const int y1 = min(y0 + 1, a.h - 1), x1 = min(x0 + 1, a.w - 1);
@@ -1137,7 +1170,28 @@ __global__ void __launch_bounds__(256) dl_resize_argmax_generic(const DlArgmaxAr
             if (c == 0 || v > best) { best = v; bi = c; }
         }
     }
-    a.out[((size_t)b * a.Hout + y) * a.Wout + x] = (int64_t)bi;
+    return bi;
+}
+
+// Any class count: one thread per output pixel, float4 corner loads.
+__global__ void __launch_bounds__(256) dl_resize_argmax_generic(const DlArgmaxArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.B * a.Ho * a.Wo) return;
+    const int x = i % a.Wo, t = i / a.Wo, y = t % a.Ho, b = t / a.Ho;
+    a.out[((size_t)b * a.Hout + y) * a.Wout + x] = (int64_t)am_pixel(a, b, y, x);
+}
+
+// Its u8 form: one thread = a run of AM_PX pixels of one row of the window [row0, row1), lut[class id]
+// per pixel, the run stored through st_bytes (ncls <= 256: every id indexes the LUT).
+__global__ void __launch_bounds__(256) dl_resize_argmax_generic_u8(const DlArgmaxArgs a) {
+    const int qx = (a.Wo + AM_PX - 1) / AM_PX, rows = a.row1 - a.row0;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.B * rows * qx) return;
+    const int xq = i % qx, t = i / qx, y = a.row0 + t % rows, b = t / rows;
+    const int xb = xq * AM_PX, nx = min(AM_PX, a.Wo - xb);
+    uint64_t v = 0;
+    for (int j = 0; j < nx; ++j) v |= (uint64_t)a.lut[am_pixel(a, b, y, xb + j)] << (8 * j);
+    st_bytes(a.out8 + ((size_t)b * a.Hout + y) * a.Wout + xb, v, nx);
 }
 
 // Feature resize for the decoder: one thread = 8 channels of one output pixel; the four corner
@@ -1451,7 +1505,24 @@ hipError_t dl_launch_argmax(const DlArgmaxArgs &a, hipStream_t s) {
         return hipGetLastError();
     }
     const int n = a.B * ((a.Ho + AM_PY - 1) / AM_PY) * ((a.Wo + AM_PX - 1) / AM_PX);
-    hipLaunchKernelGGL(dl_resize_argmax_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(dl_resize_argmax_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t dl_launch_argmax_u8(const DlArgmaxArgs &a, hipStream_t s) {
+    // the window lies in the frame and every class id indexes the LUT (checked again here: the kernels
+    // trust both)
+    if (!a.out8 || !a.lut || a.row0 < 0 || a.row1 > a.Ho || a.row0 >= a.row1 || a.Ho > a.Hout || a.Wo > a.Wout ||
+        a.ncls < 1 || a.ncls > 256)
+        return hipErrorInvalidValue;
+    const int rows = a.row1 - a.row0, qx = (a.Wo + AM_PX - 1) / AM_PX;
+    if (a.LCS > AM_C) {
+        const int n = a.B * rows * qx;
+        hipLaunchKernelGGL(dl_resize_argmax_generic_u8, dim3((n + 255) / 256), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
+    const int n = a.B * ((rows + AM_PY - 1) / AM_PY) * qx;
+    hipLaunchKernelGGL(dl_resize_argmax_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

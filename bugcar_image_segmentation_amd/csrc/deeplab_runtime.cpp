@@ -27,6 +27,16 @@ struct DlOp {
     int f[BUGSEG_DL_OP_FIELDS];
 };
 
+// One forward's input and output: the frames and their channel order, and either the int64 map (seg ==
+// nullptr) or the u8 class map with the output rows [row0, row1) the final op stores.
+struct DlIo {
+    const uint8_t *img = nullptr;
+    int bgr = 0, H = 0, W = 0;
+    int64_t *out = nullptr;
+    uint8_t *seg = nullptr;
+    int row0 = 0, row1 = 0;
+};
+
 }  // namespace
 
 struct bugseg_dl {
@@ -39,10 +49,12 @@ struct bugseg_dl {
     std::vector<size_t> buf_bytes, buf_off;
     void *arena = nullptr;
     int B = 0, Hc = 0, Wc = 0;
-    // the last forward's I/O (profiling hook)
-    const uint8_t *last_rgb = nullptr;
-    int64_t *last_out = nullptr;
-    int last_H = 0, last_W = 0;
+    // the last forward's I/O (profiling hook; classes_from_logits checks its frame size)
+    DlIo last;
+    bool has_logits = false;      // a forward of the current plan has run: its logits are in the arena
+    // class LUT of the u8 final op: 256 bytes of device memory, identity until bugseg_dl_set_class_lut
+    uint8_t *dev_lut = nullptr;
+    int lut_n = 0;                // 0: identity (fits any class count), else the class count it was set for
 };
 
 namespace {
@@ -211,7 +223,7 @@ std::vector<int> conv_groups(const std::vector<DlOp> &ops) {
 }
 
 // The DlConvArgs of CONV op o (run_op and the grouped launch in bugseg_dl_forward).
-DlConvArgs conv_args(bugseg_dl *c, const DlOp &o, const uint8_t *rgb, int H, int W) {
+DlConvArgs conv_args(bugseg_dl *c, const DlOp &o, const DlIo &io) {
     const int *f = o.f;
     const char *wb = static_cast<const char *>(c->dev_w);
     const int B = c->B;
@@ -233,7 +245,7 @@ DlConvArgs conv_args(bugseg_dl *c, const DlOp &o, const uint8_t *rgb, int H, int
     a.nb = f[30] == 8 ? 8 : f[30] == 4 ? 4 : 2;
     a.zero = wb + c->zero_off;
     a.tap_packed = f[31] != 0;
-    if (f[31] == 2) { a.rgb = rgb; a.img_h = H; a.img_w = W; }   // stem with the preprocessing fused
+    if (f[31] == 2) { a.rgb = io.img; a.img_h = io.H; a.img_w = io.W; a.bgr = io.bgr; }   // stem with the preprocessing fused
     if (f[27] >= 0) {
         a.dw_w = wb + f[27];
         a.dw_b = reinterpret_cast<const float *>(wb + f[28]);
@@ -245,17 +257,17 @@ DlConvArgs conv_args(bugseg_dl *c, const DlOp &o, const uint8_t *rgb, int H, int
     return a;
 }
 
-hipError_t run_op(bugseg_dl *c, const DlOp &o, const uint8_t *rgb, int H, int W, int64_t *out, hipStream_t s) {
+hipError_t run_op(bugseg_dl *c, const DlOp &o, const DlIo &io, hipStream_t s) {
     const int *f = o.f;
     const char *wb = static_cast<const char *>(c->dev_w);
     const int B = c->B;
     switch (f[0]) {
     case OP_PREP: {
-        DlPrepArgs a{rgb, B, H, W, c->Hc, c->Wc, bufp(c, f[1])};
+        DlPrepArgs a{io.img, B, io.H, io.W, c->Hc, c->Wc, bufp(c, f[1]), io.bgr};
         return dl_launch_prep(c->prec, a, s);
     }
     case OP_CONV: {
-        const DlConvArgs a = conv_args(c, o, rgb, H, W);
+        const DlConvArgs a = conv_args(c, o, io);
         return dl_launch_conv(c->prec, f[24] != 0, a, s);
     }
     case OP_DW: {
@@ -304,8 +316,12 @@ hipError_t run_op(bugseg_dl *c, const DlOp &o, const uint8_t *rgb, int H, int W,
         a.B = B; a.h = f[2]; a.w = f[3]; a.LCS = f[4]; a.ncls = f[5];
         a.sy = c->Hc > 1 ? (float)(a.h - 1) / (float)(c->Hc - 1) : 0.f;
         a.sx = c->Wc > 1 ? (float)(a.w - 1) / (float)(c->Wc - 1) : 0.f;
-        a.Ho = H; a.Wo = W; a.Hout = H; a.Wout = W;
-        a.out = out;
+        a.Ho = io.H; a.Wo = io.W; a.Hout = io.H; a.Wout = io.W;
+        if (io.seg) {
+            a.out8 = io.seg; a.lut = c->dev_lut; a.row0 = io.row0; a.row1 = io.row1;
+            return dl_launch_argmax_u8(a, s);
+        }
+        a.out = io.out;
         return dl_launch_argmax(a, s);
     }
     }
@@ -323,6 +339,19 @@ int bugseg_dl_create(int device, int precision, bugseg_dl **out) {
     auto *c = new bugseg_dl();
     c->device = device;
     c->prec = precision == BUGSEG_BF16 ? PREC_BF16 : PREC_F32;
+    {   // the class LUT lives as long as the context: identity until one is set
+        DevGuard g(device);
+        uint8_t id[256];
+        for (int k = 0; k < 256; ++k) id[k] = (uint8_t)k;
+        void *p = nullptr;
+        if (hipMalloc(&p, 256) != hipSuccess) { delete c; return dl_fail(nullptr, BUGSEG_ENOMEM, "class LUT allocation failed"); }
+        if (hipMemcpy(p, id, 256, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(p);
+            delete c;
+            return dl_fail(nullptr, BUGSEG_EHIP, "class LUT upload failed");
+        }
+        c->dev_lut = static_cast<uint8_t *>(p);
+    }
     *out = c;
     return BUGSEG_OK;
 }
@@ -332,6 +361,7 @@ int bugseg_dl_destroy(bugseg_dl *c) {
     DevGuard g(c->device);
     if (c->dev_w) (void)hipFree(c->dev_w);
     if (c->arena) (void)hipFree(c->arena);
+    if (c->dev_lut) (void)hipFree(c->dev_lut);
     delete c;
     return BUGSEG_OK;
 }
@@ -349,6 +379,7 @@ int bugseg_dl_load_weights(bugseg_dl *c, const void *blob, size_t bytes) {
     c->w_bytes = bytes;
     c->ops.clear();
     c->group_len.clear();
+    c->has_logits = false;
     return BUGSEG_OK;
 }
 
@@ -416,18 +447,47 @@ int bugseg_dl_set_plan(bugseg_dl *c, const int32_t *ops, int nops, const uint64_
     c->buf_bytes = std::move(bb);
     c->buf_off = std::move(off);
     c->B = B; c->Hc = Hc; c->Wc = Wc;
+    c->has_logits = false;
     return BUGSEG_OK;
 }
 
-int bugseg_dl_forward(bugseg_dl *c, const uint8_t *rgb_dev, int B, int H, int W, int64_t *out_dev, void *stream) {
-    if (!c || !rgb_dev || !out_dev) return dl_fail(c, BUGSEG_EINVAL, "null argument");
-    if (c->ops.empty()) return dl_fail(c, BUGSEG_ESTATE, "forward before set_plan");
+}  // extern "C"
+
+namespace {
+
+// The plan's ARGMAX op (its last one), or nullptr.
+const DlOp *argmax_op(const bugseg_dl *c) {
+    for (size_t i = c->ops.size(); i-- > 0;)
+        if (c->ops[i].f[0] == OP_ARGMAX) return &c->ops[i];
+    return nullptr;
+}
+
+int check_frame(bugseg_dl *c, int B, int H, int W) {
     if (B != c->B || H < 1 || W < 1 || H > c->Hc || W > c->Wc)
         return dl_fail(c, BUGSEG_EINVAL, "input (" + std::to_string(B) + ", " + std::to_string(H) + ", " + std::to_string(W) +
                                              ") does not fit the plan (B = " + std::to_string(c->B) + ", crop " +
                                              std::to_string(c->Hc) + "x" + std::to_string(c->Wc) + ")");
-    DevGuard g(c->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    return BUGSEG_OK;
+}
+
+// What the u8 final op needs beyond check_frame: a window inside the frame, a class count a byte holds
+// and a LUT set for this plan's class count (one set for another plan is stale).
+int check_classes(bugseg_dl *c, int H, int row0, int row1) {
+    if (row0 < 0 || row1 > H || row0 >= row1)
+        return dl_fail(c, BUGSEG_EINVAL, "row window [" + std::to_string(row0) + ", " + std::to_string(row1) +
+                                             ") is empty or leaves [0, " + std::to_string(H) + ")");
+    const DlOp *am = argmax_op(c);
+    if (!am) return dl_fail(c, BUGSEG_ESTATE, "the plan has no class-map op");
+    const int ncls = am->f[5];
+    if (ncls < 1 || ncls > 256) return dl_fail(c, BUGSEG_EINVAL, "a u8 class map holds at most 256 classes, the plan has " + std::to_string(ncls));
+    if (c->lut_n != 0 && c->lut_n != ncls)
+        return dl_fail(c, BUGSEG_EINVAL, "the class LUT was set for " + std::to_string(c->lut_n) + " classes, the plan has " +
+                                             std::to_string(ncls));
+    return BUGSEG_OK;
+}
+
+// Every op of the plan on stream s (callers have validated io against the plan).
+int run_plan(bugseg_dl *c, const DlIo &io, hipStream_t s) {
     const char *ge = std::getenv("BUGSEG_DL_GROUP");
     const bool group = !(ge && *ge == '0');
     for (size_t i = 0; i < c->ops.size(); ++i) {
@@ -435,23 +495,88 @@ int bugseg_dl_forward(bugseg_dl *c, const uint8_t *rgb_dev, int B, int H, int W,
         if (n > 1) {   // same-shape convs as one launch (the ASPP's atrous branches)
             DlConvGroup grp{};
             grp.n = n;
-            for (int k = 0; k < n; ++k) grp.a[k] = conv_args(c, c->ops[i + k], rgb_dev, H, W);
+            for (int k = 0; k < n; ++k) grp.a[k] = conv_args(c, c->ops[i + k], io);
             const hipError_t e = dl_launch_conv_group(c->prec, grp, s);
             if (e == hipSuccess) { i += n - 1; continue; }
             if (e != hipErrorNotSupported) return dl_fail(c, BUGSEG_EHIP, "grouped launch at op " + std::to_string(i) + ": " + hipGetErrorString(e));
             (void)hipGetLastError();
         }
-        const hipError_t e = run_op(c, c->ops[i], rgb_dev, H, W, out_dev, s);
+        const hipError_t e = run_op(c, c->ops[i], io, s);
         if (e != hipSuccess) return dl_fail(c, BUGSEG_EHIP, "launch of op " + std::to_string(i) + ": " + hipGetErrorString(e));
     }
-    c->last_rgb = rgb_dev; c->last_out = out_dev; c->last_H = H; c->last_W = W;
+    c->last = io;
+    c->has_logits = true;
     return BUGSEG_OK;
 }
 
-int bugseg_dl_launch_op(bugseg_dl *c, int op, void *stream) {
-    if (!c || op < 0 || op >= (int)c->ops.size() || !c->last_rgb) return dl_fail(c, BUGSEG_EINVAL, "no such op / no forward yet");
+}  // namespace
+
+extern "C" {
+
+int bugseg_dl_forward(bugseg_dl *c, const uint8_t *rgb_dev, int B, int H, int W, int64_t *out_dev, void *stream) {
+    if (!c || !rgb_dev || !out_dev) return dl_fail(c, BUGSEG_EINVAL, "null argument");
+    if (c->ops.empty()) return dl_fail(c, BUGSEG_ESTATE, "forward before set_plan");
+    if (const int rc = check_frame(c, B, H, W)) return rc;
     DevGuard g(c->device);
-    const hipError_t e = run_op(c, c->ops[op], c->last_rgb, c->last_H, c->last_W, c->last_out, static_cast<hipStream_t>(stream));
+    DlIo io;
+    io.img = rgb_dev; io.H = H; io.W = W; io.out = out_dev;
+    return run_plan(c, io, static_cast<hipStream_t>(stream));
+}
+
+int bugseg_dl_set_class_lut(bugseg_dl *c, const uint8_t *lut, int n) {
+    if (!c) return dl_fail(c, BUGSEG_EINVAL, "null argument");
+    if (!lut) {   // identity
+        n = 0;
+    } else {
+        if (n < 1 || n > 256) return dl_fail(c, BUGSEG_EINVAL, "a class LUT has 1 to 256 entries, got " + std::to_string(n));
+        const DlOp *am = c->ops.empty() ? nullptr : argmax_op(c);
+        if (am && am->f[5] != n)
+            return dl_fail(c, BUGSEG_EINVAL, "class LUT of " + std::to_string(n) + " entries for a plan of " +
+                                                 std::to_string(am->f[5]) + " classes");
+    }
+    uint8_t host[256];
+    for (int k = 0; k < 256; ++k) host[k] = lut && k < n ? lut[k] : (uint8_t)k;
+    DevGuard g(c->device);
+    // a synchronous copy from pageable memory: it orders after every earlier forward's reads of the
+    // old table, and leaves nothing for a later captured step to copy
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(c->dev_lut, host, 256, hipMemcpyHostToDevice) != hipSuccess)
+        return dl_fail(c, BUGSEG_EHIP, "class LUT upload failed");
+    c->lut_n = n;
+    return BUGSEG_OK;
+}
+
+int bugseg_dl_forward_classes(bugseg_dl *c, const uint8_t *img_dev, int bgr, int B, int H, int W, uint8_t *seg_dev,
+                              int row0, int row1, void *stream) {
+    if (!c || !img_dev || !seg_dev) return dl_fail(c, BUGSEG_EINVAL, "null argument");
+    if (bgr != 0 && bgr != 1) return dl_fail(c, BUGSEG_EINVAL, "bgr must be 0 or 1");
+    if (c->ops.empty()) return dl_fail(c, BUGSEG_ESTATE, "forward before set_plan");
+    if (const int rc = check_frame(c, B, H, W)) return rc;
+    if (const int rc = check_classes(c, H, row0, row1)) return rc;
+    DevGuard g(c->device);
+    DlIo io;
+    io.img = img_dev; io.bgr = bgr; io.H = H; io.W = W; io.seg = seg_dev; io.row0 = row0; io.row1 = row1;
+    return run_plan(c, io, static_cast<hipStream_t>(stream));
+}
+
+int bugseg_dl_classes_from_logits(bugseg_dl *c, int B, int H, int W, uint8_t *seg_dev, int row0, int row1, void *stream) {
+    if (!c || !seg_dev) return dl_fail(c, BUGSEG_EINVAL, "null argument");
+    if (c->ops.empty() || !c->has_logits) return dl_fail(c, BUGSEG_ESTATE, "classes_from_logits before a forward of this plan");
+    if (const int rc = check_frame(c, B, H, W)) return rc;
+    if (H != c->last.H || W != c->last.W)
+        return dl_fail(c, BUGSEG_EINVAL, "the last forward ran " + std::to_string(c->last.H) + "x" + std::to_string(c->last.W) +
+                                             " frames, not " + std::to_string(H) + "x" + std::to_string(W));
+    if (const int rc = check_classes(c, H, row0, row1)) return rc;
+    DevGuard g(c->device);
+    DlIo io = c->last;
+    io.seg = seg_dev; io.row0 = row0; io.row1 = row1;
+    const hipError_t e = run_op(c, *argmax_op(c), io, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? BUGSEG_OK : dl_fail(c, BUGSEG_EHIP, hipGetErrorString(e));
+}
+
+int bugseg_dl_launch_op(bugseg_dl *c, int op, void *stream) {
+    if (!c || op < 0 || op >= (int)c->ops.size() || !c->last.img) return dl_fail(c, BUGSEG_EINVAL, "no such op / no forward yet");
+    DevGuard g(c->device);
+    const hipError_t e = run_op(c, c->ops[op], c->last, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? BUGSEG_OK : dl_fail(c, BUGSEG_EHIP, hipGetErrorString(e));
 }
 

@@ -8,7 +8,8 @@ the final transposed-convolution epilogue. There is no CPU fallback: without the
 every call raises.
 
 Additions beyond the reference API (device fast paths for batching): `predict_device`,
-`logits`, `preprocess_device`.
+`logits`, `preprocess_device`; for DeepLabV3 as the occupancy pipeline's segmenter, `class_lut`,
+`predict_classes_device`, `clone` and the table helpers `class_lut3` / `class_lut_binary`.
 """
 from __future__ import annotations
 
@@ -190,6 +191,42 @@ class ENET(InferenceModel):
         return cls.preprocess_device(bgr_frame, N.PRE_NCHW_F64).cpu().numpy()
 
 
+def _class_ids(name: str, ids, num_classes: int) -> list:
+    out = []
+    for v in ids:
+        k = int(v)
+        if k != v or not 0 <= k < num_classes:
+            raise ValueError(f"{name} id {v!r} is not a class of 0..{num_classes - 1}")
+        out.append(k)
+    if len(set(out)) != len(out):
+        raise ValueError(f"{name} ids repeat: {out}")
+    return out
+
+
+def class_lut3(num_classes: int, road, flat) -> np.ndarray:
+    """The three-class table of models.py:56-58 for any label set: `road` ids -> 1, `flat` ids (flat
+    non-road: pavement, vegetation) -> 0, every other id -> 2. The reference's own ids are
+    class_lut3(15, (0, 1), (2, 9)). For DeepLabV3.class_lut."""
+    if int(num_classes) != num_classes or not 1 <= num_classes <= 256:
+        raise ValueError("num_classes must be 1..256 (one byte per class id)")
+    road, flat = _class_ids("road", road, num_classes), _class_ids("flat", flat, num_classes)
+    if set(road) & set(flat):
+        raise ValueError(f"ids {sorted(set(road) & set(flat))} are both road and flat")
+    lut = np.full(int(num_classes), 2, dtype=np.uint8)
+    lut[flat] = 0
+    lut[road] = 1
+    return lut
+
+
+def class_lut_binary(num_classes: int, road) -> np.ndarray:
+    """The binary table of models.py:79-80: `road` ids -> 1, every other id -> 0."""
+    if int(num_classes) != num_classes or not 1 <= num_classes <= 256:
+        raise ValueError("num_classes must be 1..256 (one byte per class id)")
+    lut = np.zeros(int(num_classes), dtype=np.uint8)
+    lut[_class_ids("road", road, num_classes)] = 1
+    return lut
+
+
 class DeepLabV3(InferenceModel):
     """models.py:98-136 on the MI355X engine (BASELINE config 4).
 
@@ -273,6 +310,36 @@ class DeepLabV3(InferenceModel):
         self.plan_info = None
         self.fuse_dw = bool(int(os.environ.get("BUGSEG_DL_FUSE_DW", "0"))) if fuse_dw is None else fuse_dw
         self.fuse_prep = fuse_prep
+        self._class_lut = None
+
+    @property
+    def class_lut(self):
+        """The byte ``predict_classes_device`` (and an OccupancyPipeline over this model) stores per class
+        id: a uint8 array of ``net.num_classes`` entries (``class_lut3`` / ``class_lut_binary`` build the
+        reference's two conventions), or None for the raw ids. Setting it uploads the table to the
+        context once (it synchronises the device); no forward copies it."""
+        return None if self._class_lut is None else self._class_lut.copy()
+
+    @class_lut.setter
+    def class_lut(self, lut) -> None:
+        if lut is not None:
+            a = np.asarray(lut)
+            if a.dtype != np.uint8 or a.ndim != 1:
+                raise ValueError("class_lut must be a 1-D uint8 array")
+            if a.shape[0] != self.net.num_classes:
+                raise ValueError(f"class_lut has {a.shape[0]} entries, the network has {self.net.num_classes} classes")
+            lut = np.ascontiguousarray(a).copy()
+        self.ctx.set_class_lut(None if lut is None else lut.tolist())
+        self._class_lut = lut
+
+    def clone(self, device: int | None = None) -> "DeepLabV3":
+        """Another engine for the same network: same net, precision, fuse options and class LUT, its own
+        context (weights, arena, plan). The occupancy pipeline runs one per frame shard."""
+        m = DeepLabV3(net=self.net, precision=self.precision, device=self.ctx.device if device is None else device,
+                      fuse_dw=self.fuse_dw, fuse_prep=self.fuse_prep)
+        if self._class_lut is not None:
+            m.class_lut = self._class_lut
+        return m
 
     def _ensure_plan(self, B: int) -> None:
         if self._plan_B == B:
@@ -302,6 +369,36 @@ class DeepLabV3(InferenceModel):
         if out is None:
             out = torch.empty((B, H, W), dtype=torch.int64, device=x.device)
         self.ctx.forward(x, B, H, W, out, torch.cuda.current_stream(x.device))
+        return out
+
+    def predict_classes_device(self, frames, *, bgr: bool = False, rows=None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """(B, H, W, 3) u8 frames (device or host; bgr=True: bytes in B, G, R order, else R, G, B) -> the
+        (B, H, W) u8 device map ``class_lut[class id]`` (the raw id without a LUT), from the same resize and
+        argmax as ``predict_device``, one byte per pixel straight from the final kernel. rows=(row0, row1)
+        stores those output rows only (a new ``out`` is zero elsewhere; a given one is left as it was);
+        ``ctx.classes_from_logits`` fills further rows without another forward."""
+        x = _as_device_tensor(frames, torch.uint8, self.ctx.device)
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        if x.dim() != 4 or x.shape[3] != 3:
+            raise ValueError(f"expected u8 images (B, H, W, 3), got {tuple(x.shape)}")
+        B, H, W = x.shape[:3]
+        Hc, Wc = self._spec.crop_hw(self.net)
+        if H > Hc or W > Wc:
+            raise ValueError(f"image {H}x{W} exceeds the export's {Hc}x{Wc} crop: resize it first "
+                             "(DeepLabV3.preprocess)")
+        if self.net.num_classes > 256:
+            raise ValueError(f"a u8 class map holds at most 256 classes, the network has {self.net.num_classes}")
+        if rows is not None:
+            rows = (int(rows[0]), int(rows[1]))
+            if not 0 <= rows[0] < rows[1] <= H:
+                raise ValueError(f"rows {rows} is empty or leaves [0, {H})")
+        if out is None:
+            out = (torch.empty if rows is None else torch.zeros)((B, H, W), dtype=torch.uint8, device=x.device)
+        elif tuple(out.shape) != (B, H, W) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {(B, H, W)} on {x.device}")
+        self._ensure_plan(B)
+        self.ctx.forward_classes(x, bgr, B, H, W, out, rows, torch.cuda.current_stream(x.device))
         return out
 
     def logits_device(self) -> torch.Tensor:

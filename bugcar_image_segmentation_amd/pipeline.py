@@ -8,6 +8,11 @@
 Everything stays in HBM; there is no host round trip between stages. With streams > 1 every frame
 shard runs all three stages on its own context and stream. This is the
 loop the reference's (absent) ROS node runs per frame (README.md:19), batched.
+
+With a DeepLabV3 model the middle stage is its plan with the u8 final op: the resized
+BGR frames go in as they are (the stem or the prep launch swaps the channels as it loads them), the
+final op stores model.class_lut[class id] for the rows the rasteriser reads, and the resize and the
+rasteriser run on a weightless engine context per shard.
 """
 from __future__ import annotations
 
@@ -16,7 +21,7 @@ import torch
 
 from . import _native as N
 from .bev import bev_transform_tools
-from .models import ENET
+from .models import ENET, DeepLabV3
 
 
 class OccupancyPipeline:
@@ -24,7 +29,7 @@ class OccupancyPipeline:
     (own activation arena) on its own HIP stream, so the launches of different shards overlap on the
     device (one shard's compute phases beside another's memory phases). Results are identical."""
 
-    def __init__(self, model: ENET, bev: bev_transform_tools, grid_w_m: float, grid_h_m: float, cell_m: float,
+    def __init__(self, model: "ENET | DeepLabV3", bev: bev_transform_tools, grid_w_m: float, grid_h_m: float, cell_m: float,
                  model_hw: tuple[int, int] | None = None, ros_layout: bool = False, streams: int = 1,
                  binary: bool = False, stream_priority: int = 0, chain_forwards: bool = False, shard_offset: int = 0,
                  window_rows: bool = True):
@@ -42,12 +47,30 @@ class OccupancyPipeline:
         (Context.bev_source_rows: for a forward-looking camera, the rows below the horizon): the decoder's
         last six launches run just the tiles those rows need (Context.forward_bgr_rows). The grids are the
         same; the rows of the internal class map that nothing samples are not computed. A calibration
-        that samples the whole image, or window_rows=False, makes the full-frame calls."""
+        that samples the whole image, or window_rows=False, makes the full-frame calls.
+        model may be a DeepLabV3 with its class_lut set (models.class_lut3 / class_lut_binary for the
+        reference's conventions; binary=True only selects the binary rasteriser for what the LUT
+        produces). model_hw then defaults to the net's crop and must fit inside it; every shard runs its
+        own DeepLabV3.clone planned for that shard's frames; the row window applies to the final op
+        alone (the ASPP image pooling needs the whole frame); shard_offset is refused."""
         self.model = model
+        self._dl = isinstance(model, DeepLabV3)
         self.binary = binary
         self.bev = bev
         self.grid = (grid_w_m, grid_h_m, cell_m)
-        self.H, self.W = model_hw if model_hw is not None else (ENET.INPUT_HEIGHT, ENET.INPUT_WIDTH)
+        if self._dl:
+            crop = model._spec.crop_hw(model.net)
+            self.H, self.W = model_hw if model_hw is not None else crop
+            if self.H > crop[0] or self.W > crop[1] or self.H < 1 or self.W < 1:
+                raise ValueError(f"model_hw {self.H}x{self.W} does not fit the network's {crop[0]}x{crop[1]} crop")
+            if model.class_lut is None:
+                raise ValueError("a DeepLabV3 model needs its class_lut set (models.class_lut3 / class_lut_binary): "
+                                 "there is no default mapping of an arbitrary label set to the rasteriser's classes")
+            if int(shard_offset) > 0:
+                raise ValueError("shard_offset needs a forward that runs a range of launches, which DeepLabV3 lacks; "
+                                 "use chain_forwards to stagger its shards")
+        else:
+            self.H, self.W = model_hw if model_hw is not None else (ENET.INPUT_HEIGHT, ENET.INPUT_WIDTH)
         self.ros_layout = ros_layout
         if (self.H, self.W) != (bev.input_width, bev.input_height):
             raise ValueError(f"model output {self.H}x{self.W} must equal the calibration's input image size "
@@ -58,7 +81,10 @@ class OccupancyPipeline:
         self.stream_priority = stream_priority
         self.chain_forwards = chain_forwards
         self.shard_offset = int(shard_offset)
-        self._ctxs = [model.ctx]
+        # DeepLab: _ctxs are weightless engine contexts (resize, source rows, rasteriser: none of them
+        # needs weights) and _engines the DeepLabV3 of each shard, shard 0 the caller's own
+        self._ctxs = [N.Context(model.ctx.device, N.FP32)] if self._dl else [model.ctx]
+        self._engines = [model] if self._dl else []
         self._streams = []
         self.window_rows = bool(window_rows)
         self._windowed = False       # the forwards of the run in progress are windowed
@@ -70,11 +96,49 @@ class OccupancyPipeline:
 
     def _shard_ctxs(self, dev: torch.device):
         while len(self._ctxs) < self.streams:
-            c = N.Context(dev.index, self.model.ctx.precision)
-            c.load_weights(self.model.blob)
+            if self._dl:
+                c = N.Context(dev.index, N.FP32)
+                self._engines.append(self.model.clone(dev.index))
+            else:
+                c = N.Context(dev.index, self.model.ctx.precision)
+                c.load_weights(self.model.blob)
             self._ctxs.append(c)
             self._streams.append(torch.cuda.Stream(device=dev, priority=self.stream_priority))
         return self._ctxs, self._streams
+
+    def _bounds(self, B: int):
+        """Frame bounds of the shards a batch of B runs as ([0, B]: one shard on the model's own engine)."""
+        if self.streams == 1 or B < self.streams:
+            return [0, B]
+        return [B * i // self.streams for i in range(self.streams + 1)]
+
+    def _prepare_dl(self, B: int, dev: torch.device, may_build: bool) -> None:
+        """Every shard's engine with its weights, class LUT and a plan for its share of B frames, and the
+        row window of every shard's calibration. set_plan and set_class_lut allocate and synchronise the
+        device, so none of this may happen while a stream is capturing: with may_build False a missing piece
+        raises before any library call."""
+        lut = self.model.class_lut
+        if lut is None:
+            raise ValueError("the model's class_lut was removed: an occupancy pipeline needs one")
+        bounds = self._bounds(B)
+        n = len(bounds) - 1
+        todo = n > len(self._ctxs)
+        for i in range(min(n, len(self._engines))):
+            m = self._engines[i]
+            todo = todo or m._plan_B != bounds[i + 1] - bounds[i] or not np.array_equal(m._class_lut, lut)
+        if not todo:
+            return
+        if not may_build:
+            raise RuntimeError(f"OccupancyPipeline.run inside a stream capture with no plan for a batch of {B}: planning "
+                               "allocates and synchronises the device; use capture(), or run this batch size once first")
+        if n > 1:
+            self._shard_ctxs(dev)
+        for i in range(n):
+            m = self._engines[i]
+            if not np.array_equal(m._class_lut, lut):
+                m.class_lut = lut
+            m._ensure_plan(bounds[i + 1] - bounds[i])
+            self._source_rows(self._ctxs[i])
 
     def _bufs(self, B: int, dev: torch.device):
         if self._x is None or self._x.shape[0] != B or self._x.device != dev:
@@ -96,6 +160,13 @@ class OccupancyPipeline:
             st = torch.cuda.current_stream(frames.device)
             for i in range(len(bounds) - 1):
                 s, e = bounds[i], bounds[i + 1]
+                if self._dl:
+                    # the final op alone over the missing rows, on the logits the shard's forward left
+                    r0, r1 = self._source_rows(self._ctxs[i])
+                    for rows in ((0, r0), (r1, self.H)):
+                        if rows[0] < rows[1]:
+                            self._engines[i].ctx.classes_from_logits(e - s, self.H, self.W, self._seg_raw[s:e], rows, st)
+                    continue
                 self._run_forward(self._ctxs[i], frames[s:e], self._x[s:e], self._seg_raw[s:e], st, window=False)
         return self._seg_raw
 
@@ -111,6 +182,8 @@ class OccupancyPipeline:
         if frames_bgr.dim() != 4 or frames_bgr.shape[3] != 3 or frames_bgr.dtype != torch.uint8 or not frames_bgr.is_cuda:
             raise ValueError("frames must be a (B, H0, W0, 3) uint8 device tensor")
         B, H0, W0 = frames_bgr.shape[:3]
+        if self._dl:
+            self._prepare_dl(B, frames_bgr.device, may_build=not torch.cuda.is_current_stream_capturing())
         x, seg, grid = self._bufs(B, frames_bgr.device)
         if grid.shape != self._grid_shape(B):       # the calibration's laserscan flag changed
             self._grid = grid = torch.empty(self._grid_shape(B), dtype=torch.int8, device=frames_bgr.device)
@@ -121,7 +194,7 @@ class OccupancyPipeline:
         p = self._params()
         self._seg_partial = None
         if self.streams == 1 or B < self.streams:
-            self._run_shard(self.model.ctx, frames, x, seg, out, p, None)
+            self._run_shard(self._ctxs[0], frames, x, seg, out, p, None)
             if self._windowed:
                 self._seg_partial = (frames, [0, B])
             return out
@@ -129,7 +202,7 @@ class OccupancyPipeline:
         ctxs, streams = self._shard_ctxs(frames.device)
         main = torch.cuda.current_stream(frames.device)
         ready = main.record_event()
-        bounds = [B * i // self.streams for i in range(self.streams + 1)]
+        bounds = self._bounds(B)
         for i in range(self.streams):
             s, e = bounds[i], bounds[i + 1]
             st = main if i == 0 else streams[i - 1]
@@ -173,8 +246,11 @@ class OccupancyPipeline:
         must stay alive and keep their addresses. warm=True runs the step once eagerly first;
         warm=False captures the very first call at this shape and geometry (the library allocates
         arenas and builds its tables on its own stream during the capture; only the shard contexts
-        and streams are created beforehand)."""
+        and streams are created beforehand). A DeepLabV3 pipeline prepares every shard's engine, weights,
+        plan and class LUT before either form: planning must not run inside a capture."""
         dev = frames_bgr.device
+        if self._dl:
+            self._prepare_dl(frames_bgr.shape[0], dev, may_build=True)
         if warm:
             self.run(frames_bgr, out)
         elif self.streams > 1 and frames_bgr.shape[0] >= self.streams:
@@ -228,6 +304,13 @@ class OccupancyPipeline:
             # resize only (models.py:87); colour swap + normalisation are fused into the initial block
             ctx.preprocess(frames, B, H0, W0, self.H, self.W, N.PRE_BGR_U8, x, stream)
             frames = x
+        if self._dl:
+            rows = self._source_rows(ctx) if window else None
+            if window:
+                self._windowed = rows is not None
+            engine = self._engines[self._ctxs.index(ctx)]
+            engine.ctx.forward_classes(frames, True, B, self.H, self.W, seg, rows, stream)
+            return
         kind = N.OUT_BINARY_U8 if self.binary else N.OUT_CLASS3_U8
         rows = self._source_rows(ctx) if window else None
         if window:

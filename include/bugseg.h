@@ -311,6 +311,27 @@ int bugseg_dl_set_plan(bugseg_dl *dl, const int32_t *ops, int nops, const uint64
 /* rgb_dev: (B, H, W, 3) u8 RGB, H <= Hc, W <= Wc (padded with the mean pixel to the crop, as the
  * export's preprocessing does); out_dev: (B, H, W) int64 class ids. */
 int bugseg_dl_forward(bugseg_dl *dl, const uint8_t *rgb_dev, int B, int H, int W, int64_t *out_dev, void *stream);
+/* The u8 class-map form of the forward, for the occupancy pipeline (the int64 map of bugseg_dl_forward
+ * remapped to the rasteriser's classes costs 9 bytes per pixel written and 8 read again for one byte).
+ *
+ * bugseg_dl_set_class_lut: the byte the u8 form stores for each class id: lut[0 .. n) in HOST memory,
+ * n = the plan's class count, at most 256; lut == NULL restores the identity. The table is copied to
+ * device memory the context owns when it is set (the call synchronises the device: not inside a stream
+ * capture), never per forward. n is checked against the current plan here and again at every u8
+ * forward, so a plan with another class count is never run with a stale table (EINVAL). */
+int bugseg_dl_set_class_lut(bugseg_dl *dl, const uint8_t *lut, int n);
+/* The whole plan with the final op in the u8 form: img_dev (B, H, W, 3) u8 in R, G, B byte order
+ * (bgr = 0) or B, G, R (bgr = 1: channel c reads byte 2 - c, so a BGR frame gives the activations of
+ * its RGB flip bit for bit); seg_dev (B, H, W) u8, lut[argmax] with the int64 form's lerp chain and
+ * first-maximum tie rule. Only output rows [row0, row1) of every frame are stored ([0, H): the whole
+ * map); no other byte of seg_dev is written. An empty window or one leaving [0, H): EINVAL. */
+int bugseg_dl_forward_classes(bugseg_dl *dl, const uint8_t *img_dev, int bgr, int B, int H, int W, uint8_t *seg_dev,
+                              int row0, int row1, void *stream);
+/* Only the final op, u8 form, on the logits the last forward of this plan (either form) left in the
+ * arena: rows [row0, row1) of the class map of that forward's frames, which must have been B x H x W.
+ * ESTATE before any forward of the current plan. Completes a windowed map without a second forward. */
+int bugseg_dl_classes_from_logits(bugseg_dl *dl, int B, int H, int W, uint8_t *seg_dev, int row0, int row1,
+                                  void *stream);
 /* Profiling hook: enqueue op `op` of the plan alone, on the last forward's I/O buffers. */
 int bugseg_dl_launch_op(bugseg_dl *dl, int op, void *stream);
 /* Test hook: copy `bytes` of activation buffer `buf` (deeplab_spec.lower's numbering; 7 = the f32
