@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
+#include <variant>
 
 #include "bugseg_internal.h"
 #include "../../include/bugseg.h"
@@ -112,24 +113,54 @@ struct Packed {
     std::vector<float> rabs, rbias, rslope;
 };
 
-struct Op {
-    int kind = 0;          // 0: conv_kernel launch, 1: fused bottleneck launch, 2: fused upsampling block
-    ConvArgs a;
+// One kernel launch of the plan: which launch_* it goes to, that call's dispatch arguments and its argument
+// struct. Everything but span and rev (issue) and the forward's bindings (bind) is final once the plan is built.
+struct ConvLaunch {    // launch_conv: the unfused convolutions, the initial block, the class layer
     int nr = 0, epi = 0;
-    BneckArgs bn;
-    UpArgs up;
-    int up_cin = 0, up_it = 0, up_cout = 0;
-    int bn_c = 0, bn_var = 0, bn_cin = 0;   // bn_cin > 0: a downsampling block (cin input channels)
-    bool bn_asym = false;
+    ConvArgs a{};
+};
+struct BneckLaunch {   // launch_bneck: a fused bottleneck; cin > 0: a downsampling block (cin input channels)
+    int C = 0, var = 0, cin = 0;
+    bool asym = false;
+    bool win = false;  // the row-windowed fp32 C = 128 kernels (BneckArgs::oy_end)
+    bool cls = false;  // launch_bneck_cls: the C = 16 block with the class layer fused in (Plan::cls_fused)
+    BneckArgs a{};
+};
+struct UpLaunch {      // launch_up: a fused upsampling block
+    int cin = 0, it = 0, cout = 0;
+    UpArgs a{};
+};
+using Launch = std::variant<ConvLaunch, BneckLaunch, UpLaunch>;
+
+// A plan op: its full-frame launch and its accounting. Immutable between build_plan calls: a forward's input and
+// output (Binding) and a row window (WinPlan) go into a copy of the launch, never into the plan.
+struct Op {
+    Launch l;
     double bytes = 0, flops = 0;
     double layer_bytes = -1;   // per-layer (unfused) algorithmic bytes of the work; -1: same as bytes
     int launches = 1;          // kernel launches the op issues (every form today: one)
     int pos = 0;               // launches the plan issues before this op (build_plan): its walk direction's parity
-    Op() {
-        std::memset(&a, 0, sizeof(a));
-        std::memset(&bn, 0, sizeof(bn));
-        std::memset(&up, 0, sizeof(up));
+    double layer() const { return layer_bytes >= 0 ? layer_bytes : bytes; }
+    const ConvLaunch *conv() const { return std::get_if<ConvLaunch>(&l); }
+    const BneckLaunch *bneck() const { return std::get_if<BneckLaunch>(&l); }
+    const UpLaunch *up() const { return std::get_if<UpLaunch>(&l); }
+    // a fused regular bottleneck (3x3, undilated, one phase) of C channels on an h-row grid
+    bool regular(int C, int h) const {
+        const BneckLaunch *b = bneck();
+        return b && b->C == C && !b->asym && b->cin == 0 && b->a.dt == 1 && b->a.phases == 1 && b->a.H == h;
     }
+    bool up_on(int h) const { return up() && up()->a.h == h; }          // a fused upsampling block reading an h-row grid
+    bool epi(int e) const { return conv() && conv()->epi == e; }
+    // the class layer as the class kernel runs it (cls_kernels.hip), not the generic EPI_CLASSES convolution
+    bool class_kernel() const { return epi(EPI_CLASSES) && cls_supported(conv()->a) && !std::getenv("BUGSEG_CLS_CONV"); }
+};
+
+// What one forward binds into the plan's first and last launch (bind): the input and its kind, the output and
+// its kind, and whether the BGR normalisation runs in its affine form (BUGSEG_INIT_TABLE, read per forward).
+struct Binding {
+    const void *in = nullptr;
+    bool bgr = false, naff_on = false;
+    int out_kind = 0; void *out = nullptr;
 };
 
 // Row-windowed decoder (bugseg_enet_forward_bgr_rows): the rows each of the plan's last WIN_OPS ops runs
@@ -137,14 +168,22 @@ struct Op {
 // stage-4 bottlenecks, the 64 -> 16 upsampling block, the stage-5 bottleneck and the class layer. y0, y1:
 // rows of the op's own grid, input rows for the upsampling blocks and the class layer (pointwise in their
 // input grid), output rows for the bottlenecks; a bottleneck also carries the tile form picked for its
-// window (pick_bneck_variant over the window's rows).
+// window (pick_bneck_variant over the window's rows). l: the op's finished windowed launch (narrow), built
+// once with the window; launch_op only picks it.
 constexpr int WIN_OPS = 6;
-struct WinOp { int y0 = 0, y1 = 0, var = 0, tr = 0, te = 1, tiles_x = 0, tiles_y = 0; };   // te: image rows per tile row
+struct WinOp { int y0 = 0, y1 = 0, var = 0, tr = 0, te = 1, tiles_x = 0, tiles_y = 0; Launch l; };   // te: image rows per tile row
 // The walk goes on into stage 3 (stage3_windows): s3[k] is the window of the (k + 1)-th op before those six, a
 // fused fp32 C = 128 bottleneck in its windowed form (launch_bneck win = true), for k < ns3 <= S3_OPS. y0, y1:
 // output rows; tiles_y: tile rows per frame (a row-dilated form: of its longest row phase).
 constexpr int S3_OPS = 2;
-struct WinPlan { int row0 = 0, row1 = 0; WinOp op[WIN_OPS]; int ns3 = 0; WinOp s3[S3_OPS]; };
+struct WinPlan {
+    int row0 = 0, row1 = 0; WinOp op[WIN_OPS]; int ns3 = 0; WinOp s3[S3_OPS];
+    // the windowed launch of op i of an n-op plan; null: the op runs its full-frame launch
+    const Launch *launch_of(int i, int n) const {
+        const int k = i - (n - WIN_OPS);
+        return k >= 0 ? &op[k].l : -k - 1 < ns3 ? &s3[-k - 1].l : nullptr;
+    }
+};
 
 struct Plan {
     int B = 0, H = 0, W = 0;
@@ -160,9 +199,12 @@ struct Plan {
     std::vector<size_t> idx_bytes;
     // ENet's last bottleneck (C = 16) and the class layer as ONE launch (bneck_kernels.hip, class fusion;
     // opt-in, BUGSEG_CLS_FUSE=1: measured slower, see there): possible for this plan (cls_ok: the plan ends
-    // with that bottleneck feeding the class kernel), and taken by the last forward (cls_on: a class-map
-    // output, both ops in its range). The last op then launches nothing; its plan_op tag is "fused".
+    // with that bottleneck feeding the class kernel; cls_fused is then that launch, its output unbound), and
+    // taken by the last forward (cls_on: a class-map output, both ops in its range). The last op then launches
+    // nothing; its plan_op tag is "fused".
     bool cls_ok = false, cls_on = false;
+    Launch cls_fused;
+    Binding bound;           // the last forward's binding (in == nullptr: none since the plan was built)
     // Tile walk direction of the launches (bugseg_internal.h tile_walk), BUGSEG_TILE_ORDER, read per plan
     // build as BUGSEG_NO_FUSE is: 0 every launch ascending, 1 alternating from ascending, 2 every launch
     // descending (a control). Alternating, a launch starts on the frames the launch before it finished
@@ -761,20 +803,30 @@ ConvArgs base_args(const bugseg_ctx *ctx, const Packed &p) {
     return a;
 }
 
+// BUGSEG_NO_FUSE=1: every block as its separate convolutions (read per plan build: plans are cached)
+bool no_fuse() {
+    const char *env = std::getenv("BUGSEG_NO_FUSE");
+    return env && *env && *env != '0';
+}
+// Every PReLU slope (both slope vectors) of the packed units is <= 1: max(v, s*v) is then exact
+bool slopes_le1(const bugseg_ctx *ctx, std::initializer_list<const Packed *> units) {
+    for (const Packed *p : units) {
+        const float *s1 = (const float *)(ctx->host_w.data() + p->o_s1), *s2 = (const float *)(ctx->host_w.data() + p->o_s2);
+        for (int c = 0; c < p->Npad; ++c)
+            if (!(s1[c] <= 1.f) || !(s2[c] <= 1.f)) return false;
+    }
+    return true;
+}
+
 // A regular block runs as ONE fused launch (bneck_kernels.hip) when its shape is one the fused
 // kernel is built for and a tile variant covers the layer efficiently (pick_bneck_variant);
 // otherwise as its 3-4 conv launches. BUGSEG_NO_FUSE=1 forces the unfused plan (A/B testing;
 // results are bit-identical).
 bool fusable_regular(const bugseg_ctx *ctx, const BlockDesc &b, const std::vector<int> &ids, int &r, int &d) {
-    const char *env = std::getenv("BUGSEG_NO_FUSE");     // read per plan build (plans are cached)
-    if (env && *env && *env != '0') return false;
+    if (no_fuse()) return false;
     // the fused kernel computes PReLU as max(v, s*v), exact only for slopes <= 1
-    for (const int id : ids) {
-        const Packed &p = ctx->packed[id];
-        const float *s1 = (const float *)(ctx->host_w.data() + p.o_s1), *s2 = (const float *)(ctx->host_w.data() + p.o_s2);
-        for (int c = 0; c < p.Npad; ++c)
-            if (!(s1[c] <= 1.f) || !(s2[c] <= 1.f)) return false;
-    }
+    for (const int id : ids)
+        if (!slopes_le1(ctx, {&ctx->packed[id]})) return false;
     const int C = b.attrs[0];
     if (C != 128 && C != 64 && C != 16) return false;
     const int nu = (int)b.units.size();
@@ -800,17 +852,12 @@ bool fusable_regular(const bugseg_ctx *ctx, const BlockDesc &b, const std::vecto
 // (16 -> 64, 64 -> 128, internal cin / 4), 2x2 stride-2 projection, 3x3 middle conv, PReLU slopes
 // <= 1. -> the tile variant (C64: 16x16, C128: 20x16, untransposed) or -1.
 int fusable_down(const bugseg_ctx *ctx, const BlockDesc &b, const std::vector<int> &ids) {
-    const char *env = std::getenv("BUGSEG_NO_FUSE");
-    if (env && *env && *env != '0') return -1;
+    if (no_fuse()) return -1;
     const int cin = b.attrs[0], C = b.attrs[1];
     const int v = C == 64 && cin == 16 ? 0 : C == 128 && cin == 64 ? 1 : -1;
     if (v < 0 || b.units.size() != 3) return -1;
-    for (const int id : ids) {
-        const Packed &p = ctx->packed[id];
-        const float *s1 = (const float *)(ctx->host_w.data() + p.o_s1), *s2 = (const float *)(ctx->host_w.data() + p.o_s2);
-        for (int c = 0; c < p.Npad; ++c)
-            if (!(s1[c] <= 1.f) || !(s2[c] <= 1.f)) return -1;
-    }
+    for (const int id : ids)
+        if (!slopes_le1(ctx, {&ctx->packed[id]})) return -1;
     const UnitDesc &u1 = b.units[0], &u2 = b.units[1], &u3 = b.units[2];
     const int I = cin / 4;                              // ENet: internal = input channels / 4
     if (u1.kh != 2 || u1.kw != 2 || u1.stride != 2 || u1.pad_h != 0 || u1.pad_w != 0 || u1.cin != cin || u1.cout != I)
@@ -873,7 +920,8 @@ int pick_bneck_variant(const bugseg_ctx *ctx, int C, bool asym, int d, int B, in
     return best;
 }
 
-// Walk the network for (B, H, W). With fill == false only the buffer sizes are computed.
+// Walk the network for (B, H, W), twice: run(false) computes only the buffer sizes, run(true), with the arena
+// carved, the ops. run dispatches to one method per block type; wire / slopes_le1 / sums are what those share.
 struct Walker {
     bugseg_ctx *ctx;
     int B, H, W;
@@ -910,8 +958,58 @@ struct Walker {
 
     size_t tbytes(const Shape &s) const { return (size_t)B * s.H * s.W * s.C * es; }
 
-    void conv(const Packed &p, int epi, const void *in, Shape si, Shape sg, void *out, Shape so, Op &op) {
-        ConvArgs a = base_args(ctx, p);
+    // ---- the walk's state, shared by the block methods: the pass, the current activation (curp == nullptr: the
+    // engine input, bound per call), the index of the block being walked, its packed units and its output buffer
+    bool fill = false;
+    Shape cur{0, 0, 0};
+    const unsigned char *curp = nullptr;
+    size_t bi = 0;
+    const std::vector<int> *ids = nullptr;
+    unsigned char *dst = nullptr;
+    const Packed &P(int i) const { return ctx->packed[(size_t)(*ids)[(size_t)i]]; }
+    static ConvArgs &args(Op &op) { return std::get<ConvLaunch>(op.l).a; }
+    static uint32_t clamp31(size_t v) { return (uint32_t)std::min<size_t>(v, 0x7fffffff); }
+
+    // a packed unit's weights, bias and first slope vector on the device; its second slope vector
+    void wire(const Packed &p, const void *&w, const float *&b, const float *&s) const {
+        const unsigned char *dw = (const unsigned char *)ctx->dev_w;
+        w = dw + p.o_w; b = (const float *)(dw + p.o_bias); s = (const float *)(dw + p.o_s1);
+    }
+    const float *slope2(const Packed &p) const { return (const float *)((const unsigned char *)ctx->dev_w + p.o_s2); }
+    // weight bytes and flops over px GEMM pixels of the block's first n units
+    void sums(int n, double px, double &wb, double &fl) const {
+        wb = fl = 0;
+        for (int i = 0; i < n; ++i) { wb += (double)P(i).Npad * P(i).Kpad * es; fl += 2.0 * P(i).macs_per_px * px; }
+    }
+    // fp32 range scaling of a launch: its input's measured range; measure: its output's range is measured too
+    void range_io(RangeArgs &rg, const void *in, const void *out, bool measure = true) {
+        rg.amax_in = words_of(in);
+        rg.off = ctx->range_off;
+        if (!measure) return;
+        rg.amax_out = take_words();
+        wrote(out, rg.amax_out);
+    }
+    static void residual(ConvArgs &a, const void *res, Shape s, int C) {
+        a.res = res; a.resH = s.H; a.resW = s.W; a.resC = C; a.resCS = s.C;
+    }
+    // the units of a fused bottleneck (p2b: the asymmetric block's 1x5, else p2 again)
+    void wire_bneck(BneckArgs &q, const Packed &p1, const Packed &p2, const Packed &p2b, const Packed &p3) const {
+        wire(p1, q.w1, q.b1, q.s1); wire(p2, q.w2, q.b2, q.s2);
+        wire(p2b, q.w2b, q.b2b, q.s2b); wire(p3, q.w3, q.b3, q.s3);
+        q.s_out = slope2(p3);
+        q.slopes_le1 = slopes_le1(ctx, {&p1, &p2, &p2b, &p3});
+        q.rg.sw[0] = p1.sw; q.rg.sw[1] = p2.sw; q.rg.sw[2] = p2b.sw; q.rg.sw[3] = p3.sw;
+        row_bound(p1, 0, p1.cout, q.rg.n[0], q.rg.c[0]);
+        row_bound(p2, 0, p2.cout, q.rg.n[1], q.rg.c[1]);
+    }
+
+    // one convolution launch, appended to ops
+    Op &conv(const Packed &p, int epi, const void *in, Shape si, Shape sg, void *out, Shape so) {
+        Op op;
+        ConvLaunch &l = op.l.emplace<ConvLaunch>();
+        l.nr = p.nr; l.epi = epi;
+        ConvArgs &a = l.a;
+        a = base_args(ctx, p);
         a.in = in; a.B = B; a.Hin = si.H; a.Win = si.W;
         a.Hg = sg.H; a.Wg = sg.W; a.M = B * sg.H * sg.W;
         a.out = out; a.Hout = so.H; a.Wout = so.W; a.outC = so.C;
@@ -919,311 +1017,225 @@ struct Walker {
         const int epc = 16 / (int)es;
         a.stg_elems = epi == EPI_CLASSES ? 64 * 20 * 4 / (int)es      // 64 pixels x 20 floats (conv_kernels.hip CLS_STR)
                     : epi == EPI_SHUFFLE ? 64 * (so.C + epc) : 16 * (so.C + epc);
-        // PReLU as max(v, s*v) is exact when every slope of the launch is <= 1
-        const float *s1 = (const float *)(ctx->host_w.data() + p.o_s1), *s2 = (const float *)(ctx->host_w.data() + p.o_s2);
-        a.slopes_le1 = 1;
-        for (int c = 0; c < p.Npad; ++c)
-            if (!(s1[c] <= 1.f) || !(s2[c] <= 1.f)) a.slopes_le1 = 0;
-        // fp32 range scaling: the input's measured range, the weights' exponent, this output measured
-        a.rg.amax_in = words_of(in);
+        a.slopes_le1 = slopes_le1(ctx, {&p});
         a.rg.sw[0] = p.sw;
-        a.rg.off = ctx->range_off;
-        if (out && epi != EPI_CLASSES) {
-            a.rg.amax_out = take_words();
-            wrote(out, a.rg.amax_out);
-        }
-        op.a = a; op.nr = p.nr; op.epi = epi;
+        range_io(a.rg, in, out, out && epi != EPI_CLASSES);
         op.flops = 2.0 * p.macs_per_px * a.M;
         op.bytes = (double)B * si.H * si.W * si.C * es + (double)p.Npad * p.Kpad * es +
                    (epi == EPI_CLASSES ? 0.0 : (double)B * so.H * so.W * so.C * es);
+        ops.push_back(op);
+        return ops.back();
     }
 
-    bool run(bool fill, std::string &why) {
+    void initial(const BlockDesc &b) {
+        Shape so{H / 2, W / 2, cstore(P(0).cout)};
+        szX = std::max(szX, tbytes(so));
+        if (fill) {
+            ConvArgs &a = args(conv(P(0), EPI_INIT, curp, cur, so, dst, so));
+            a.cconv = b.attrs[1]; a.cpool = b.attrs[0]; a.pool_k = b.attrs[2];
+            a.CinS = 8;
+        }
+        cur = so;
+    }
+
+    void down(const BlockDesc &b) {
+        Shape s1{cur.H / 2, cur.W / 2, cstore(P(0).cout)}, s2{s1.H, s1.W, cstore(P(1).cout)};
+        Shape so{s1.H, s1.W, cstore(P(2).cout)};
+        const int idxCS = cstore(b.attrs[0]);
+        szT = std::max({szT, tbytes(s1), tbytes(s2)});
+        szX = std::max(szX, tbytes(so));
+        if (!fill) szIdx[bi] = (size_t)B * so.H * so.W * idxCS;
+        const int dv = cur.C == b.attrs[0] ? fusable_down(ctx, b, *ids) : -1;
+        const Shape sp{so.H, so.W, idxCS};
+        if (dv >= 0) szT = std::max(szT, tbytes(sp));
+        if (fill && dv >= 0) {
+            // one launch: 2x2 projection + 3x3 + expansion + pooled main branch (pooled values
+            // through the T[0] scratch, read back as the residual)
+            Op op;
+            BneckLaunch &l = op.l.emplace<BneckLaunch>();
+            l.C = b.attrs[1]; l.var = dv; l.cin = b.attrs[0];
+            BneckArgs &q = l.a;
+            int th, tw, nw;
+            bneck_shape(l.C, dv, th, tw, nw, nullptr);
+            q.x = nullptr; q.out = dst; q.B = B; q.H = so.H; q.W = so.W;
+            q.dt = 1; q.phases = 1; q.tr = 0;
+            q.tiles_y = (so.H + th - 1) / th; q.tiles_x = (so.W + tw - 1) / tw;
+            q.ntiles = B * q.tiles_y * q.tiles_x;
+            wire_bneck(q, P(0), P(1), P(1), P(2));
+            q.xin = curp;                             // (x_bytes: build_plan, as for every fused bottleneck)
+            q.xin_bytes = clamp31(tbytes(cur));
+            q.pool = T[0];
+            q.pool_bytes = clamp31(tbytes(sp));
+            q.idx_out = idx[bi]; q.idxCS = idxCS;
+            q.idx_bytes = clamp31((size_t)B * so.H * so.W * idxCS);
+            range_io(q.rg, curp, dst);
+            const double px = (double)B * so.H * so.W;
+            double wb, fl;
+            sums(3, px, wb, fl);
+            op.flops = fl;
+            // x read once, out + indices written once (the pooled scratch round trip is L2)
+            op.bytes = (double)tbytes(cur) + (double)tbytes(so) + px * idxCS + wb;
+            op.layer_bytes = (double)tbytes(cur) * 2 + 2.0 * (tbytes(s1) + tbytes(s2)) + (double)tbytes(so) +
+                             px * idxCS + wb;
+            ops.push_back(op);
+        } else if (fill) {
+            conv(P(0), EPI_PLAIN, curp, cur, s1, T[0], s1);
+            conv(P(1), EPI_PLAIN, T[0], s1, s2, T[1], s2);
+            Op &o3 = conv(P(2), EPI_RESPOOL, T[1], s2, so, dst, so);
+            residual(args(o3), curp, cur, b.attrs[0]);
+            args(o3).idx_out = idx[bi]; args(o3).idxCS = idxCS;
+            o3.bytes += (double)B * cur.H * cur.W * cur.C * es + (double)B * so.H * so.W * idxCS;
+        }
+        cur = so;
+    }
+
+    void regular(const BlockDesc &b) {
+        const int nu = (int)b.units.size();
+        int rr = 0, dd = 1, ty = 0, tx = 0, ttr = 0, trd = 0, var = -1;
+        if (fusable_regular(ctx, b, *ids, rr, dd))
+            var = pick_bneck_variant(ctx, b.attrs[0], nu == 4, dd, B, cur.H, cur.W, ty, tx, ttr, trd);
+        if (var >= 0) {
+            // one launch: projection + middle conv + expansion + residual, internals in LDS
+            szX = std::max(szX, tbytes(cur));
+            if (!fill) return;
+            Op op;
+            BneckLaunch &l = op.l.emplace<BneckLaunch>();
+            l.C = b.attrs[0]; l.asym = nu == 4; l.var = var;
+            BneckArgs &q = l.a;
+            const Packed &p2b = P(nu == 4 ? 2 : 1);
+            q.x = curp; q.out = dst; q.B = B; q.H = cur.H; q.W = cur.W;
+            q.dt = dd; q.phases = trd ? dd : dd * dd; q.tr = ttr;
+            q.tiles_y = ty; q.tiles_x = tx;
+            q.ntiles = B * q.phases * ty * tx;
+            wire_bneck(q, P(0), P(1), p2b, P(nu - 1));
+            row_bound(p2b, 0, p2b.cout, q.rg.n[2], q.rg.c[2]);
+            range_io(q.rg, curp, dst);
+            const double px = (double)B * cur.H * cur.W;
+            double wb, fl, lb = 0;
+            sums(nu, px, wb, fl);
+            for (int i = 0; i < nu; ++i) lb += px * (cstore(b.units[i].cin) + cstore(b.units[i].cout)) * es;   // layer by layer
+            op.flops = fl;
+            op.bytes = 2.0 * px * cur.C * es + wb;             // what this launch must move
+            op.layer_bytes = lb + px * cur.C * es + wb;        // + the residual re-read
+            ops.push_back(op);
+            return;
+        }
+        Shape s = cur;
+        const unsigned char *src = curp;
+        for (int i = 0; i < nu; ++i) {
+            const bool last = i + 1 == nu;
+            Shape so{s.H, s.W, cstore(b.units[i].cout)};
+            unsigned char *o = last ? dst : T[i % 3];
+            if (!last) szT = std::max(szT, tbytes(so));
+            else szX = std::max(szX, tbytes(so));
+            if (fill) {
+                Op &op = conv(P(i), last ? EPI_RESADD : EPI_PLAIN, src, s, so, o, so);
+                if (last) {
+                    residual(args(op), curp, cur, b.attrs[0]);
+                    op.bytes += (double)B * cur.H * cur.W * cur.C * es;
+                }
+            }
+            s = so;
+            src = o;
+        }
+        cur = s;
+    }
+
+    void up(const BlockDesc &b) {
+        const int ref = b.attrs[2];
+        Shape sm{cur.H, cur.W, cstore(P(0).cout)}, s1{cur.H, cur.W, cstore(P(1).cout)};
+        Shape st{cur.H * 2, cur.W * 2, cstore(P(2).cout)}, so{cur.H * 2, cur.W * 2, cstore(P(3).cout)};
+        szM = std::max(szM, tbytes(sm));
+        szT = std::max({szT, tbytes(s1), tbytes(st)});
+        szX = std::max(szX, tbytes(so));
+        const int cin_b = b.attrs[0], cout_b = b.attrs[1], it_b = P(1).cout;
+        const int idxCS = cstore(ctx->blocks[(size_t)ref].attrs[0]);
+        const bool fuse_up = ids->size() >= 5 && up_supported(cin_b, it_b, cout_b) && cur.C == cin_b && so.C == cout_b && !no_fuse();
+        const bool pair = ids->size() == 6;
+        // unfused, paired: the main and extension 1x1 outputs share one tensor (main channels first)
+        Shape sp{cur.H, cur.W, pair ? sm.C + s1.C : sm.C};
+        if (!fuse_up) szM = std::max(szM, tbytes(sp));
+        if (fill && fuse_up) {
+            // one launch: x read once, out written once, everything else in registers
+            Op op;
+            UpLaunch &l = op.l.emplace<UpLaunch>();
+            l.cin = cin_b; l.it = it_b; l.cout = cout_b;
+            UpArgs &q = l.a;
+            const Packed &p1 = P(4), &p2 = P(2), &p3 = P(3);
+            q.x = curp; q.idx = idx[(size_t)ref]; q.out = dst;
+            q.M = B * cur.H * cur.W; q.h = cur.H; q.w = cur.W;
+            q.y0 = 0; q.hwin = cur.H;                 // the full frame (narrow: a window)
+            q.idxCS = idxCS;
+            fastdiv((uint32_t)(cur.H * cur.W), q.mHW, q.sHW);
+            fastdiv((uint32_t)cur.W, q.mW, q.sW);
+            wire(p1, q.w1, q.b1, q.s1);
+            wire(p2, q.w2, q.b2, q.s2);
+            wire(p3, q.w3, q.b3, q.s3);
+            q.s_out = slope2(p3);
+            q.slopes_le1 = slopes_le1(ctx, {&p1, &p2, &p3});
+            q.rg.sw[0] = p1.sw; q.rg.sw[1] = p2.sw; q.rg.sw[2] = p3.sw;
+            row_bound(p1, cout_b, cout_b + it_b, q.rg.n[0], q.rg.c[0]);   // the pair's e1 rows
+            row_bound(p2, 0, p2.Npad, q.rg.n[1], q.rg.c[1]);
+            range_io(q.rg, curp, dst);
+            q.x_bytes = clamp31(tbytes(cur));
+            q.idx_bytes = clamp31((size_t)B * cur.H * cur.W * idxCS);
+            q.out_bytes = clamp31(tbytes(so));
+            const double px = (double)B * cur.H * cur.W;
+            double wb, fl;
+            sums(4, px, wb, fl);
+            op.flops = fl;
+            op.bytes = px * cur.C * es + px * idxCS + 4.0 * px * so.C * es + wb;   // x + idx in, out
+            op.layer_bytes = px * cur.C * es * 2 + px * (sm.C + s1.C) * es + px * s1.C * es + 4.0 * px * st.C * es * 2 +
+                             px * sm.C * es + px * idxCS + 4.0 * px * so.C * es + wb;
+            ops.push_back(op);
+        } else if (fill) {
+            if (pair) {
+                conv(P(4), EPI_PLAIN, curp, cur, sp, Mb, sp);
+                conv(P(5), EPI_SHUFFLE, Mb, sp, sp, T[1], st).bytes -= (double)B * sp.H * sp.W * sm.C * es;   // reads only the extension half
+            } else {
+                conv(P(0), EPI_PLAIN, curp, cur, sm, Mb, sm);
+                conv(P(1), EPI_PLAIN, curp, cur, s1, T[0], s1);
+                conv(P(2), EPI_SHUFFLE, T[0], s1, s1, T[1], st);
+            }
+            Op &o2 = conv(P(3), EPI_RESUNPOOL, T[1], st, so, dst, so);
+            residual(args(o2), Mb, sp, b.attrs[1]);
+            args(o2).idx_in = idx[(size_t)ref]; args(o2).idxCS = idxCS;
+            o2.bytes += (double)B * sm.H * sm.W * sm.C * es + (double)B * sm.H * sm.W * idxCS;
+        }
+        cur = so;
+    }
+
+    bool fullconv(std::string &why) {
+        Shape so{cur.H * 2, cur.W * 2, P(0).cout};
+        if (so.H != H || so.W != W) { why = "network does not return to the input resolution"; return false; }
+        if (fill) args(conv(P(0), EPI_CLASSES, curp, cur, cur, nullptr, so)).ncls = ctx->ncls;
+        cur = so;
+        return true;
+    }
+
+    // fill == false: only the buffer sizes; fill == true (the arena carved): the ops
+    bool run(bool fill_, std::string &why) {
+        fill = fill_;
         es = prec_es(ctx->prec);
         if (H % 8 || W % 8 || H <= 0 || W <= 0 || B <= 0) { why = "H and W must be positive multiples of 8"; return false; }
         const size_t nb = ctx->blocks.size();
         if (!fill) szIdx.assign(nb, 0);
-        Shape cur{H, W, 8};
-        const unsigned char *curp = nullptr;    // engine input, patched per call
+        cur = Shape{H, W, 8};
+        curp = nullptr;
         int xi = 0;
         ops.clear();
         nwords = 1;
         wmap.clear();
-        for (size_t bi = 0; bi < nb; ++bi) {
+        for (bi = 0; bi < nb; ++bi) {
             const BlockDesc &b = ctx->blocks[bi];
-            const std::vector<int> &ids = ctx->block_convs[bi];
-            auto P = [&](int i) -> const Packed & { return ctx->packed[ids[i]]; };
-            unsigned char *dst = X[xi];
+            ids = &ctx->block_convs[bi];
+            dst = X[xi];
             switch (b.type) {
-            case BT_INITIAL: {
-                Shape so{H / 2, W / 2, cstore(P(0).cout)};
-                szX = std::max(szX, tbytes(so));
-                if (fill) {
-                    Op op;
-                    conv(P(0), EPI_INIT, curp, cur, so, dst, so, op);
-                    op.a.cconv = b.attrs[1]; op.a.cpool = b.attrs[0]; op.a.pool_k = b.attrs[2];
-                    op.a.CinS = 8;
-                    ops.push_back(op);
-                }
-                cur = so;
-                break;
-            }
-            case BT_DOWN: {
-                Shape s1{cur.H / 2, cur.W / 2, cstore(P(0).cout)}, s2{s1.H, s1.W, cstore(P(1).cout)};
-                Shape so{s1.H, s1.W, cstore(P(2).cout)};
-                const int idxCS = cstore(b.attrs[0]);
-                szT = std::max({szT, tbytes(s1), tbytes(s2)});
-                szX = std::max(szX, tbytes(so));
-                if (!fill) szIdx[bi] = (size_t)B * so.H * so.W * idxCS;
-                const int dv = cur.C == b.attrs[0] ? fusable_down(ctx, b, ids) : -1;
-                if (dv >= 0) {
-                    // one launch: 2x2 projection + 3x3 + expansion + pooled main branch (pooled values
-                    // through the T[0] scratch, read back as the residual)
-                    const Shape sp{so.H, so.W, idxCS};
-                    szT = std::max(szT, tbytes(sp));
-                    if (fill) {
-                        Op op;
-                        op.kind = 1;
-                        op.bn_c = b.attrs[1];
-                        op.bn_var = dv;
-                        op.bn_cin = b.attrs[0];
-                        BneckArgs &q = op.bn;
-                        std::memset(&q, 0, sizeof(q));
-                        const unsigned char *dw = (const unsigned char *)ctx->dev_w;
-                        const Packed &p1 = P(0), &p2 = P(1), &p3 = P(2);
-                        int th, tw, nw;
-                        bneck_shape(op.bn_c, dv, th, tw, nw, nullptr);
-                        q.x = nullptr; q.out = dst; q.B = B; q.H = so.H; q.W = so.W;
-                        q.dt = 1; q.phases = 1; q.tr = 0;
-                        q.tiles_y = (so.H + th - 1) / th; q.tiles_x = (so.W + tw - 1) / tw;
-                        q.ntiles = B * q.tiles_y * q.tiles_x;
-                        q.w1 = dw + p1.o_w; q.b1 = (const float *)(dw + p1.o_bias); q.s1 = (const float *)(dw + p1.o_s1);
-                        q.w2 = dw + p2.o_w; q.b2 = (const float *)(dw + p2.o_bias); q.s2 = (const float *)(dw + p2.o_s1);
-                        q.w2b = q.w2; q.b2b = q.b2; q.s2b = q.s2;
-                        q.w3 = dw + p3.o_w; q.b3 = (const float *)(dw + p3.o_bias); q.s3 = (const float *)(dw + p3.o_s1);
-                        q.s_out = (const float *)(dw + p3.o_s2);
-                        q.slopes_le1 = 1;
-                        q.x_bytes = (uint32_t)std::min<size_t>(tbytes(so), 0x7fffffff);
-                        q.xin = curp;
-                        q.xin_bytes = (uint32_t)std::min<size_t>(tbytes(cur), 0x7fffffff);
-                        q.pool = T[0];
-                        q.pool_bytes = (uint32_t)std::min<size_t>(tbytes(sp), 0x7fffffff);
-                        q.idx_out = idx[bi]; q.idxCS = idxCS;
-                        q.idx_bytes = (uint32_t)std::min<size_t>((size_t)B * so.H * so.W * idxCS, 0x7fffffff);
-                        q.rg.amax_in = words_of(curp);
-                        q.rg.off = ctx->range_off;
-                        q.rg.sw[0] = p1.sw; q.rg.sw[1] = p2.sw; q.rg.sw[2] = p2.sw; q.rg.sw[3] = p3.sw;
-                        row_bound(p1, 0, p1.cout, q.rg.n[0], q.rg.c[0]);
-                        row_bound(p2, 0, p2.cout, q.rg.n[1], q.rg.c[1]);
-                        q.rg.amax_out = take_words();
-                        wrote(dst, q.rg.amax_out);
-                        const double px = (double)B * so.H * so.W;
-                        double wb = 0, fl = 0;
-                        for (int i = 0; i < 3; ++i) { wb += (double)P(i).Npad * P(i).Kpad * es; fl += 2.0 * P(i).macs_per_px * px; }
-                        op.flops = fl;
-                        // x read once, out + indices written once (the pooled scratch round trip is L2)
-                        op.bytes = (double)tbytes(cur) + (double)tbytes(so) + px * idxCS + wb;
-                        op.layer_bytes = (double)tbytes(cur) * 2 + 2.0 * (tbytes(s1) + tbytes(s2)) + (double)tbytes(so) +
-                                         px * idxCS + wb;
-                        ops.push_back(op);
-                    }
-                    cur = so;
-                    break;
-                }
-                if (fill) {
-                    Op o1, o2, o3;
-                    conv(P(0), EPI_PLAIN, curp, cur, s1, T[0], s1, o1);
-                    conv(P(1), EPI_PLAIN, T[0], s1, s2, T[1], s2, o2);
-                    conv(P(2), EPI_RESPOOL, T[1], s2, so, dst, so, o3);
-                    o3.a.res = curp; o3.a.resH = cur.H; o3.a.resW = cur.W; o3.a.resC = b.attrs[0]; o3.a.resCS = cur.C;
-                    o3.a.idx_out = idx[bi]; o3.a.idxCS = idxCS;
-                    o3.bytes += (double)B * cur.H * cur.W * cur.C * es + (double)B * so.H * so.W * idxCS;
-                    ops.push_back(o1); ops.push_back(o2); ops.push_back(o3);
-                }
-                cur = so;
-                break;
-            }
-            case BT_REGULAR: {
-                const int nu = (int)b.units.size();
-                Shape s = cur;
-                const unsigned char *src = curp;
-                int rr = 0, dd = 1, ty = 0, tx = 0, ttr = 0, trd = 0, var = -1;
-                if (fusable_regular(ctx, b, ids, rr, dd))
-                    var = pick_bneck_variant(ctx, b.attrs[0], nu == 4, dd, B, cur.H, cur.W, ty, tx, ttr, trd);
-                if (var >= 0) {
-                    // one launch: projection + middle conv + expansion + residual, internals in LDS
-                    szX = std::max(szX, tbytes(cur));
-                    if (fill) {
-                        Op op;
-                        op.kind = 1;
-                        op.bn_c = b.attrs[0];
-                        op.bn_asym = nu == 4;
-                        op.bn_var = var;
-                        BneckArgs &q = op.bn;
-                        std::memset(&q, 0, sizeof(q));
-                        const unsigned char *dw = (const unsigned char *)ctx->dev_w;
-                        const Packed &p1 = P(0), &p2 = P(1), &p3 = P(nu - 1), &p2b = P(nu == 4 ? 2 : 1);
-                        q.x = curp; q.out = dst; q.B = B; q.H = cur.H; q.W = cur.W;
-                        q.dt = dd; q.phases = trd ? dd : dd * dd; q.tr = ttr;
-                        q.tiles_y = ty; q.tiles_x = tx;
-                        q.ntiles = B * q.phases * ty * tx;
-                        q.w1 = dw + p1.o_w; q.b1 = (const float *)(dw + p1.o_bias); q.s1 = (const float *)(dw + p1.o_s1);
-                        q.w2 = dw + p2.o_w; q.b2 = (const float *)(dw + p2.o_bias); q.s2 = (const float *)(dw + p2.o_s1);
-                        q.w2b = dw + p2b.o_w; q.b2b = (const float *)(dw + p2b.o_bias); q.s2b = (const float *)(dw + p2b.o_s1);
-                        q.w3 = dw + p3.o_w; q.b3 = (const float *)(dw + p3.o_bias); q.s3 = (const float *)(dw + p3.o_s1);
-                        q.s_out = (const float *)(dw + p3.o_s2);
-                        q.rg.amax_in = words_of(curp);
-                        q.rg.off = ctx->range_off;
-                        q.rg.sw[0] = p1.sw; q.rg.sw[1] = p2.sw; q.rg.sw[2] = p2b.sw; q.rg.sw[3] = p3.sw;
-                        row_bound(p1, 0, p1.cout, q.rg.n[0], q.rg.c[0]);
-                        row_bound(p2, 0, p2.cout, q.rg.n[1], q.rg.c[1]);
-                        row_bound(p2b, 0, p2b.cout, q.rg.n[2], q.rg.c[2]);
-                        q.rg.amax_out = take_words();
-                        wrote(dst, q.rg.amax_out);
-                        q.slopes_le1 = 1;
-                        const std::pair<size_t, int> slopes[] = {{p1.o_s1, p1.Npad}, {p2.o_s1, p2.Npad}, {p2b.o_s1, p2b.Npad},
-                                                                 {p3.o_s1, p3.Npad}, {p3.o_s2, p3.Npad}};
-                        for (const auto &sv : slopes) {
-                            const float *sl = (const float *)(ctx->host_w.data() + sv.first);
-                            for (int c = 0; c < sv.second; ++c)
-                                if (!(sl[c] <= 1.f)) q.slopes_le1 = 0;
-                        }
-                        double fl = 0, wb = 0, lb = 0;
-                        const double px = (double)B * cur.H * cur.W;
-                        for (int i = 0; i < nu; ++i) {
-                            fl += 2.0 * P(i).macs_per_px * px;
-                            wb += (double)P(i).Npad * P(i).Kpad * es;
-                            lb += px * (cstore(b.units[i].cin) + cstore(b.units[i].cout)) * es;   // layer by layer
-                        }
-                        op.flops = fl;
-                        op.bytes = 2.0 * px * cur.C * es + wb;             // what this launch must move
-                        op.layer_bytes = lb + px * cur.C * es + wb;        // + the residual re-read
-                        ops.push_back(op);
-                    }
-                    break;
-                }
-                for (int i = 0; i < nu; ++i) {
-                    const UnitDesc &u = b.units[i];
-                    const bool last = i + 1 == nu;
-                    Shape so{s.H, s.W, cstore(u.cout)};
-                    unsigned char *o = last ? dst : T[i % 3];
-                    if (!last) szT = std::max(szT, tbytes(so));
-                    else szX = std::max(szX, tbytes(so));
-                    if (fill) {
-                        Op op;
-                        conv(P(i), last ? EPI_RESADD : EPI_PLAIN, src, s, so, o, so, op);
-                        if (last) {
-                            op.a.res = curp; op.a.resH = cur.H; op.a.resW = cur.W; op.a.resC = b.attrs[0]; op.a.resCS = cur.C;
-                            op.bytes += (double)B * cur.H * cur.W * cur.C * es;
-                        }
-                        ops.push_back(op);
-                    }
-                    s = so;
-                    src = o;
-                }
-                cur = s;
-                break;
-            }
-            case BT_UP: {
-                const int ref = b.attrs[2];
-                Shape sm{cur.H, cur.W, cstore(P(0).cout)}, s1{cur.H, cur.W, cstore(P(1).cout)};
-                Shape st{cur.H * 2, cur.W * 2, cstore(P(2).cout)}, so{cur.H * 2, cur.W * 2, cstore(P(3).cout)};
-                szM = std::max(szM, tbytes(sm));
-                szT = std::max({szT, tbytes(s1), tbytes(st)});
-                szX = std::max(szX, tbytes(so));
-                const int cin_b = b.attrs[0], cout_b = b.attrs[1], it_b = P(1).cout;
-                const char *nf = std::getenv("BUGSEG_NO_FUSE");
-                const bool fuse_up = ids.size() >= 5 && up_supported(cin_b, it_b, cout_b) && cur.C == cin_b &&
-                                     so.C == cout_b && !(nf && *nf && *nf != '0');
-                if (fuse_up) {
-                    // one launch: x read once, out written once, everything else in registers
-                    if (fill) {
-                        Op op;
-                        op.kind = 2;
-                        op.up_cin = cin_b; op.up_it = it_b; op.up_cout = cout_b;
-                        UpArgs &q = op.up;
-                        const unsigned char *dw = (const unsigned char *)ctx->dev_w;
-                        const Packed &p1 = P(4), &p2 = P(2), &p3 = P(3);
-                        q.x = curp; q.idx = idx[ref]; q.out = dst;
-                        q.M = B * cur.H * cur.W; q.h = cur.H; q.w = cur.W;
-                        q.y0 = 0; q.hwin = cur.H;                 // the full frame (window_plan narrows them)
-                        q.idxCS = cstore(ctx->blocks[ref].attrs[0]);
-                        fastdiv((uint32_t)(cur.H * cur.W), q.mHW, q.sHW);
-                        fastdiv((uint32_t)cur.W, q.mW, q.sW);
-                        q.w1 = dw + p1.o_w; q.b1 = (const float *)(dw + p1.o_bias); q.s1 = (const float *)(dw + p1.o_s1);
-                        q.w2 = dw + p2.o_w; q.b2 = (const float *)(dw + p2.o_bias); q.s2 = (const float *)(dw + p2.o_s1);
-                        q.w3 = dw + p3.o_w; q.b3 = (const float *)(dw + p3.o_bias); q.s3 = (const float *)(dw + p3.o_s1);
-                        q.s_out = (const float *)(dw + p3.o_s2);
-                        q.rg.amax_in = words_of(curp);
-                        q.rg.off = ctx->range_off;
-                        q.rg.sw[0] = p1.sw; q.rg.sw[1] = p2.sw; q.rg.sw[2] = p3.sw;
-                        row_bound(p1, cout_b, cout_b + it_b, q.rg.n[0], q.rg.c[0]);   // the pair's e1 rows
-                        row_bound(p2, 0, p2.Npad, q.rg.n[1], q.rg.c[1]);
-                        q.rg.amax_out = take_words();
-                        wrote(dst, q.rg.amax_out);
-                        q.x_bytes = (uint32_t)std::min<size_t>((size_t)B * cur.H * cur.W * cur.C * es, 0x7fffffff);
-                        q.idx_bytes = (uint32_t)std::min<size_t>((size_t)B * cur.H * cur.W * q.idxCS, 0x7fffffff);
-                        q.out_bytes = (uint32_t)std::min<size_t>((size_t)B * so.H * so.W * so.C * es, 0x7fffffff);
-                        q.slopes_le1 = 1;
-                        const std::pair<size_t, int> sl[] = {{p1.o_s1, p1.Npad}, {p2.o_s1, p2.Npad}, {p3.o_s1, p3.Npad},
-                                                             {p3.o_s2, p3.Npad}};
-                        for (const auto &v : sl) {
-                            const float *f = (const float *)(ctx->host_w.data() + v.first);
-                            for (int c = 0; c < v.second; ++c)
-                                if (!(f[c] <= 1.f)) q.slopes_le1 = 0;
-                        }
-                        const double px = (double)B * cur.H * cur.W;
-                        double wb = 0, fl = 0;
-                        for (int i = 0; i < 4; ++i) { wb += (double)P(i).Npad * P(i).Kpad * es; fl += 2.0 * P(i).macs_per_px * px; }
-                        op.flops = fl;
-                        op.bytes = px * cur.C * es + px * q.idxCS + 4.0 * px * so.C * es + wb;   // x + idx in, out
-                        op.layer_bytes = px * cur.C * es * 2 + px * (sm.C + s1.C) * es + px * s1.C * es + 4.0 * px * st.C * es * 2 +
-                                         px * sm.C * es + px * q.idxCS + 4.0 * px * so.C * es + wb;
-                        ops.push_back(op);
-                    }
-                    cur = so;
-                    break;
-                }
-                const bool pair = ids.size() == 6;
-                // paired: the main and extension 1x1 outputs share one tensor (main channels first)
-                Shape sp{cur.H, cur.W, pair ? sm.C + s1.C : sm.C};
-                szM = std::max(szM, tbytes(sp));
-                if (fill && pair) {
-                    Op om1, ot, o2;
-                    conv(P(4), EPI_PLAIN, curp, cur, sp, Mb, sp, om1);
-                    conv(P(5), EPI_SHUFFLE, Mb, sp, sp, T[1], st, ot);
-                    ot.bytes -= (double)B * sp.H * sp.W * sm.C * es;    // reads only the extension half
-                    conv(P(3), EPI_RESUNPOOL, T[1], st, so, dst, so, o2);
-                    o2.a.res = Mb; o2.a.resH = sp.H; o2.a.resW = sp.W; o2.a.resC = b.attrs[1]; o2.a.resCS = sp.C;
-                    o2.a.idx_in = idx[ref]; o2.a.idxCS = cstore(ctx->blocks[ref].attrs[0]);
-                    o2.bytes += (double)B * sm.H * sm.W * sm.C * es + (double)B * sm.H * sm.W * o2.a.idxCS;
-                    ops.push_back(om1); ops.push_back(ot); ops.push_back(o2);
-                } else if (fill) {
-                    Op om, o1, ot, o2;
-                    conv(P(0), EPI_PLAIN, curp, cur, sm, Mb, sm, om);
-                    conv(P(1), EPI_PLAIN, curp, cur, s1, T[0], s1, o1);
-                    conv(P(2), EPI_SHUFFLE, T[0], s1, s1, T[1], st, ot);
-                    conv(P(3), EPI_RESUNPOOL, T[1], st, so, dst, so, o2);
-                    o2.a.res = Mb; o2.a.resH = sm.H; o2.a.resW = sm.W; o2.a.resC = b.attrs[1]; o2.a.resCS = sm.C;
-                    o2.a.idx_in = idx[ref]; o2.a.idxCS = cstore(ctx->blocks[ref].attrs[0]);
-                    o2.bytes += (double)B * sm.H * sm.W * sm.C * es + (double)B * sm.H * sm.W * o2.a.idxCS;
-                    ops.push_back(om); ops.push_back(o1); ops.push_back(ot); ops.push_back(o2);
-                }
-                cur = so;
-                break;
-            }
-            case BT_FULLCONV: {
-                Shape so{cur.H * 2, cur.W * 2, P(0).cout};
-                if (so.H != H || so.W != W) { why = "network does not return to the input resolution"; return false; }
-                if (fill) {
-                    Op op;
-                    conv(P(0), EPI_CLASSES, curp, cur, cur, nullptr, so, op);
-                    op.a.ncls = ctx->ncls;
-                    ops.push_back(op);
-                }
-                cur = so;
-                break;
-            }
+            case BT_INITIAL: initial(b); break;
+            case BT_DOWN: down(b); break;
+            case BT_REGULAR: regular(b); break;
+            case BT_UP: up(b); break;
+            case BT_FULLCONV: if (!fullconv(why)) return false; break;
             }
             if (b.type != BT_FULLCONV) {
                 curp = dst;
@@ -1258,6 +1270,22 @@ bool finish_conv_args(ConvArgs &a, int epi, size_t es) {
     return true;
 }
 
+// The class-fused launch (Plan::cls_ok) of the last bottleneck q and the class layer l: q's arguments, 15 x
+// 15-strided 16 x 16 tiles, no block output or range words written, l's weights and bias; the class map and
+// its LUT are the forward's (bind)
+Launch cls_fused_launch(const BneckLaunch &q, const ConvArgs &l) {
+    BneckLaunch f = q;
+    f.cls = true;
+    BneckArgs &a = f.a;
+    a.rg.amax_out = nullptr;
+    a.tr = 0;
+    a.tiles_y = (a.H + 14) / 15; a.tiles_x = (a.W + 14) / 15;
+    a.ntiles = a.B * a.tiles_y * a.tiles_x;
+    a.cw = l.w; a.cbias = l.bias; a.ncls = l.ncls; a.csw = l.rg.sw[0];
+    a.cls_bytes = (uint32_t)((size_t)l.B * l.Hout * l.Wout);
+    return f;
+}
+
 bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *stream = nullptr) {
     Plan &pl = ctx->plan;
     if (pl.arena && pl.B == B && pl.H == H && pl.W == W) return true;
@@ -1289,14 +1317,16 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
     if (!w.run(true, why)) return false;
     if (words_bytes && w.nwords > Walker::max_words(ctx->blocks.size())) { why = "range words: plan too long"; return false; }
     for (Op &op : w.ops) {
-        if (op.kind == 1) {
-            const double bytes = (double)op.bn.B * op.bn.H * op.bn.W * op.bn_c * w.es;
-            const double in_bytes = op.bn_cin ? 4.0 * op.bn.B * op.bn.H * op.bn.W * op.bn_cin * w.es : 0.0;
-            if (bytes >= 2147483648.0 || in_bytes >= 2147483648.0) { why = "batch too large for 32-bit tensor offsets"; return false; }
-            op.bn.x_bytes = (uint32_t)bytes;
-            continue;
+        bool fits = true;
+        if (BneckLaunch *b = std::get_if<BneckLaunch>(&op.l)) {
+            const double bytes = (double)b->a.B * b->a.H * b->a.W * b->C * w.es;
+            const double in_bytes = b->cin ? 4.0 * b->a.B * b->a.H * b->a.W * b->cin * w.es : 0.0;
+            fits = bytes < 2147483648.0 && in_bytes < 2147483648.0;
+            if (fits) b->a.x_bytes = (uint32_t)bytes;
+        } else if (ConvLaunch *c = std::get_if<ConvLaunch>(&op.l)) {
+            fits = finish_conv_args(c->a, c->epi, w.es);
         }
-        if (!finish_conv_args(op.a, op.epi, w.es)) { why = "batch too large for 32-bit tensor offsets"; return false; }
+        if (!fits) { why = "batch too large for 32-bit tensor offsets"; return false; }
     }
     pl.ops = std::move(w.ops);
     int issued = 0;
@@ -1306,13 +1336,14 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
         if (*to >= '0' && *to <= '2' && !to[1]) pl.tile_order = *to - '0';
     pl.cls_ok = false;
     pl.cls_on = false;
-    if (pl.ops.size() >= 2) {
-        const Op &l = pl.ops.back(), &q = pl.ops[pl.ops.size() - 2];
-        const char *fe = std::getenv("BUGSEG_CLS_FUSE");
-        pl.cls_ok = fe && *fe == '1' && l.kind == 0 && l.epi == EPI_CLASSES && cls_supported(l.a) &&
-                    !std::getenv("BUGSEG_CLS_CONV") && q.kind == 1 && q.bn_c == 16 && !q.bn_asym && q.bn_cin == 0 &&
-                    q.bn.dt == 1 && q.bn.phases == 1 && q.bn.out == l.a.in && l.a.B == q.bn.B && l.a.Hin == q.bn.H &&
-                    l.a.Win == q.bn.W && (double)B * l.a.Hout * l.a.Wout < 2147483648.0;
+    pl.bound = Binding();
+    const char *fe = std::getenv("BUGSEG_CLS_FUSE");
+    if (fe && *fe == '1' && pl.ops.size() >= 2 && pl.ops.back().class_kernel()) {
+        const ConvArgs &l = pl.ops.back().conv()->a;
+        const Op &q = pl.ops[pl.ops.size() - 2];
+        pl.cls_ok = q.regular(16, l.Hin) && q.bneck()->a.out == l.in && l.B == q.bneck()->a.B && l.Win == q.bneck()->a.W &&
+                    (double)B * l.Hout * l.Wout < 2147483648.0;
+        if (pl.cls_ok) pl.cls_fused = cls_fused_launch(*q.bneck(), l);
     }
     pl.idx = w.idx;
     pl.idx_bytes = w.szIdx;
@@ -1397,6 +1428,36 @@ int stage3_windows(int h, int y0, int y1, int n, const S3Desc *blk, F tile_rows,
     return k;
 }
 
+// The full-frame launch `full` narrowed to its window w of a forward for class rows [row0, row1): the same
+// arguments with the per-frame extent cut to the window's rows and its first row as an offset; walk direction,
+// XCD grouping and range words as in the full launch, over the smaller count. All the window arithmetic of the
+// launch path is here. s3: a stage-3 block (WinPlan::s3), which takes the windowed kernels.
+Launch narrow(const Launch &full, const WinOp &w, bool s3, int row0, int row1) {
+    Launch l = full;
+    const int rows = w.y1 - w.y0;
+    if (BneckLaunch *b = std::get_if<BneckLaunch>(&l)) {
+        BneckArgs &q = b->a;
+        b->var = w.var;
+        b->win = s3;
+        q.tr = w.tr; q.tiles_x = w.tiles_x; q.tiles_y = w.tiles_y;
+        q.ntiles = q.B * q.phases * q.tiles_y * q.tiles_x;   // (the decoder's blocks: one phase)
+        q.oy_base = w.y0;
+        if (s3) q.oy_end = w.y1;
+    } else if (UpLaunch *u = std::get_if<UpLaunch>(&l)) {
+        UpArgs &q = u->a;
+        q.y0 = w.y0; q.hwin = rows;
+        q.M = (q.M / q.h) * rows;                            // B * rows * w
+        fastdiv((uint32_t)(rows * q.w), q.mHW, q.sHW);
+    } else {
+        ConvArgs &q = std::get<ConvLaunch>(l).a;             // the class layer
+        q.wy0 = w.y0; q.wrows = rows;
+        q.M = q.B * rows * q.Wg;
+        fastdiv((uint32_t)(rows * q.Wg), q.mHWg, q.sHWg);
+        q.orow0 = row0; q.orow1 = row1;
+    }
+    return l;
+}
+
 // The windowed form of the current plan for class rows [row0, row1), cached by window; nullptr = run the
 // full-frame plan: the window is the whole frame or out of range, or the plan does not end in the six
 // fused launches the windows are defined for (BUGSEG_NO_FUSE, BUGSEG_CLS_CONV, BUGSEG_CLS_FUSE, a class
@@ -1406,78 +1467,69 @@ const WinPlan *window_plan(bugseg_ctx *ctx, int row0, int row1) {
     if (row0 < 0 || row1 > pl.H || row0 >= row1 || (row0 == 0 && row1 == pl.H)) return nullptr;
     for (const WinPlan &w : pl.wins)
         if (w.row0 == row0 && w.row1 == row1) return &w;
-    const int n = (int)pl.ops.size();
-    if (n < WIN_OPS + 1 || pl.cls_ok || std::getenv("BUGSEG_CLS_CONV")) return nullptr;
+    const int n = (int)pl.ops.size(), H = pl.H;
+    if (n < WIN_OPS + 1 || pl.cls_ok) return nullptr;
     const Op *o = &pl.ops[(size_t)(n - WIN_OPS)];
-    auto reg = [&](const Op &q, int C, int h) {
-        return q.kind == 1 && q.bn_c == C && !q.bn_asym && q.bn_cin == 0 && q.bn.dt == 1 && q.bn.phases == 1 && q.bn.H == h;
-    };
-    const int H = pl.H;
-    if (!(o[0].kind == 2 && o[0].up.h == H / 8 && reg(o[1], 64, H / 4) && reg(o[2], 64, H / 4) && o[3].kind == 2 &&
-          o[3].up.h == H / 4 && reg(o[4], 16, H / 2) && o[5].kind == 0 && o[5].epi == EPI_CLASSES && cls_supported(o[5].a) &&
-          o[5].a.Hg == H / 2))
+    if (!(o[0].up_on(H / 8) && o[1].regular(64, H / 4) && o[2].regular(64, H / 4) && o[3].up_on(H / 4) &&
+          o[4].regular(16, H / 2) && o[5].class_kernel() && o[5].conv()->a.Hg == H / 2))
         return nullptr;
+    // the op k blocks before the 128 -> 64 block, as a fused bottleneck (null: none, or another launch form)
+    auto s3b = [&](int k) { return n - WIN_OPS - 1 - k >= 0 ? pl.ops[(size_t)(n - WIN_OPS - 1 - k)].bneck() : nullptr; };
+    // The tile form of block q for the `rows` rows it must produce, into r: the picker's choice for the window,
+    // else (a thin window: none efficient enough) the full frame's. s3: among the untransposed forms with a
+    // windowed kernel. -> image rows per tile row (0: no form).
+    auto form = [&](const BneckLaunch &q, int rows, bool s3, WinOp &r) {
+        auto built = [&](int v) { return !s3 || bneck_slots_per_cu(ctx->prec, q.C, q.asym, v, false, 0, true) > 0; };
+        int ty = 0, tx = 0, tr = 0, rd = 0;
+        int v = pick_bneck_variant(ctx, q.C, q.asym, 1, pl.B, rows, q.a.W, ty, tx, tr, rd);
+        if (v < 0 || rd || (s3 && (tr || !built(v)))) { v = q.var; tr = s3 ? 0 : q.a.tr; }
+        if (!built(v)) return 0;
+        int th, tw, nw;
+        bneck_shape(q.C, v, th, tw, nw, nullptr);
+        r.var = v; r.tr = tr;
+        r.te = tr ? tw : th;
+        r.tiles_x = tr ? (q.a.W + th - 1) / th : (q.a.W + tw - 1) / tw;
+        return r.te;
+    };
     WinPlan w;
     w.row0 = row0; w.row1 = row1;
     int win[WIN_OPS][2];
-    row_windows(H, row0, row1, [&](int k, int need0, int need1) {
-        // the tile form for the rows the block must produce; none efficient enough (a thin window): the full frame's
-        const Op &q = o[k];
+    row_windows(H, row0, row1, [&](int k, int need0, int need1) { return form(*o[k].bneck(), need1 - need0, false, w.op[k]); }, win);
+    for (int k = 0; k < WIN_OPS; ++k) {
         WinOp &r = w.op[k];
-        int ty = 0, tx = 0, tr = 0, rd = 0;
-        int v = pick_bneck_variant(ctx, q.bn_c, false, 1, pl.B, need1 - need0, q.bn.W, ty, tx, tr, rd);
-        if (v < 0 || rd) { v = q.bn_var; tr = q.bn.tr; }
-        int th, tw, nw;
-        bneck_shape(q.bn_c, v, th, tw, nw, nullptr);
-        r.var = v; r.tr = tr;
-        r.te = tr ? tw : th;
-        r.tiles_x = tr ? (q.bn.W + th - 1) / th : (q.bn.W + tw - 1) / tw;
-        return r.te;
-    }, win);
-    for (int k = 0; k < WIN_OPS; ++k) { w.op[k].y0 = win[k][0]; w.op[k].y1 = win[k][1]; }
+        r.y0 = win[k][0]; r.y1 = win[k][1];
+        r.tiles_y = (r.y1 - r.y0 + r.te - 1) / r.te;
+        r.l = narrow(o[k].l, r, false, row0, row1);
+    }
     // on into stage 3: the ops before the 128 -> 64 block, while they are fused C = 128 bottlenecks on its input
     // grid whose form has a windowed kernel (fp32). BUGSEG_ROW_WINDOW_S3=0: the decoder's windows only (A/B)
     const char *s3e = std::getenv("BUGSEG_ROW_WINDOW_S3");
     if (!(s3e && *s3e == '0')) {
         S3Desc blk[S3_OPS];
-        int nb = 0;
-        for (; nb < S3_OPS && n - WIN_OPS - 1 - nb >= 0; ++nb) {
-            const Op &q = pl.ops[(size_t)(n - WIN_OPS - 1 - nb)];
-            if (!(q.kind == 1 && q.bn_c == 128 && q.bn_cin == 0 && q.bn.H == H / 8 && q.bn.W == o[0].up.w)) break;
-            int th, tw, nw, rd;
-            bneck_shape(128, q.bn_var, th, tw, nw, &rd);
-            blk[nb].asym = q.bn_asym; blk[nb].d = q.bn.dt; blk[nb].rd = rd;
-            blk[nb].rows_full = rd ? q.bn.phases * q.bn.tiles_y * th : q.bn.tr ? 0 : q.bn.tiles_y * th;
-            if (rd && bneck_slots_per_cu(ctx->prec, 128, false, q.bn_var, false, 0, true) <= 0) blk[nb].rows_full = 0;
+        int nb = 0, th[S3_OPS], tw, nw;
+        for (; nb < S3_OPS; ++nb) {
+            const BneckLaunch *q = s3b(nb);
+            if (!(q && q->C == 128 && q->cin == 0 && q->a.H == H / 8 && q->a.W == o[0].up()->a.w)) break;
+            S3Desc &d = blk[nb];
+            bneck_shape(128, q->var, th[nb], tw, nw, &d.rd);
+            d.asym = q->asym; d.d = q->a.dt;
+            d.rows_full = d.rd ? q->a.phases * q->a.tiles_y * th[nb] : q->a.tr ? 0 : q->a.tiles_y * th[nb];
+            if (d.rd && bneck_slots_per_cu(ctx->prec, 128, false, q->var, false, 0, true) <= 0) d.rows_full = 0;
         }
         int w3[S3_OPS][2];
-        w.ns3 = stage3_windows(H / 8, w.op[0].y0, w.op[0].y1, nb, blk, [&](int k, int need0, int need1) {
-            // the form for the rows the block must produce, among those with a windowed kernel: the picker's
-            // choice for the window, else the full frame's
-            const Op &q = pl.ops[(size_t)(n - WIN_OPS - 1 - k)];
-            WinOp &r = w.s3[k];
-            int ty = 0, tx = 0, tr = 0, rd = 0;
-            int v = pick_bneck_variant(ctx, 128, q.bn_asym, 1, pl.B, need1 - need0, q.bn.W, ty, tx, tr, rd);
-            if (v < 0 || rd || tr || bneck_slots_per_cu(ctx->prec, 128, q.bn_asym, v, false, 0, true) <= 0) v = q.bn_var;
-            if (bneck_slots_per_cu(ctx->prec, 128, q.bn_asym, v, false, 0, true) <= 0) return 0;
-            int th, tw, nw;
-            bneck_shape(128, v, th, tw, nw, nullptr);
-            r.var = v; r.tr = 0; r.te = th;
-            r.tiles_x = (q.bn.W + tw - 1) / tw;
-            return th;
-        }, w3);
+        w.ns3 = stage3_windows(H / 8, w.op[0].y0, w.op[0].y1, nb, blk,
+                               [&](int k, int need0, int need1) { return form(*s3b(k), need1 - need0, true, w.s3[k]); }, w3);
         for (int k = 0; k < w.ns3; ++k) {
-            const Op &q = pl.ops[(size_t)(n - WIN_OPS - 1 - k)];
+            const BneckLaunch &q = *s3b(k);
             WinOp &r = w.s3[k];
             r.y0 = w3[k][0]; r.y1 = w3[k][1];
-            if (blk[k].rd) {
-                int th, tw, nw;
-                bneck_shape(128, q.bn_var, th, tw, nw, nullptr);
-                r.var = q.bn_var; r.tr = 0; r.te = th; r.tiles_x = 1;
-                r.tiles_y = ((r.y1 - r.y0 + q.bn.dt - 1) / q.bn.dt + th - 1) / th;   // the longest row phase
+            if (blk[k].rd) {   // the full frame's form; tiles_y: of the longest row phase
+                r.var = q.var; r.tr = 0; r.te = th[k]; r.tiles_x = 1;
+                r.tiles_y = ((r.y1 - r.y0 + q.a.dt - 1) / q.a.dt + r.te - 1) / r.te;
             } else {
                 r.tiles_y = (r.y1 - r.y0 + r.te - 1) / r.te;
             }
+            r.l = narrow(q, r, true, row0, row1);
         }
     }
     if (pl.wins.size() >= 8) pl.wins.erase(pl.wins.begin());
@@ -1735,86 +1787,68 @@ int bugseg_nchw_to_input(bugseg_ctx *ctx, const void *x, int is_f64, int B, int 
     return BUGSEG_OK;
 }
 
-// the class-fused launch's arguments (Plan::cls_ok): the last bottleneck's, 15 x 15-strided 16 x 16
-// tiles, no block output or range words written, the class op's weights / bias / output / LUT
-static BneckArgs cls_fused_args(const Plan &pl) {
-    const Op &q = pl.ops[pl.ops.size() - 2], &l = pl.ops.back();
-    BneckArgs a = q.bn;
-    a.rg.amax_out = nullptr;
-    a.tr = 0;
-    a.tiles_y = (a.H + 14) / 15;
-    a.tiles_x = (a.W + 14) / 15;
-    a.ntiles = a.B * a.tiles_y * a.tiles_x;
-    a.cw = l.a.w;
-    a.cbias = l.a.bias;
-    a.cls_out = l.a.cls_out;
-    a.cls_bytes = (uint32_t)((size_t)l.a.B * l.a.Hout * l.a.Wout);
-    a.lut = l.a.lut;
-    a.lut_kind = l.a.lut_kind;
-    a.ncls = l.a.ncls;
-    a.csw = l.a.rg.sw[0];
-    return a;
+static hipError_t dispatch(int prec, const ConvLaunch &l, hipStream_t s) { return launch_conv(prec, l.nr, l.epi, l.a, s); }
+static hipError_t dispatch(int prec, const UpLaunch &l, hipStream_t s) { return launch_up(prec, l.cin, l.it, l.cout, l.a, s); }
+static hipError_t dispatch(int prec, const BneckLaunch &l, hipStream_t s) {
+    return l.cls ? launch_bneck_cls(prec, l.a, s) : launch_bneck(prec, l.C, l.asym, l.var, l.a, s, l.cin, l.win);
+}
+// One launch record to its kernel, with its launch-span slots (or null) and its tile walk direction: the one
+// place that sets them.
+static hipError_t issue(int prec, Launch &l, int rev, unsigned long long *span, hipStream_t s) {
+    return std::visit([&](auto &r) {
+        r.a.span = span;
+        r.a.rev = rev;
+        return dispatch(prec, r, s);
+    }, l);
 }
 
-// one plan op, with its launch-span slots when bugseg_debug_set_spans armed them. Its walk direction
-// (Plan::tile_order) follows the number of launches the plan issues before it (Op::pos, counted at plan
-// build from Op::launches), so a single op (bugseg_plan_launch_op) and an op range walk as they do in the
-// whole forward. The last op of a class-fused plan issues nothing; nothing follows it.
-// wp (a row-windowed forward, window_plan): the last WIN_OPS ops run their windows — the same arguments with
-// the per-frame extent narrowed to the window's rows and the first row as an offset; walk direction, XCD
-// grouping and range words as in the full launch, over the smaller count.
+// A forward's binding into a copy of a launch. first: the plan's first op (the initial block) takes the input;
+// last: the class layer, or the class-fused bottleneck, takes the output.
+static void bind(const bugseg_ctx *ctx, const Binding &b, bool first, bool last, Launch &l) {
+    ConvLaunch *c = std::get_if<ConvLaunch>(&l);
+    if (first && c) {
+        c->epi = b.bgr ? EPI_INIT_BGR : EPI_INIT;
+        c->a.in = b.in;
+        c->a.nlut = b.bgr ? (const double *)((const unsigned char *)ctx->dev_luts + 32) : nullptr;
+        c->a.naff_on = b.naff_on;
+        std::memcpy(c->a.naff, ctx->naff, sizeof(ctx->naff));
+        // fp32 range scaling: the BGR input's range is the normalisation table's (static); an engine input
+        // the caller supplied is measured (block 0 of the range words)
+        c->a.rg.amax_in = b.bgr ? nullptr : ctx->plan.words;
+        c->a.rg.amax_static = b.bgr ? ctx->norm_amax : 0.f;
+    }
+    if (!last) return;
+    const uint8_t *luts = (const uint8_t *)ctx->dev_luts;
+    const bool logits = b.out_kind == BUGSEG_OUT_LOGITS_F32;
+    uint8_t *cls_out = logits ? nullptr : (uint8_t *)b.out;
+    const int lut_kind = b.out_kind == BUGSEG_OUT_CLASS3_U8 ? 1 : b.out_kind == BUGSEG_OUT_BINARY_U8 ? 2 : 0;
+    const uint8_t *lut = lut_kind ? luts + 16 * (lut_kind - 1) : nullptr;
+    if (BneckLaunch *f = std::get_if<BneckLaunch>(&l)) {
+        f->a.cls_out = cls_out; f->a.lut = lut; f->a.lut_kind = lut_kind;
+    } else if (c) {
+        c->a.cls_out = cls_out; c->a.lut = lut; c->a.lut_kind = lut_kind;
+        c->a.logits_out = logits ? (float *)b.out : nullptr;
+    }
+}
+
+// One plan op for the last forward's binding (Plan::bound). launch_op only picks the op's record — its windowed
+// launch when wp (a row-windowed forward, window_plan) has one, the class-fused launch when the forward took it
+// (the last op then issues nothing; nothing follows it), else the full-frame launch — binds a copy and issues
+// it. The walk direction (Plan::tile_order) follows the number of launches the plan issues before the op
+// (Op::pos, counted at plan build from Op::launches), so a single op (bugseg_plan_launch_op) and an op range
+// walk as they do in the whole forward; the span slots are those bugseg_debug_set_spans armed.
 static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const WinPlan *wp = nullptr) {
     const Plan &pl = ctx->plan;
-    const Op &o = pl.ops[(size_t)i];
-    const int rev = pl.tile_order == 2 ? 1 : pl.tile_order == 1 ? (o.pos & 1) : 0;
+    const int n = (int)pl.ops.size();
+    if (pl.cls_on && i + 1 == n) return hipSuccess;   // (ran within op i - 1)
+    const bool fused = pl.cls_on && i + 2 == n;
+    const Launch *pick = wp ? wp->launch_of(i, n) : nullptr;
+    if (!pick) pick = fused ? &pl.cls_fused : &pl.ops[(size_t)i].l;
+    Launch l = *pick;
+    bind(ctx, pl.bound, i == 0, fused || i + 1 == n, l);
+    const int rev = pl.tile_order == 2 ? 1 : pl.tile_order == 1 ? (pl.ops[(size_t)i].pos & 1) : 0;
     unsigned long long *sp = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;   // (mfma_common.h: 64 slots x 64 B)
-    const int wk = i - ((int)pl.ops.size() - WIN_OPS);
-    if (wp && wk < 0 && -wk - 1 < wp->ns3) {
-        // a stage-3 block in its windowed form (WinPlan::s3)
-        const WinOp &w = wp->s3[-wk - 1];
-        BneckArgs q = o.bn;
-        q.span = sp; q.rev = rev;
-        q.tr = 0; q.tiles_x = w.tiles_x; q.tiles_y = w.tiles_y;
-        q.ntiles = q.B * q.phases * q.tiles_y * q.tiles_x;
-        q.oy_base = w.y0; q.oy_end = w.y1;
-        return launch_bneck(ctx->prec, o.bn_c, o.bn_asym, w.var, q, s, 0, true);
-    }
-    if (wp && wk >= 0) {
-        const WinOp &w = wp->op[wk];
-        const int rows = w.y1 - w.y0;
-        if (o.kind == 1) {
-            BneckArgs q = o.bn;
-            q.span = sp; q.rev = rev;
-            q.tr = w.tr; q.tiles_x = w.tiles_x;
-            q.tiles_y = (rows + w.te - 1) / w.te;
-            q.ntiles = q.B * q.tiles_y * q.tiles_x;
-            q.oy_base = w.y0;
-            return launch_bneck(ctx->prec, o.bn_c, false, w.var, q, s, 0);
-        }
-        if (o.kind == 2) {
-            UpArgs q = o.up;
-            q.span = sp; q.rev = rev;
-            q.y0 = w.y0; q.hwin = rows;
-            q.M = (q.M / q.h) * rows;                  // B * rows * w
-            fastdiv((uint32_t)(rows * q.w), q.mHW, q.sHW);
-            return launch_up(ctx->prec, o.up_cin, o.up_it, o.up_cout, q, s);
-        }
-        ConvArgs q = o.a;
-        q.span = sp; q.rev = rev;
-        q.wy0 = w.y0; q.wrows = rows;
-        q.M = q.B * rows * q.Wg;
-        fastdiv((uint32_t)(rows * q.Wg), q.mHWg, q.sHWg);
-        q.orow0 = wp->row0; q.orow1 = wp->row1;
-        return launch_conv(ctx->prec, o.nr, o.epi, q, s);
-    }
-    if (pl.cls_on && i + 2 == (int)pl.ops.size()) { BneckArgs q = cls_fused_args(pl); q.span = sp; q.rev = rev; return launch_bneck_cls(ctx->prec, q, s); }
-    if (pl.cls_on && i + 1 == (int)pl.ops.size()) return hipSuccess;   // (ran within op i - 1)
-    if (o.kind == 1) { BneckArgs q = o.bn; q.span = sp; q.rev = rev; return launch_bneck(ctx->prec, o.bn_c, o.bn_asym, o.bn_var, q, s, o.bn_cin); }
-    if (o.kind == 2) { UpArgs q = o.up; q.span = sp; q.rev = rev; return launch_up(ctx->prec, o.up_cin, o.up_it, o.up_cout, q, s); }
-    ConvArgs q = o.a;
-    q.span = sp;
-    q.rev = rev;
-    return launch_conv(ctx->prec, o.nr, o.epi, q, s);
+    return issue(ctx->prec, l, rev, sp, s);
 }
 
 static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H, int W, int out_kind, void *out,
@@ -1827,25 +1861,7 @@ static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H,
     if (!build_plan(ctx, B, H, W, why, stream)) return fail(ctx, BUGSEG_EINVAL, why);
     Plan &pl = ctx->plan;
     if (stream_capturing(stream)) pl.pinned = true;
-    Op &first = pl.ops.front();
-    first.a.in = in;
-    first.epi = bgr ? EPI_INIT_BGR : EPI_INIT;
-    first.a.nlut = bgr ? (const double *)((const unsigned char *)ctx->dev_luts + 32) : nullptr;
-    first.a.naff_on = bgr && ctx->naff_on && !std::getenv("BUGSEG_INIT_TABLE");
-    std::memcpy(first.a.naff, ctx->naff, sizeof(ctx->naff));
-    // fp32 range scaling: the BGR input's range is the normalisation table's (static); an engine input
-    // the caller supplied is measured (block 0 of the range words)
-    first.a.rg.amax_in = bgr ? nullptr : pl.words;
-    first.a.rg.amax_static = bgr ? ctx->norm_amax : 0.f;
-    ConvArgs &last = pl.ops.back().a;
-    last.cls_out = nullptr; last.logits_out = nullptr; last.lut = nullptr; last.lut_kind = 0;
-    const uint8_t *luts = (const uint8_t *)ctx->dev_luts;
-    switch (out_kind) {
-    case BUGSEG_OUT_LOGITS_F32: last.logits_out = (float *)out; break;
-    case BUGSEG_OUT_CLASS15_U8: last.cls_out = (uint8_t *)out; break;
-    case BUGSEG_OUT_CLASS3_U8: last.cls_out = (uint8_t *)out; last.lut = luts; last.lut_kind = 1; break;
-    case BUGSEG_OUT_BINARY_U8: last.cls_out = (uint8_t *)out; last.lut = luts + 16; last.lut_kind = 2; break;
-    }
+    pl.bound = Binding{in, bgr, bgr && ctx->naff_on && !std::getenv("BUGSEG_INIT_TABLE"), out_kind, out};
     const int nops = (int)pl.ops.size();
     if (last_op < 0 || last_op > nops) last_op = nops;
     if (first_op < 0 || first_op > last_op) return fail(ctx, BUGSEG_EINVAL, "bad op range");
@@ -2350,7 +2366,7 @@ int bugseg_debug_plan_windows(bugseg_ctx *ctx, int row0, int row1, int32_t *win)
     const int n = (int)ctx->plan.ops.size();
     for (int k = 0; k < wp->ns3; ++k) {
         const WinOp &r = wp->s3[k];
-        const int32_t v[5] = {n - WIN_OPS - 1 - k, r.y0, r.y1, r.var, r.tiles_y * r.tiles_x * ctx->plan.ops[(size_t)(n - WIN_OPS - 1 - k)].bn.phases};
+        const int32_t v[5] = {n - WIN_OPS - 1 - k, r.y0, r.y1, r.var, r.tiles_y * r.tiles_x * std::get<BneckLaunch>(r.l).a.phases};
         std::memcpy(win + 5 * k, v, sizeof(v));
     }
     return wp->ns3;
@@ -2360,10 +2376,10 @@ int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_
     if (!ctx || !dst_dev) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     const Plan &pl = ctx->plan;
     if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
-    if (op < 0 || op >= (int)pl.ops.size() || pl.ops[(size_t)op].kind != 1 || bytes != pl.ops[(size_t)op].bn.x_bytes)
-        return fail(ctx, BUGSEG_EINVAL, "not a fused bottleneck launch, or not its output's size");
+    const BneckLaunch *b = op >= 0 && op < (int)pl.ops.size() ? pl.ops[(size_t)op].bneck() : nullptr;
+    if (!b || bytes != b->a.x_bytes) return fail(ctx, BUGSEG_EINVAL, "not a fused bottleneck launch, or not its output's size");
     DeviceGuard g(ctx->device);
-    hipError_t e = hipMemcpyAsync(dst_dev, pl.ops[(size_t)op].bn.out, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    hipError_t e = hipMemcpyAsync(dst_dev, b->a.out, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("read block output: ") + hipGetErrorString(e));
     return BUGSEG_OK;
 }
@@ -2404,15 +2420,14 @@ int bugseg_plan_info(bugseg_ctx *ctx, int B, int H, int W, int out_kind, int bgr
     double lb = 0, pb = 0, fl = 0;
     for (const Op &op : ctx->plan.ops) {
         pb += op.bytes;
-        lb += op.layer_bytes >= 0 ? op.layer_bytes : op.bytes;
+        lb += op.layer();
         fl += op.flops;
     }
     // final epilogue output
     const double fin = out_kind == BUGSEG_OUT_LOGITS_F32 ? (double)B * H * W * ctx->ncls * 4 : (double)B * H * W;
     // class fusion: the last bottleneck's output is neither written nor read back
     if (ctx->plan.cls_ok && out_kind != BUGSEG_OUT_LOGITS_F32) {
-        const Op &q = ctx->plan.ops[ctx->plan.ops.size() - 2];
-        pb -= 2.0 * q.bn.B * q.bn.H * q.bn.W * q.bn_c * prec_es(ctx->prec);
+        pb -= 2.0 * std::get<BneckLaunch>(ctx->plan.cls_fused).a.x_bytes;
     }
     // raw BGR input (bugseg_enet_forward_bgr): 3 bytes per pixel instead of the 8-channel engine input
     double adj = bgr_input ? (double)B * H * W * (8.0 * prec_es(ctx->prec) - 3.0) : 0.0;
@@ -2432,64 +2447,48 @@ int bugseg_plan_op(bugseg_ctx *ctx, int B, int H, int W, int op, char *kernel, i
     if (op < 0 || op >= (int)pl.ops.size()) return fail(ctx, BUGSEG_EINVAL, "op index out of range");
     const Op &o = pl.ops[op];
     const int nops = (int)pl.ops.size();
-    std::string tag;
-    if (pl.cls_on && op + 1 == nops) {
-        // ran within the previous op (class fusion)
-        if (kernel && kernel_len > 0) std::snprintf(kernel, (size_t)kernel_len, "fused");
-        if (alg_bytes) *alg_bytes = 0;
-        if (plan_bytes) *plan_bytes = 0;
-        if (flops) *flops = 0;
+    auto put = [&](const std::string &tag, double lb, double pb, double fl) {
+        if (kernel && kernel_len > 0) {
+            std::strncpy(kernel, tag.c_str(), (size_t)kernel_len - 1);
+            kernel[kernel_len - 1] = 0;
+        }
+        if (alg_bytes) *alg_bytes = lb;
+        if (plan_bytes) *plan_bytes = pb;
+        if (flops) *flops = fl;
         return BUGSEG_OK;
-    }
+    };
+    if (pl.cls_on && op + 1 == nops) return put("fused", 0, 0, 0);   // ran within the previous op (class fusion)
     if (pl.cls_on && op + 2 == nops) {
         // the last bottleneck and the class layer in one launch: block input in, class map out
         const Op &l = pl.ops.back();
-        const double outb = (double)o.bn.B * o.bn.H * o.bn.W * o.bn_c * prec_es(ctx->prec);
-        const double fin = (double)B * H * W;
-        if (kernel && kernel_len > 0) std::snprintf(kernel, (size_t)kernel_len, "bneck C16+classes 16x16");
-        const double lb_b = o.layer_bytes >= 0 ? o.layer_bytes : o.bytes, lb_l = l.layer_bytes >= 0 ? l.layer_bytes : l.bytes;
-        if (alg_bytes) *alg_bytes = lb_b + lb_l + fin;
-        if (plan_bytes) *plan_bytes = o.bytes - outb + (l.bytes - outb) + fin;
-        if (flops) *flops = o.flops + l.flops;
-        return BUGSEG_OK;
+        const double outb = o.bneck()->a.x_bytes, fin = (double)B * H * W;
+        return put("bneck C16+classes 16x16", o.layer() + l.layer() + fin, o.bytes - outb + (l.bytes - outb) + fin, o.flops + l.flops);
     }
-    if (o.kind == 2) {
-        tag = "up C" + std::to_string(o.up_cout);
-    } else if (o.kind == 1) {
+    std::string tag;
+    if (const UpLaunch *u = o.up()) {
+        tag = "up C" + std::to_string(u->cout);
+    } else if (const BneckLaunch *b = o.bneck()) {
         int th, tw, nw;
-        bneck_shape(o.bn_c, o.bn_var, th, tw, nw, nullptr);
-        tag = std::string(o.bn_cin ? "down C" : o.bn_var == BNECK2_V && o.bn_c == 128 ? "bneck2 C" : "bneck C") +
-              std::to_string(o.bn_c) + (o.bn_asym ? " asym" : "") + " " + std::to_string(th) + "x" + std::to_string(tw);
-        (void)nw;
+        bneck_shape(b->C, b->var, th, tw, nw, nullptr);
+        tag = std::string(b->cin ? "down C" : b->var == BNECK2_V && b->C == 128 ? "bneck2 C" : "bneck C") +
+              std::to_string(b->C) + (b->asym ? " asym" : "") + " " + std::to_string(th) + "x" + std::to_string(tw);
     }
-    else if (o.epi == EPI_INIT || o.epi == EPI_INIT_BGR) tag = "init";
-    else if (o.epi == EPI_CLASSES && cls_supported(o.a) && !std::getenv("BUGSEG_CLS_CONV")) tag = "classes";
-    else tag = "conv NR" + std::to_string(o.nr) + " E" + std::to_string(o.epi);
-    if (kernel && kernel_len > 0) {
-        std::strncpy(kernel, tag.c_str(), (size_t)kernel_len - 1);
-        kernel[kernel_len - 1] = 0;
-    }
-    double lb = o.layer_bytes >= 0 ? o.layer_bytes : o.bytes, pb = o.bytes;
-    const int es = prec_es(ctx->prec);
-    if (o.kind == 0 && o.epi == EPI_INIT_BGR) {           // raw BGR input: 3 B/px, not the 8-channel engine input
-        const double adj = (double)B * H * W * (8.0 * es - 3.0);
-        lb -= adj; pb -= adj;
-    }
-    if (o.kind == 0 && o.epi == EPI_CLASSES) {            // the output the last forward asked for
-        const double fin = o.a.logits_out ? (double)B * H * W * ctx->ncls * 4 : (double)B * H * W;
-        lb += fin; pb += fin;
-    }
-    if (alg_bytes) *alg_bytes = lb;
-    if (plan_bytes) *plan_bytes = pb;
-    if (flops) *flops = o.flops;
-    return BUGSEG_OK;
+    else if (o.epi(EPI_INIT)) tag = "init";
+    else if (o.class_kernel()) tag = "classes";
+    else tag = "conv NR" + std::to_string(o.conv()->nr) + " E" + std::to_string(o.conv()->epi);
+    double adj = 0;
+    if (o.epi(EPI_INIT) && pl.bound.bgr)                  // raw BGR input: 3 B/px, not the 8-channel engine input
+        adj = -(double)B * H * W * (8.0 * prec_es(ctx->prec) - 3.0);
+    if (o.epi(EPI_CLASSES))                               // the output the last forward asked for
+        adj = pl.bound.in && pl.bound.out_kind == BUGSEG_OUT_LOGITS_F32 ? (double)B * H * W * ctx->ncls * 4 : (double)B * H * W;
+    return put(tag, o.layer() + adj, o.bytes + adj, o.flops);
 }
 
 int bugseg_plan_launch_op(bugseg_ctx *ctx, int B, int H, int W, int op, void *stream) {
     if (!ctx) return fail(ctx, BUGSEG_EINVAL, "NULL ctx");
     if (!ctx->loaded) return fail(ctx, BUGSEG_ESTATE, "no weights loaded");
     Plan &pl = ctx->plan;
-    if (!pl.arena || pl.B != B || pl.H != H || pl.W != W || !pl.ops.front().a.in)
+    if (!pl.arena || pl.B != B || pl.H != H || pl.W != W || !pl.bound.in)
         return fail(ctx, BUGSEG_ESTATE, "no forward has run at these dimensions");
     if (op < 0 || op >= (int)pl.ops.size()) return fail(ctx, BUGSEG_EINVAL, "op index out of range");
     DeviceGuard g(ctx->device);
