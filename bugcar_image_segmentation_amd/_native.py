@@ -32,7 +32,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
             "bugseg_debug_parse_pack", "bugseg_debug_polar_tables", "bugseg_debug_ctx_info", "bugseg_debug_tile_walk", "bugseg_debug_set_spans", "bugseg_debug_pool_indices",
-            "bugseg_dl_debug_check_plan")
+            "bugseg_dl_debug_check_plan", "bugseg_debug_knobs", "bugseg_dl_debug_knobs")
 DL_OP_FIELDS = 32
 
 
@@ -112,6 +112,8 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_debug_set_spans": (i, [vp, vp, i]),
             "bugseg_debug_pool_indices": (i, [vp, i, i, i, i, vp, sz, ctypes.POINTER(ctypes.c_int), vp]),
             "bugseg_dl_debug_check_plan": (i, [vp, i, vp, i, i, i, i, i, sz]),
+            "bugseg_debug_knobs": (i, [vp, vp, i]),
+            "bugseg_dl_debug_knobs": (i, [vp, vp, i]),
         }
         for name, (res, args) in proto.items():
             f = getattr(lib, name)
@@ -128,6 +130,21 @@ def check(code: int, ctx=None) -> None:
         if code == EINVAL:
             raise ValueError(msg)
         raise BugsegError(code, msg)
+
+
+def knobs(ctx=None, size: int = 4096, dl: bool = False) -> dict[str, int]:
+    """Test hook (bugseg_debug_knobs / bugseg_dl_debug_knobs): the BUGSEG_* run-time knobs as {name: value}:
+    those the context handle `ctx` was created with, or (None; host only, no device) those of the environment
+    as it is now. A bad value, or a `size`-byte buffer too small for the dump, raises ValueError."""
+    lib = load_library()
+    buf = ctypes.create_string_buffer(size)
+    if dl:
+        rc = lib.bugseg_dl_debug_knobs(ctx, buf, size)
+        if rc != OK:
+            raise (ValueError if rc == EINVAL else RuntimeError)(lib.bugseg_dl_last_error(ctx).decode(errors="replace"))
+    else:
+        check(lib.bugseg_debug_knobs(ctx, buf, size), ctx)
+    return {k: int(v) for k, v in (line.split("=") for line in buf.value.decode().splitlines())}
 
 
 def tile_walk(ntiles: int, grid: int, rev: int) -> list[list[int]]:
@@ -307,6 +324,10 @@ class Context:
         scaling off, 2 = weight exponent of packed convolution `arg`."""
         return int(self.lib.bugseg_debug_ctx_info(self.h, what, arg))
 
+    def knobs(self) -> dict[str, int]:
+        """The BUGSEG_* knobs this context was created with (they never change afterwards)."""
+        return knobs(self.h)
+
     def set_spans(self, spans=None):
         """Measurement hook (bugseg_debug_set_spans): a CUDA int64 tensor of 512 words per plan op (64
         [entry, exit] slots, 64 B apart) that later launches fold their clock into (None disarms); ops
@@ -416,6 +437,10 @@ class DeepLabContext:
         r0, r1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
         self._check(self.lib.bugseg_dl_classes_from_logits(self.h, B, H, W, seg.data_ptr(), r0, r1,
                                                            stream_handle(stream)), self.h)
+
+    def knobs(self) -> dict[str, int]:
+        """The BUGSEG_* knobs this context was created with (they never change afterwards)."""
+        return knobs(self.h, dl=True)
 
     def launch_op(self, op, stream=None):
         self._check(self.lib.bugseg_dl_launch_op(self.h, op, ctypes.c_void_p(stream_handle(stream))), self.h)

@@ -1055,35 +1055,28 @@ extern "C" int bugseg_debug_set_bev_stamps(void *p) {
     return hipMemcpyToSymbol(HIP_SYMBOL(bugseg_bev_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -3;
 }
 #endif
-hipError_t launch_bev(const BevArgs &a, hipStream_t s) {
+hipError_t launch_bev(const Knobs &k, const BevArgs &a, hipStream_t s) {
     // form (measured, scripts/bev_probe.py): the gather kernel, 1 frame per thread (BUGSEG_BEV_F = 2 / 4:
-    // frames per thread; BUGSEG_BEV_FG = n > 0: the LDS-staged kernel with n frames per workgroup);
-    // read per call so tests can exercise every form
-    const char *fe = std::getenv("BUGSEG_BEV_F");
-    const int F = fe ? std::atoi(fe) : 1;
+    // frames per thread; BUGSEG_BEV_FG = n > 0: the LDS-staged kernel with n frames per workgroup)
     const long total = (long)a.occ_h * a.occ_w * a.B;
-    const int f = F == 4 ? 4 : F == 1 ? 1 : 2;
+    const int f = k.bev_f ? k.bev_f : 1;
     const long band = (long)((a.occ_h + 7) / 8) * a.occ_w * ((a.B + f - 1) / f);   // items of one XCD
     long gf = 8 * ((band + 255) / 256);
     if (gf > 8192) gf = 8192;
     if (gf < 8) gf = 8;
-    const char *fge = std::getenv("BUGSEG_BEV_FG");
-    const int FG = fge ? std::atoi(fge) : 0;
-    // BUGSEG_BEV_BAND=0: the gather / block-staged forms (A/B and tests)
-    const char *be = std::getenv("BUGSEG_BEV_BAND");
-    const bool banded = (!be || std::atoi(be) != 0) && !fe && FG == 0 && a.in_cols % 16 == 0;
+    // BUGSEG_BEV_BAND=0 (or BUGSEG_BEV_F / _FG set): the gather / block-staged forms (A/B and tests)
+    const bool banded = k.bev_band && !k.bev_f && k.bev_fg == 0 && a.in_cols % 16 == 0;
     if (banded) {
-        // frames per workgroup (BUGSEG_BEV_FB = 1 or 2; read per call)
-        const char *fbe = std::getenv("BUGSEG_BEV_FB");
+        // frames per workgroup (BUGSEG_BEV_FB = 1 or 2)
         // (measured at 32 frames of 480x640: FB = 1 38.7-40.1 us, FB = 2 44.6-48.5 us)
-        const int FB = fbe && std::atoi(fbe) == 2 ? 2 : 1;
+        const int FB = k.bev_fb;
         const dim3 grid(8u * (unsigned)((a.B + FB - 1) / FB), (unsigned)((a.nitems + 7) / 8));   // (frame group x XCD, item slot)
         if (FB == 1) hipLaunchKernelGGL(bev_band_kernel<1>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(bev_band_kernel<2>, grid, dim3(256), 0, s, a);
-    } else if (F != 0 && a.in_cols % 16 == 0 && FG > 0) {
+    } else if (a.in_cols % 16 == 0 && k.bev_fg > 0) {
         const long nblk = (long)((a.occ_w + BEV_CB - 1) / BEV_CB) * ((a.occ_h + BEV_CB - 1) / BEV_CB);
-        const long grid = nblk * ((a.B + FG - 1) / FG);
-        if (grid < (1L << 31)) hipLaunchKernelGGL(bev_occgrid_lds_kernel, dim3((unsigned)grid), dim3(256), 0, s, a, FG);
+        const long grid = nblk * ((a.B + k.bev_fg - 1) / k.bev_fg);
+        if (grid < (1L << 31)) hipLaunchKernelGGL(bev_occgrid_lds_kernel, dim3((unsigned)grid), dim3(256), 0, s, a, k.bev_fg);
     } else if (f == 1) hipLaunchKernelGGL(bev_occgrid_kernel<1>, dim3((unsigned)gf), dim3(256), 0, s, a);
     else if (f == 2) hipLaunchKernelGGL(bev_occgrid_kernel<2>, dim3((unsigned)gf), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(bev_occgrid_kernel<4>, dim3((unsigned)gf), dim3(256), 0, s, a);

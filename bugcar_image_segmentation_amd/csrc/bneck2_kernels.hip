@@ -378,12 +378,11 @@ int bneck2_slots_per_cu() {
     return cached;
 }
 
-hipError_t launch_bneck2(const BneckArgs &a, hipStream_t s) {
+hipError_t launch_bneck2(const Knobs &k, const BneckArgs &a, hipStream_t s) {
     hipError_t e = allow_dynamic_lds((const void *)bneck2_f32_kernel);
     if (e != hipSuccess) return e;
     // one resident round: one workgroup per CU, each walking its two halves' tiles
-    const char *ge = std::getenv("BUGSEG_BNECK_GRID");
-    const int cap = ge && std::atoi(ge) > 0 ? std::atoi(ge) : device_cus() * std::max(1, bneck2_slots_per_cu());
+    const int cap = k.bneck_grid > 0 ? k.bneck_grid : device_cus() * std::max(1, bneck2_slots_per_cu());
     const int want = (a.ntiles + 1) / 2;                     // two tiles per workgroup at a time
     int g = want < cap ? want : cap;
     g = (g + 7) & ~7;

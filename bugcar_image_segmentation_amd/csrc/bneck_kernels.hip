@@ -1870,13 +1870,12 @@ static const void *bneck_fun(int prec, int C, bool asym, int v, bool tr, int cin
                                                             : kfun<float>(C, asym, v, tr);
 }
 
-int bneck_slots_per_cu(int prec, int C, bool asym, int v, bool tr, int cin, bool win) {
+int bneck_slots_per_cu(const Knobs &k, int prec, int C, bool asym, int v, bool tr, int cin, bool win) {
     if (C == 128 && v == BNECK2_V) {
         if (win) return 0;
         // planned only with BUGSEG_BNECK2=1: measured slower (round 6, B = 64, A/B on one box: 103 vs 87 us
         // per launch; bneck2_kernels.hip says why)
-        const char *on = std::getenv("BUGSEG_BNECK2");
-        return prec == PREC_F32 && !asym && !tr && cin == 0 && on && *on == '1' ? bneck2_slots_per_cu() : 0;
+        return prec == PREC_F32 && !asym && !tr && cin == 0 && k.bneck2 ? bneck2_slots_per_cu() : 0;
     }
     // (cached per device and form: launch_bneck asks on every launch; bugseg_runtime.cpp occupancy_per_cu)
     const void *f = bneck_fun(prec, C, asym, v, tr, cin, win);
@@ -1886,9 +1885,9 @@ int bneck_slots_per_cu(int prec, int C, bool asym, int v, bool tr, int cin, bool
     return occupancy_per_cu(f, nw * 64, bneck_lds_bytes(prec, C, asym, v, cin));
 }
 
-hipError_t launch_bneck(int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin, bool win) {
+hipError_t launch_bneck(const Knobs &k, int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin, bool win) {
     if (C == 128 && v == BNECK2_V)
-        return prec == PREC_F32 && !asym && !a.tr && cin == 0 && !win ? launch_bneck2(a, s) : hipErrorInvalidValue;
+        return prec == PREC_F32 && !asym && !a.tr && cin == 0 && !win ? launch_bneck2(k, a, s) : hipErrorInvalidValue;
     const void *f = bneck_fun(prec, C, asym, v, a.tr != 0, cin, win);
     if (!f) return hipErrorInvalidValue;
     int th, tw, nw;
@@ -1899,17 +1898,15 @@ hipError_t launch_bneck(int prec, int C, bool asym, int v, const BneckArgs &a, h
         if (e != hipSuccess) return e;
     }
     // grid: one round of resident workgroups (each walks ntiles / grid tiles, staging its weights
-    // once), or the earlier fixed cap of 2048 (BUGSEG_BNECK_GRID=cap: A/B knob, 0 = resident slots)
-    // (read per launch, so a test can force multi-tile walks at any shape)
+    // once), or the earlier fixed cap of 2048 (BUGSEG_BNECK_GRID=cap: A/B knob, 0 = resident slots; a test
+    // forces multi-tile walks with it at any shape)
     const int n_cu = device_cus();
-    const char *ge = std::getenv("BUGSEG_BNECK_GRID");
-    const int grid_cap = ge ? std::atoi(ge) : 0;
-    int cap = grid_cap;
+    int cap = k.bneck_grid;
     if (cap <= 0) {
         // (BUGSEG_BNECK_GRID=-k: 1/k of the resident slots, at least one per CU — leaves room for a
         // concurrent shard's launch on another stream; A/B knob)
-        const int spc = bneck_slots_per_cu(prec, C, asym, v, a.tr != 0, cin, win);
-        const int per = grid_cap < 0 ? std::max(1, spc / -grid_cap) : spc;
+        const int spc = bneck_slots_per_cu(k, prec, C, asym, v, a.tr != 0, cin, win);
+        const int per = k.bneck_grid < 0 ? std::max(1, spc / -k.bneck_grid) : spc;
         cap = spc > 0 && n_cu > 0 ? per * n_cu : 2048;
     }
     int g = a.ntiles < cap ? a.ntiles : cap;
@@ -1924,7 +1921,7 @@ static const void *kfun_cls(int lk) {
                    : (const void *)bneck_cls_kernel<T, 0>;
 }
 
-hipError_t launch_bneck_cls(int prec, const BneckArgs &a, hipStream_t s) {
+hipError_t launch_bneck_cls(const Knobs &k, int prec, const BneckArgs &a, hipStream_t s) {
     const int lk = a.lut && (a.lut_kind == 1 || a.lut_kind == 2) ? a.lut_kind : 0;
     const void *f = prec == PREC_BF16 ? kfun_cls<__bf16>(lk) : prec == PREC_F16 ? kfun_cls<_Float16>(lk) : kfun_cls<float>(lk);
     const size_t lds = bneck_lds_bytes(prec, 16, false, 0, 0, true);
@@ -1934,9 +1931,7 @@ hipError_t launch_bneck_cls(int prec, const BneckArgs &a, hipStream_t s) {
     }
     // one round of resident workgroups, as launch_bneck
     const int spc = occupancy_per_cu(f, 256, lds), n_cu = device_cus();
-    const char *ge = std::getenv("BUGSEG_BNECK_GRID");
-    const int grid_cap = ge ? std::atoi(ge) : 0;
-    const int cap = grid_cap > 0 ? grid_cap : spc > 0 && n_cu > 0 ? spc * n_cu : 2048;
+    const int cap = k.bneck_grid > 0 ? k.bneck_grid : spc > 0 && n_cu > 0 ? spc * n_cu : 2048;
     int g = a.ntiles < cap ? a.ntiles : cap;
     g = (g + 7) & ~7;
     void *args[] = {const_cast<BneckArgs *>(&a)};

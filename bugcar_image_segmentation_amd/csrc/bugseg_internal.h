@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "knobs.h"
+
 namespace bugseg {
 
 // ---- implicit-GEMM convolution (conv_kernels.hip) -------------------------------------------
@@ -42,7 +44,7 @@ struct RangeArgs {
     float amax_static;      // max |x| when amax_in is nullptr (the BGR input: the normalisation table's max)
     int sw[4];              // weight exponents of the launch's matrices, in launch order
     float n[3], c[3];       // internal tensors: |t_i| <= n[i] * |t_(i-1)| + c[i], t_(-1) = the input
-    int off;                // BUGSEG_F32_RANGE=0 (A/B, negative control of tests/test_gpu_range.py): no scaling
+    int off;                // !Knobs::f32_range: no scaling
 };
 // weight exponent of a matrix whose largest |w| is m (the measured-tensor window of the kernels)
 int range_weight_exp(double m);
@@ -76,7 +78,7 @@ struct ConvArgs {
     const double *nlut;  // EPI_INIT_BGR: [3][256] normalisation table, RGB order (models.py:91)
     float naff[6];       // EPI_INIT_BGR, naff_on: the table as fmaf(v, naff[c], naff[3 + c]) (exact, see bugseg_runtime.cpp)
     int naff_on;
-    int pool_scan;       // init (A/B and tests): 1 = the per-tap pool scan instead of the packed f16 form
+    int pool_scan;       // init (Knobs::init_pool_scan): 1 = the per-tap pool scan instead of the packed f16 form
     int ntiles;
     int rev;             // tile walk direction (tile_walk): 0 ascending, 1 descending
     int stg_elems;       // per-wave output staging (elements)
@@ -138,13 +140,14 @@ int device_cus();
 int occupancy_per_cu(const void *f, int threads, size_t lds);
 hipError_t allow_dynamic_lds(const void *f);
 
-// Launch one convolution. nr = Npad / 16 in {1, 2, 4, 8}. Returns hipSuccess or the launch error.
-hipError_t launch_conv(int prec, int nr, int epi, const ConvArgs &a, hipStream_t s);
+// Launch one convolution. nr = Npad / 16 in {1, 2, 4, 8}. cls: an EPI_CLASSES launch goes to the class kernel
+// (launch_cls; decided once, when the launch record is built). Returns hipSuccess or the launch error.
+hipError_t launch_conv(int prec, int nr, int epi, const ConvArgs &a, hipStream_t s, bool cls = false);
 // pixels per tile for a given nr (sizes the grid)
 int conv_tile_pixels(int nr);
 size_t conv_lds_bytes(int prec, const ConvArgs &a);
 
-// ---- class layer (cls_kernels.hip): EPI_CLASSES launches with 16 input channels land here.
+// ---- class layer (cls_kernels.hip): EPI_CLASSES launches with 16 input channels land here, unless Knobs::cls_conv.
 bool cls_supported(const ConvArgs &a);
 hipError_t launch_cls(int prec, const ConvArgs &a, hipStream_t s);
 
@@ -205,20 +208,20 @@ void bneck_shape(int C, int v, int &th, int &tw, int &nw, int *rd = nullptr);
 // cin > 0: the downsampling form (bneck_kernels.hip) with a cin-channel input; built for (64, v0,
 // cin 16) and (128, v1, cin 64)
 size_t bneck_lds_bytes(int prec, int C, bool asym, int v, int cin = 0, bool cls = false);
-// resident workgroups per CU (occupancy API); 0 if (C, asym, v, tr, cin) is not built
+// resident workgroups per CU (occupancy API); 0 if (C, asym, v, tr, cin) is not built (BNECK2_V: or not Knobs::bneck2)
 // win: the row-windowed form (BneckArgs::oy_end), built for fp32 C = 128 asymmetric 16 x 16 / 20 x 16 / 8 x 16
 // and row-dilated 4 x 80 tiles; the C = 64 / 16 regular forms take their window in the plain form
-int bneck_slots_per_cu(int prec, int C, bool asym, int v, bool tr, int cin = 0, bool win = false);
-hipError_t launch_bneck(int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin = 0, bool win = false);
+int bneck_slots_per_cu(const Knobs &k, int prec, int C, bool asym, int v, bool tr, int cin = 0, bool win = false);
+hipError_t launch_bneck(const Knobs &k, int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin = 0, bool win = false);
 // the C = 16 block with the class layer fused (variant 0, untransposed; tiles 15 apart: tiles_x =
 // ceil(W / 15), tiles_y = ceil(H / 15)); bneck_lds_bytes(..., cls = true) its LDS
-hipError_t launch_bneck_cls(int prec, const BneckArgs &a, hipStream_t s);
+hipError_t launch_bneck_cls(const Knobs &k, int prec, const BneckArgs &a, hipStream_t s);
 // variant BNECK2_V of C = 128 (fp32, symmetric, untransposed 16 x 16 tiles): bneck2_kernels.hip, one
 // 16-wave workgroup per CU running two phase-shifted tiles on one weight copy
 constexpr int BNECK2_V = 5;
 size_t bneck2_lds_bytes();
 int bneck2_slots_per_cu();
-hipError_t launch_bneck2(const BneckArgs &a, hipStream_t s);
+hipError_t launch_bneck2(const Knobs &k, const BneckArgs &a, hipStream_t s);
 
 // ---- fused upsampling bottleneck (up_kernels.hip) ----------------------------------------------
 struct UpArgs {
@@ -294,7 +297,7 @@ struct BevArgs {
     // set by the host from the band records after the table build (bugseg_runtime.cpp bev_occgrid)
     int nitems;
 };
-hipError_t launch_bev(const BevArgs &a, hipStream_t s);
+hipError_t launch_bev(const Knobs &k, const BevArgs &a, hipStream_t s);   // the form: Knobs::bev_*
 hipError_t launch_bev_table(const BevArgs &a, hipStream_t s);
 size_t bev_table_bytes(int occ_w, int occ_h);   // tap table + per-band class-map boxes
 

@@ -11,6 +11,7 @@
 //     indices carved from ONE device arena, sized for the batch (HBM is 288 GB: the arena for
 //     B=64 at 640x480 is a few GB and stays resident between calls);
 //   * enqueues on the caller's stream; no host synchronisation, no allocation once a plan exists.
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -66,6 +67,40 @@ hipError_t bugseg::allow_dynamic_lds(const void *f) {
     return e;
 }
 
+// ---- the one reader of the BUGSEG_* behaviour knobs (knobs.h) and their dump; deeplab_runtime.cpp calls them too
+bool bugseg::read_knobs(Knobs &k, std::string &err) {
+    k = Knobs();
+    auto read = [&](const char *var, int &field, long lo, long hi) {
+        const char *v = std::getenv(var);
+        if (!v || !*v) return true;
+        char *end = nullptr;
+        const long n = std::strtol(v, &end, 10);
+        const bool ok = (*v == '-' || (*v >= '0' && *v <= '9')) && !*end && n >= lo && n <= hi && !(&field == &k.bev_f && n == 3);
+        if (ok) field = (int)n;
+        else err = std::string(var) + "=" + v + ": not a decimal integer this knob takes (" + std::to_string(lo) + " to " + std::to_string(hi) + ")";
+        return ok;
+    };
+#define X(name, field, def, lo, hi) if (!read("BUGSEG_" #name, k.field, lo, hi)) return false;
+    BUGSEG_KNOBS(X)
+#undef X
+    return true;
+}
+int bugseg::dump_knobs(const Knobs *k, char *buf, int len, std::string &err) {
+    Knobs now;
+    if (!k && !read_knobs(now, err)) return BUGSEG_EINVAL;
+    if (!k) k = &now;
+    std::string s;
+#define X(name, field, def, lo, hi) s += "BUGSEG_" #name "=" + std::to_string(k->field) + "\n";
+    BUGSEG_KNOBS(X)
+#undef X
+    if (!buf || len <= (int)s.size()) {
+        err = "the knob dump needs a buffer of " + std::to_string(s.size() + 1) + " bytes";
+        return BUGSEG_EINVAL;
+    }
+    std::memcpy(buf, s.c_str(), s.size() + 1);
+    return BUGSEG_OK;
+}
+
 // the weights' exponent for the fp32 mode's split-f16 products: 0 while the largest |w| lies in the
 // kernels' measured window [2^-2, 2^15) (mfma_common.h rng_exp_meas), else the exponent that brings it
 // to [2^14, 2^15), clamped as the kernels clamp
@@ -117,6 +152,8 @@ struct Packed {
 // struct. Everything but span and rev (issue) and the forward's bindings (bind) is final once the plan is built.
 struct ConvLaunch {    // launch_conv: the unfused convolutions, the initial block, the class layer
     int nr = 0, epi = 0;
+    bool cls = false;  // the class layer's route: the class kernel (cls_kernels.hip), not the generic EPI_CLASSES
+                       // convolution (Knobs::cls_conv, or a shape the class kernel does not take)
     ConvArgs a{};
 };
 struct BneckLaunch {   // launch_bneck: a fused bottleneck; cin > 0: a downsampling block (cin input channels)
@@ -151,15 +188,14 @@ struct Op {
     }
     bool up_on(int h) const { return up() && up()->a.h == h; }          // a fused upsampling block reading an h-row grid
     bool epi(int e) const { return conv() && conv()->epi == e; }
-    // the class layer as the class kernel runs it (cls_kernels.hip), not the generic EPI_CLASSES convolution
-    bool class_kernel() const { return epi(EPI_CLASSES) && cls_supported(conv()->a) && !std::getenv("BUGSEG_CLS_CONV"); }
+    // the class layer as the class kernel runs it (ConvLaunch::cls)
+    bool class_kernel() const { return conv() && conv()->cls; }
 };
 
-// What one forward binds into the plan's first and last launch (bind): the input and its kind, the output and
-// its kind, and whether the BGR normalisation runs in its affine form (BUGSEG_INIT_TABLE, read per forward).
+// What one forward binds into the plan's first and last launch (bind): the input and its kind, the output and its kind.
 struct Binding {
     const void *in = nullptr;
-    bool bgr = false, naff_on = false;
+    bool bgr = false;
     int out_kind = 0; void *out = nullptr;
 };
 
@@ -205,17 +241,7 @@ struct Plan {
     bool cls_ok = false, cls_on = false;
     Launch cls_fused;
     Binding bound;           // the last forward's binding (in == nullptr: none since the plan was built)
-    // Tile walk direction of the launches (bugseg_internal.h tile_walk), BUGSEG_TILE_ORDER, read per plan
-    // build as BUGSEG_NO_FUSE is: 0 every launch ascending, 1 alternating from ascending, 2 every launch
-    // descending (a control). Alternating, a launch starts on the frames the launch before it finished
-    // with, whose lines are the likeliest to still be in the last-level cache.
-    int tile_order = 0;
 };
-
-// default of BUGSEG_TILE_ORDER (the measurement that chose it)
-#ifndef BUGSEG_TILE_ORDER_DEFAULT
-#define BUGSEG_TILE_ORDER_DEFAULT 1
-#endif
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline int pow2_nr(int npad) {   // 16-row fragments, rounded up to 1, 2, 4 or 8
@@ -228,12 +254,13 @@ inline int pow2_nr(int npad) {   // 16-row fragments, rounded up to 1, 2, 4 or 8
 }  // namespace
 
 struct bugseg_ctx {
+    explicit bugseg_ctx(const Knobs &k) : knobs(k) {}
+    const Knobs knobs;                             // the BUGSEG_* knobs as bugseg_create read them (knobs.h)
     int device = 0;
     int prec = PREC_F32;
     float naff[6] = {};                            // exact affine form of the normalisation table (find_affine)
-    bool naff_on = false;
+    bool naff_on = false;                          // ... found (never searched for under Knobs::init_table)
     float norm_amax = 0.f;                         // max |table| (the BGR input's range, fp32 range scaling)
-    bool range_off = false;                        // BUGSEG_F32_RANGE=0 at load_weights: no fp32 range scaling (A/B)
     unsigned long long *spans = nullptr;           // bugseg_debug_set_spans: 512 u64 of launch-span slots per op, or null
     int spans_ops = 0;                             // ... for ops [0, spans_ops) only (the caller's buffer size)
     std::string err;
@@ -430,6 +457,7 @@ float f16_to_f32(uint16_t h) {
 
 struct Packer {
     int prec;
+    bool range;   // fp32 with Knobs::f32_range: the packed matrices carry a weight exponent (range_stats)
     std::vector<unsigned char> &buf;
     size_t push(const void *d, size_t n) {
         size_t off = round_up((int)buf.size(), 256);
@@ -488,9 +516,8 @@ int gentry(int dy, int dx, int coff) { return (dy & 0xff) | ((dx & 0xff) << 8) |
 
 // fp32 mode range scaling: the weight exponent of the packed matrix and its rows' bound terms
 // (bugseg_internal.h RangeArgs). w: the folded [Npad][Kpad] matrix; bias / slope per row.
-void range_stats(Packed &p, int prec, const std::vector<double> &w, const std::vector<float> &bias,
+void range_stats(Packed &p, bool scaled, const std::vector<double> &w, const std::vector<float> &bias,
                  const std::vector<float> &slope) {
-    const char *off = std::getenv("BUGSEG_F32_RANGE");          // (read at pack time: load_weights)
     p.sw = 0;
     p.rabs.assign(p.Npad, 0.f);
     p.rbias.assign(p.Npad, 0.f);
@@ -507,7 +534,7 @@ void range_stats(Packed &p, int prec, const std::vector<double> &w, const std::v
         p.rbias[r] = std::fabs(bias[r]);
         p.rslope[r] = std::max(1.f, std::fabs(slope[r]));
     }
-    if (prec == PREC_F32 && !(off && *off == '0')) p.sw = range_weight_exp(mx);
+    if (scaled) p.sw = range_weight_exp(mx);
 }
 // |act(W x + b)| <= n |x| + c over the rows [r0, r1) of a packed matrix (a 1e-4 margin for the f32
 // arithmetic the kernels evaluate the bound in)
@@ -557,7 +584,7 @@ Packed pack_conv(Packer &pk, const UnitDesc &u, int CinS, const std::vector<floa
         s1[c] = u.slope[c];
         if (slope2) s2[c] = (*slope2)[c];
     }
-    range_stats(p, pk.prec, w, bias, s1);
+    range_stats(p, pk.range, w, bias, s1);
     p.o_w = pk.push_w(w, p.sw);
     p.o_gtab = pk.push(gt.data(), gt.size() * 4);
     p.o_bias = pk.push_f(bias);
@@ -640,7 +667,7 @@ Packed pack_tconv(Packer &pk, const UnitDesc &u, int CinS, std::string &why, int
             bias[ph * p.coutP + c] = (float)shift[c];
             s1[ph * p.coutP + c] = u.slope[c];
         }
-    range_stats(p, pk.prec, w, bias, s1);
+    range_stats(p, pk.range, w, bias, s1);
     p.o_w = pk.push_w(w, p.sw);
     p.o_gtab = pk.push(gt.data(), gt.size() * 4);
     p.o_bias = pk.push_f(bias);
@@ -656,7 +683,7 @@ bool pack_all(bugseg_ctx *ctx, std::string &why) {
     ctx->packed.clear();
     ctx->block_convs.clear();
     ctx->host_w.clear();
-    Packer pk{ctx->prec, ctx->host_w};
+    Packer pk{ctx->prec, ctx->prec == PREC_F32 && ctx->knobs.f32_range, ctx->host_w};
     int cur_c = 3;
     std::vector<int> down_cin(ctx->blocks.size(), -1);
     for (size_t bi = 0; bi < ctx->blocks.size(); ++bi) {
@@ -751,7 +778,7 @@ bool pack_all(bugseg_ctx *ctx, std::string &why) {
             const bool same_bias = bias_acc(pow2_nr(round_up(um.cout, 16))) && bias_acc(pow2_nr(round_up(u1.cout, 16)));
             if (um.cout % 16 == 0 && u1.cout % 16 == 0 && um.eps == u1.eps && same_bias) {
                 add(pack_conv_pair(pk, um, u1, cstore(cin)));
-                if ((chunks & (chunks - 1)) == 0 && nr_pair <= 8 && bias_acc(nr_pair) && !std::getenv("BUGSEG_NO_PAIR")) {
+                if ((chunks & (chunks - 1)) == 0 && nr_pair <= 8 && bias_acc(nr_pair) && !ctx->knobs.no_pair) {
                     Packed t2 = pack_tconv(pk, ut, mc, why, cstore(um.cout));
                     if (!why.empty()) return false;
                     add(t2);
@@ -803,11 +830,6 @@ ConvArgs base_args(const bugseg_ctx *ctx, const Packed &p) {
     return a;
 }
 
-// BUGSEG_NO_FUSE=1: every block as its separate convolutions (read per plan build: plans are cached)
-bool no_fuse() {
-    const char *env = std::getenv("BUGSEG_NO_FUSE");
-    return env && *env && *env != '0';
-}
 // Every PReLU slope (both slope vectors) of the packed units is <= 1: max(v, s*v) is then exact
 bool slopes_le1(const bugseg_ctx *ctx, std::initializer_list<const Packed *> units) {
     for (const Packed *p : units) {
@@ -823,7 +845,7 @@ bool slopes_le1(const bugseg_ctx *ctx, std::initializer_list<const Packed *> uni
 // otherwise as its 3-4 conv launches. BUGSEG_NO_FUSE=1 forces the unfused plan (A/B testing;
 // results are bit-identical).
 bool fusable_regular(const bugseg_ctx *ctx, const BlockDesc &b, const std::vector<int> &ids, int &r, int &d) {
-    if (no_fuse()) return false;
+    if (ctx->knobs.no_fuse) return false;
     // the fused kernel computes PReLU as max(v, s*v), exact only for slopes <= 1
     for (const int id : ids)
         if (!slopes_le1(ctx, {&ctx->packed[id]})) return false;
@@ -852,7 +874,7 @@ bool fusable_regular(const bugseg_ctx *ctx, const BlockDesc &b, const std::vecto
 // (16 -> 64, 64 -> 128, internal cin / 4), 2x2 stride-2 projection, 3x3 middle conv, PReLU slopes
 // <= 1. -> the tile variant (C64: 16x16, C128: 20x16, untransposed) or -1.
 int fusable_down(const bugseg_ctx *ctx, const BlockDesc &b, const std::vector<int> &ids) {
-    if (no_fuse()) return -1;
+    if (ctx->knobs.no_fuse) return -1;
     const int cin = b.attrs[0], C = b.attrs[1];
     const int v = C == 64 && cin == 16 ? 0 : C == 128 && cin == 64 ? 1 : -1;
     if (v < 0 || b.units.size() != 3) return -1;
@@ -866,7 +888,7 @@ int fusable_down(const bugseg_ctx *ctx, const BlockDesc &b, const std::vector<in
         u2.cin != I || u2.cout != I)
         return -1;
     if (u3.kh != 1 || u3.kw != 1 || u3.cin != I || u3.cout != C) return -1;
-    if (bneck_slots_per_cu(ctx->prec, C, false, v, false, cin) <= 0) return -1;
+    if (bneck_slots_per_cu(ctx->knobs, ctx->prec, C, false, v, false, cin) <= 0) return -1;
     return v;
 }
 
@@ -881,10 +903,11 @@ int pick_bneck_variant(const bugseg_ctx *ctx, int C, bool asym, int d, int B, in
                        int &tr, int &rdv) {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) cus = 256;
-    const char *force = std::getenv("BUGSEG_BNECK_VARIANT");
-    if (const char *fc = std::getenv(("BUGSEG_BNECK_VARIANT_C" + std::to_string(C)).c_str())) force = fc;   // debug
-    if (asym)
-        if (const char *fa = std::getenv("BUGSEG_BNECK_VARIANT_ASYM")) force = fa;   // debug
+    const Knobs &k = ctx->knobs;
+    int force = k.bneck_variant;                                           // -1: none
+    const int fc = C == 128 ? k.bneck_variant_c128 : C == 64 ? k.bneck_variant_c64 : C == 16 ? k.bneck_variant_c16 : -1;
+    if (fc >= 0) force = fc;                                               // debug
+    if (asym && k.bneck_variant_asym >= 0) force = k.bneck_variant_asym;   // debug
     const int R = asym ? 2 : 1;
     const int hs = (H + d - 1) / d, ws = (W + d - 1) / d;    // phase sub-image (largest phase)
     int best = -1;
@@ -894,9 +917,9 @@ int pick_bneck_variant(const bugseg_ctx *ctx, int C, bool asym, int d, int B, in
         bneck_shape(C, v, th, tw, nw, &rd);
         if (bneck_lds_bytes(ctx->prec, C, asym, v) > 160 * 1024) continue;
         if (rd && (asym || W > tw || d < 2)) continue;        // row-dilated tiles span the width
-        const bool forced = force && *force && std::atoi(force) == v;
+        const bool forced = force == v;
         for (int t = 0; t < (asym || rd ? 1 : 2); ++t) {
-            const int spc = bneck_slots_per_cu(ctx->prec, C, asym, v, t != 0);
+            const int spc = bneck_slots_per_cu(k, ctx->prec, C, asym, v, t != 0);
             if (spc <= 0) continue;                           // this orientation is not built
             const int slots = spc * cus;
             const int ty = rd ? (hs + th - 1) / th : t ? (hs + tw - 1) / tw : (hs + th - 1) / th;
@@ -984,7 +1007,7 @@ struct Walker {
     // fp32 range scaling of a launch: its input's measured range; measure: its output's range is measured too
     void range_io(RangeArgs &rg, const void *in, const void *out, bool measure = true) {
         rg.amax_in = words_of(in);
-        rg.off = ctx->range_off;
+        rg.off = !ctx->knobs.f32_range;
         if (!measure) return;
         rg.amax_out = take_words();
         wrote(out, rg.amax_out);
@@ -1033,6 +1056,7 @@ struct Walker {
         if (fill) {
             ConvArgs &a = args(conv(P(0), EPI_INIT, curp, cur, so, dst, so));
             a.cconv = b.attrs[1]; a.cpool = b.attrs[0]; a.pool_k = b.attrs[2];
+            a.pool_scan = ctx->knobs.init_pool_scan;
             a.CinS = 8;
         }
         cur = so;
@@ -1150,7 +1174,7 @@ struct Walker {
         szX = std::max(szX, tbytes(so));
         const int cin_b = b.attrs[0], cout_b = b.attrs[1], it_b = P(1).cout;
         const int idxCS = cstore(ctx->blocks[(size_t)ref].attrs[0]);
-        const bool fuse_up = ids->size() >= 5 && up_supported(cin_b, it_b, cout_b) && cur.C == cin_b && so.C == cout_b && !no_fuse();
+        const bool fuse_up = ids->size() >= 5 && up_supported(cin_b, it_b, cout_b) && cur.C == cin_b && so.C == cout_b && !ctx->knobs.no_fuse;
         const bool pair = ids->size() == 6;
         // unfused, paired: the main and extension 1x1 outputs share one tensor (main channels first)
         Shape sp{cur.H, cur.W, pair ? sm.C + s1.C : sm.C};
@@ -1208,7 +1232,11 @@ struct Walker {
     bool fullconv(std::string &why) {
         Shape so{cur.H * 2, cur.W * 2, P(0).cout};
         if (so.H != H || so.W != W) { why = "network does not return to the input resolution"; return false; }
-        if (fill) args(conv(P(0), EPI_CLASSES, curp, cur, cur, nullptr, so)).ncls = ctx->ncls;
+        if (fill) {
+            ConvLaunch &l = std::get<ConvLaunch>(conv(P(0), EPI_CLASSES, curp, cur, cur, nullptr, so).l);
+            l.a.ncls = ctx->ncls;
+            l.cls = cls_supported(l.a) && !ctx->knobs.cls_conv;   // the route, decided here once
+        }
         cur = so;
         return true;
     }
@@ -1331,14 +1359,10 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
     pl.ops = std::move(w.ops);
     int issued = 0;
     for (Op &op : pl.ops) { op.pos = issued; issued += op.launches; }
-    pl.tile_order = BUGSEG_TILE_ORDER_DEFAULT;
-    if (const char *to = std::getenv("BUGSEG_TILE_ORDER"))
-        if (*to >= '0' && *to <= '2' && !to[1]) pl.tile_order = *to - '0';
     pl.cls_ok = false;
     pl.cls_on = false;
     pl.bound = Binding();
-    const char *fe = std::getenv("BUGSEG_CLS_FUSE");
-    if (fe && *fe == '1' && pl.ops.size() >= 2 && pl.ops.back().class_kernel()) {
+    if (ctx->knobs.cls_fuse && pl.ops.size() >= 2 && pl.ops.back().class_kernel()) {
         const ConvArgs &l = pl.ops.back().conv()->a;
         const Op &q = pl.ops[pl.ops.size() - 2];
         pl.cls_ok = q.regular(16, l.Hin) && q.bneck()->a.out == l.in && l.B == q.bneck()->a.B && l.Win == q.bneck()->a.W &&
@@ -1479,7 +1503,7 @@ const WinPlan *window_plan(bugseg_ctx *ctx, int row0, int row1) {
     // else (a thin window: none efficient enough) the full frame's. s3: among the untransposed forms with a
     // windowed kernel. -> image rows per tile row (0: no form).
     auto form = [&](const BneckLaunch &q, int rows, bool s3, WinOp &r) {
-        auto built = [&](int v) { return !s3 || bneck_slots_per_cu(ctx->prec, q.C, q.asym, v, false, 0, true) > 0; };
+        auto built = [&](int v) { return !s3 || bneck_slots_per_cu(ctx->knobs, ctx->prec, q.C, q.asym, v, false, 0, true) > 0; };
         int ty = 0, tx = 0, tr = 0, rd = 0;
         int v = pick_bneck_variant(ctx, q.C, q.asym, 1, pl.B, rows, q.a.W, ty, tx, tr, rd);
         if (v < 0 || rd || (s3 && (tr || !built(v)))) { v = q.var; tr = s3 ? 0 : q.a.tr; }
@@ -1503,8 +1527,7 @@ const WinPlan *window_plan(bugseg_ctx *ctx, int row0, int row1) {
     }
     // on into stage 3: the ops before the 128 -> 64 block, while they are fused C = 128 bottlenecks on its input
     // grid whose form has a windowed kernel (fp32). BUGSEG_ROW_WINDOW_S3=0: the decoder's windows only (A/B)
-    const char *s3e = std::getenv("BUGSEG_ROW_WINDOW_S3");
-    if (!(s3e && *s3e == '0')) {
+    if (ctx->knobs.row_window_s3) {
         S3Desc blk[S3_OPS];
         int nb = 0, th[S3_OPS], tw, nw;
         for (; nb < S3_OPS; ++nb) {
@@ -1514,7 +1537,7 @@ const WinPlan *window_plan(bugseg_ctx *ctx, int row0, int row1) {
             bneck_shape(128, q->var, th[nb], tw, nw, &d.rd);
             d.asym = q->asym; d.d = q->a.dt;
             d.rows_full = d.rd ? q->a.phases * q->a.tiles_y * th[nb] : q->a.tr ? 0 : q->a.tiles_y * th[nb];
-            if (d.rd && bneck_slots_per_cu(ctx->prec, 128, false, q->var, false, 0, true) <= 0) d.rows_full = 0;
+            if (d.rd && bneck_slots_per_cu(ctx->knobs, ctx->prec, 128, false, q->var, false, 0, true) <= 0) d.rows_full = 0;
         }
         int w3[S3_OPS][2];
         w.ns3 = stage3_windows(H / 8, w.op[0].y0, w.op[0].y1, nb, blk,
@@ -1570,7 +1593,10 @@ int bugseg_create(int device, int precision, bugseg_ctx **out) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n)
         return fail(nullptr, BUGSEG_EINVAL, "no such HIP device: " + std::to_string(device));
-    bugseg_ctx *c = new (std::nothrow) bugseg_ctx();
+    Knobs knobs;
+    std::string bad;
+    if (!read_knobs(knobs, bad)) return fail(nullptr, BUGSEG_EINVAL, bad);
+    bugseg_ctx *c = new (std::nothrow) bugseg_ctx(knobs);
     if (!c) return fail(nullptr, BUGSEG_ENOMEM, "out of host memory");
     c->device = device;
     c->prec = precision == BUGSEG_BF16 ? PREC_BF16 : precision == BUGSEG_F16 ? PREC_F16 : PREC_F32;
@@ -1602,7 +1628,7 @@ int bugseg_create(int device, int precision, bugseg_ctx **out) {
         // bit for bit (searched on the device, with its own conversions: init_kernels.hip
         // naff_search_kernel) — no LDS lookups, whose data-dependent addresses conflict; fp32 keeps
         // the table. BUGSEG_INIT_TABLE=1 forces the table (A/B)
-        if (e == hipSuccess && c->prec != PREC_F32) {
+        if (e == hipSuccess && c->prec != PREC_F32 && !c->knobs.init_table) {
             float base[6];
             for (int ch = 0; ch < 3; ++ch) {
                 base[ch] = (float)(1.0 / (256.0 * stdv[ch]));
@@ -1672,10 +1698,6 @@ int bugseg_load_weights(bugseg_ctx *ctx, const void *blob, size_t bytes) {
     ctx->blocks = std::move(blocks);
     ctx->ncls = ncls;
     ctx->loaded = false;
-    {
-        const char *off = std::getenv("BUGSEG_F32_RANGE");
-        ctx->range_off = off && *off == '0';
-    }
     if (!pack_all(ctx, why)) return fail(ctx, BUGSEG_EFORMAT, "weight blob: " + why);
     (void)hipDeviceSynchronize();
     if (ctx->dev_w) {
@@ -1787,18 +1809,19 @@ int bugseg_nchw_to_input(bugseg_ctx *ctx, const void *x, int is_f64, int B, int 
     return BUGSEG_OK;
 }
 
-static hipError_t dispatch(int prec, const ConvLaunch &l, hipStream_t s) { return launch_conv(prec, l.nr, l.epi, l.a, s); }
-static hipError_t dispatch(int prec, const UpLaunch &l, hipStream_t s) { return launch_up(prec, l.cin, l.it, l.cout, l.a, s); }
-static hipError_t dispatch(int prec, const BneckLaunch &l, hipStream_t s) {
-    return l.cls ? launch_bneck_cls(prec, l.a, s) : launch_bneck(prec, l.C, l.asym, l.var, l.a, s, l.cin, l.win);
+static hipError_t dispatch(const bugseg_ctx *c, const ConvLaunch &l, hipStream_t s) { return launch_conv(c->prec, l.nr, l.epi, l.a, s, l.cls); }
+static hipError_t dispatch(const bugseg_ctx *c, const UpLaunch &l, hipStream_t s) { return launch_up(c->prec, l.cin, l.it, l.cout, l.a, s); }
+static hipError_t dispatch(const bugseg_ctx *c, const BneckLaunch &l, hipStream_t s) {
+    return l.cls ? launch_bneck_cls(c->knobs, c->prec, l.a, s)
+                 : launch_bneck(c->knobs, c->prec, l.C, l.asym, l.var, l.a, s, l.cin, l.win);
 }
 // One launch record to its kernel, with its launch-span slots (or null) and its tile walk direction: the one
 // place that sets them.
-static hipError_t issue(int prec, Launch &l, int rev, unsigned long long *span, hipStream_t s) {
+static hipError_t issue(const bugseg_ctx *ctx, Launch &l, int rev, unsigned long long *span, hipStream_t s) {
     return std::visit([&](auto &r) {
         r.a.span = span;
         r.a.rev = rev;
-        return dispatch(prec, r, s);
+        return dispatch(ctx, r, s);
     }, l);
 }
 
@@ -1810,7 +1833,7 @@ static void bind(const bugseg_ctx *ctx, const Binding &b, bool first, bool last,
         c->epi = b.bgr ? EPI_INIT_BGR : EPI_INIT;
         c->a.in = b.in;
         c->a.nlut = b.bgr ? (const double *)((const unsigned char *)ctx->dev_luts + 32) : nullptr;
-        c->a.naff_on = b.naff_on;
+        c->a.naff_on = b.bgr && ctx->naff_on;   // (the exact affine form of the normalisation, where the context has one)
         std::memcpy(c->a.naff, ctx->naff, sizeof(ctx->naff));
         // fp32 range scaling: the BGR input's range is the normalisation table's (static); an engine input
         // the caller supplied is measured (block 0 of the range words)
@@ -1834,7 +1857,7 @@ static void bind(const bugseg_ctx *ctx, const Binding &b, bool first, bool last,
 // One plan op for the last forward's binding (Plan::bound). launch_op only picks the op's record — its windowed
 // launch when wp (a row-windowed forward, window_plan) has one, the class-fused launch when the forward took it
 // (the last op then issues nothing; nothing follows it), else the full-frame launch — binds a copy and issues
-// it. The walk direction (Plan::tile_order) follows the number of launches the plan issues before the op
+// it. The walk direction (Knobs::tile_order) follows the number of launches the plan issues before the op
 // (Op::pos, counted at plan build from Op::launches), so a single op (bugseg_plan_launch_op) and an op range
 // walk as they do in the whole forward; the span slots are those bugseg_debug_set_spans armed.
 static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const WinPlan *wp = nullptr) {
@@ -1846,9 +1869,10 @@ static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const W
     if (!pick) pick = fused ? &pl.cls_fused : &pl.ops[(size_t)i].l;
     Launch l = *pick;
     bind(ctx, pl.bound, i == 0, fused || i + 1 == n, l);
-    const int rev = pl.tile_order == 2 ? 1 : pl.tile_order == 1 ? (pl.ops[(size_t)i].pos & 1) : 0;
+    const int order = ctx->knobs.tile_order;   // 0 ascending, 1 alternating from ascending, 2 descending
+    const int rev = order == 2 ? 1 : order == 1 ? (pl.ops[(size_t)i].pos & 1) : 0;
     unsigned long long *sp = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;   // (mfma_common.h: 64 slots x 64 B)
-    return issue(ctx->prec, l, rev, sp, s);
+    return issue(ctx, l, rev, sp, s);
 }
 
 static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H, int W, int out_kind, void *out,
@@ -1861,7 +1885,7 @@ static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H,
     if (!build_plan(ctx, B, H, W, why, stream)) return fail(ctx, BUGSEG_EINVAL, why);
     Plan &pl = ctx->plan;
     if (stream_capturing(stream)) pl.pinned = true;
-    pl.bound = Binding{in, bgr, bgr && ctx->naff_on && !std::getenv("BUGSEG_INIT_TABLE"), out_kind, out};
+    pl.bound = Binding{in, bgr, out_kind, out};
     const int nops = (int)pl.ops.size();
     if (last_op < 0 || last_op > nops) last_op = nops;
     if (first_op < 0 || first_op > last_op) return fail(ctx, BUGSEG_EINVAL, "bad op range");
@@ -2149,8 +2173,7 @@ int bev_table(bugseg_ctx *ctx, BevArgs &a, bool cap, bugseg_ctx::BevTab *&hit, b
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e == hipSuccess) {
                 // (BUGSEG_BEV_NEAR_FIRST=1: the earlier order, nearest bands first; A/B)
-                const char *nf = std::getenv("BUGSEG_BEV_NEAR_FIRST");
-                const bool near_first = nf && std::atoi(nf) != 0;
+                const bool near_first = ctx->knobs.bev_near_first;
                 for (int i = 0; i < nb; ++i) {
                     const int b = near_first ? nb - 1 - i : i;
                     for (int k = 0; k < std::max(1, std::min(BEV_BAND, rec[(size_t)b * BEV_BOXREC].x)); ++k) items.push_back(make_int2(b, k));
@@ -2215,7 +2238,7 @@ int bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_par
         a.cells = (uint8_t *)ws;
         a.rmin = (int32_t *)((unsigned char *)ws + ls_cells_bytes(B, p));
     }
-    hipError_t e = launch_bev(a, (hipStream_t)stream);
+    hipError_t e = launch_bev(ctx->knobs, a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("bev launch: ") + hipGetErrorString(e));
     return BUGSEG_OK;
 }
@@ -2261,7 +2284,7 @@ int bugseg_bev_occgrid_ws(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugs
 // ---- test hooks (host only: no device, no HIP call) — tests/asan drives them under ASan + UBSan
 int bugseg_debug_parse_pack(const void *blob, size_t bytes, int precision, int *ncls) {
     if (!blob) return fail(nullptr, BUGSEG_EINVAL, "NULL blob");
-    bugseg_ctx c;                                     // host state only; nothing to free on the device
+    bugseg_ctx c{Knobs()};                            // host state only (default knobs); nothing to free on the device
     c.prec = precision == BUGSEG_BF16 ? PREC_BF16 : precision == BUGSEG_F16 ? PREC_F16 : PREC_F32;
     std::string why;
     if (!parse_blob(blob, bytes, c.blocks, c.ncls, why)) return fail(nullptr, BUGSEG_EFORMAT, "weight blob: " + why);
@@ -2388,10 +2411,16 @@ int bugseg_debug_ctx_info(const bugseg_ctx *ctx, int what, int arg) {
     if (!ctx) return -1;
     switch (what) {
     case 0: return ctx->naff_on ? 1 : 0;
-    case 1: return ctx->range_off ? 1 : 0;
+    case 1: return ctx->knobs.f32_range ? 0 : 1;
     case 2: return arg >= 0 && arg < (int)ctx->packed.size() ? ctx->packed[(size_t)arg].sw : -1000;
     default: return -1;
     }
+}
+
+int bugseg_debug_knobs(const bugseg_ctx *ctx, char *buf, int len) {
+    std::string err;
+    const int rc = dump_knobs(ctx ? &ctx->knobs : nullptr, buf, len, err);
+    return rc == BUGSEG_OK ? rc : fail(const_cast<bugseg_ctx *>(ctx), rc, err);
 }
 
 int bugseg_debug_polar_tables(int w, int h, int variant, int32_t *fmap, size_t fmap_n, int32_t *imap, size_t imap_n,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knobs.h"
+
 namespace bugseg {
 
 struct DlPrepArgs {
@@ -118,8 +120,8 @@ struct DlMaxPoolArgs {
 
 hipError_t dl_launch_prep(int prec, const DlPrepArgs &a, hipStream_t s);
 hipError_t dl_launch_maxpool(int prec, const DlMaxPoolArgs &a, hipStream_t s);
-hipError_t dl_launch_conv_group(int prec, const DlConvGroup &g, hipStream_t s);   // hipErrorNotSupported: launch singly
-hipError_t dl_launch_conv(int prec, bool out_f32, const DlConvArgs &a, hipStream_t s);
+hipError_t dl_launch_conv_group(const Knobs &k, int prec, const DlConvGroup &g, hipStream_t s);   // hipErrorNotSupported: launch singly
+hipError_t dl_launch_conv(const Knobs &k, int prec, bool out_f32, const DlConvArgs &a, hipStream_t s);
 hipError_t dl_launch_dw(int prec, const DlDwArgs &a, hipStream_t s);
 hipError_t dl_launch_pool(int prec, const DlPoolArgs &a, hipStream_t s);
 hipError_t dl_launch_argmax(const DlArgmaxArgs &a, hipStream_t s);

@@ -345,7 +345,7 @@ constexpr int GM_TM = 256, GM_TN = 64, GM_KT = 64, GM_RS = GM_KT + 16;   // LDS 
 
 // TM = pixels per workgroup tile: 256 (4 fragments per wave) or 128 (2 fragments per wave: a smaller
 // LDS and register footprint, so more workgroups per CU keep more loads and stores in flight)
-template <bool OUTF32, bool RPF, bool PD2 = false, int TM = GM_TM>
+template <bool OUTF32, bool RPF, int TM = GM_TM>
 __global__ void __launch_bounds__(256, 2) dl_gemm_kernel(const DlConvArgs a) {
     constexpr int FJ = TM / 64, WPX = TM / 4, NBC = TM / 32;   // fragments / pixels per wave, B chunks per thread
     constexpr int SMB = (GM_TN + TM) * GM_RS * 2, STB = 4 * 32 * DL_STG_RS * 4;   // operand / staging bytes
@@ -373,14 +373,13 @@ __global__ void __launch_bounds__(256, 2) dl_gemm_kernel(const DlConvArgs a) {
         wk[i] = (q & 7) * 8;
         woff[i] = (uint32_t)((n0 + row) * K + wk[i]) * 2u;
     }
-    uint4 pb[NBC], pw[2], qb[NBC], qw[2];   // qb / qw: PD2's second stage in flight
-    auto fetch_to = [&](int k0, uint4 (&xb)[NBC], uint4 (&xw)[2]) {
+    uint4 pb[NBC], pw[2];
+    auto fetch = [&](int k0) {
 #pragma unroll
-        for (int i = 0; i < NBC; ++i) xb[i] = bld16(rin, boff[i] != OOB && k0 + bk[i] < a.CS ? boff[i] + k0 * 2 : OOB);
+        for (int i = 0; i < NBC; ++i) pb[i] = bld16(rin, boff[i] != OOB && k0 + bk[i] < a.CS ? boff[i] + k0 * 2 : OOB);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) xw[i] = bld16(rw, k0 + wk[i] < K ? woff[i] + k0 * 2 : OOB);
+        for (int i = 0; i < 2; ++i) pw[i] = bld16(rw, k0 + wk[i] < K ? woff[i] + k0 * 2 : OOB);
     };
-    auto fetch = [&](int k0) { fetch_to(k0, pb, pw); };
     f32x4 acc[FJ][4];
 #pragma unroll
     for (int j = 0; j < FJ; ++j)
@@ -430,26 +429,12 @@ __global__ void __launch_bounds__(256, 2) dl_gemm_kernel(const DlConvArgs a) {
                 for (int r = 0; r < 4; ++r) mma(acc[j][r], wa[r], bx[j]);
         }
     };
+    // (a second stage in flight in registers, the loop unrolled by two: tried, slower, removed; dl_launch_conv)
     fetch(0);
-    if constexpr (PD2) {
-        // two stages in flight in registers (K > 64: a stage's 32 MFMAs per wave are too short to
-        // cover one fetch's latency); the loop unrolled by two so each register set's role is static
-        if (nst > 1) fetch_to(GM_KT, qb, qw);
-        for (int st = 0; st < nst; st += 2) {
-            put(pb, pw);
-            if (st + 2 < nst) fetch_to((st + 2) * GM_KT, pb, pw);
-            compute(st);
-            if (st + 1 >= nst) break;
-            put(qb, qw);
-            if (st + 3 < nst) fetch_to((st + 3) * GM_KT, qb, qw);
-            compute(st + 1);
-        }
-    } else {
-        for (int st = 0; st < nst; ++st) {
-            put(pb, pw);
-            if (st + 1 < nst) fetch((st + 1) * GM_KT);
-            compute(st);
-        }
+    for (int st = 0; st < nst; ++st) {
+        put(pb, pw);
+        if (st + 1 < nst) fetch((st + 1) * GM_KT);
+        compute(st);
     }
     // epilogue (dl_conv_kernel's, 32 pixels at a time through the wave's share of the staging LDS)
     __syncthreads();
@@ -1274,16 +1259,6 @@ hipError_t dl_launch_prep(int prec, const DlPrepArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// k-step prefetch depth of the bf16 conv (template PD): BUGSEG_DL_PD=1|2|3 forces one for A/B runs
-static int conv_pd(const DlConvArgs &a, int nb) {
-    static const int env = [] { const char *e = std::getenv("BUGSEG_DL_PD"); return e ? std::atoi(e) : 0; }();
-    if (env >= 1 && env <= 3) return env;
-    (void)a; (void)nb;
-    // measured (16 frames, 513x513, per-op HIP events): two steps ahead is 1.3% faster over the 38
-    // conv launches than one (1609 vs 1631 us); three is between (1620 us); no op gains more than 3%
-    return 2;
-}
-
 template <int NB, int PD>
 static void conv_bf16(bool out_f32, const DlConvArgs &a, const dim3 g, hipStream_t s) {
     if (out_f32) hipLaunchKernelGGL((dl_conv_kernel<__bf16, true, false, NB, PD>), g, dim3(256), 0, s, a);
@@ -1294,10 +1269,11 @@ template <int NB>
 static void conv_nb(int prec, bool out_f32, bool dwf, const DlConvArgs &a, hipStream_t s) {
     const dim3 g(((a.M + NB * 64 - 1) / (NB * 64)) * (a.NP / 64));
     if (prec == PREC_BF16 && !dwf) {   // NB = 8: bf16 only, no depthwise fusion (register budget)
-        const int pd = a.tap_packed ? 1 : conv_pd(a, NB);
-        if (pd == 3) conv_bf16<NB, 3>(out_f32, a, g, s);
-        else if (pd == 2) conv_bf16<NB, 2>(out_f32, a, g, s);
-        else conv_bf16<NB, 1>(out_f32, a, g, s);
+        // k-step prefetch depth (template PD): 1 for the tap-packed convs, else 2. Measured (16 frames, 513x513,
+        // per-op HIP events): two steps ahead is 1.3% faster over the 38 conv launches than one (1609 vs 1631
+        // us), no op gains more than 3%; three (tried, slower: 1620 us) went with its knob BUGSEG_DL_PD
+        if (a.tap_packed) conv_bf16<NB, 1>(out_f32, a, g, s);
+        else conv_bf16<NB, 2>(out_f32, a, g, s);
     } else if constexpr (NB == 8) {
         return;
     } else if (prec == PREC_BF16) {
@@ -1310,10 +1286,8 @@ static void conv_nb(int prec, bool out_f32, bool dwf, const DlConvArgs &a, hipSt
 }
 
 // the LDS-staged GEMM form applies to plain 1x1 convolutions (bf16; BUGSEG_DL_GEMM=0 turns it off)
-static bool gemm_ok(int prec, const DlConvArgs &a) {
-    const char *e = std::getenv("BUGSEG_DL_GEMM");
-    if (e && *e == '0') return false;
-    return prec == PREC_BF16 && !a.dw_w && !a.tap_packed && a.kh == 1 && a.kw == 1 && a.stride == 1 && a.pad_t == 0 &&
+static bool gemm_ok(const Knobs &k, int prec, const DlConvArgs &a) {
+    return k.dl_gemm && prec == PREC_BF16 && !a.dw_w && !a.tap_packed && a.kh == 1 && a.kw == 1 && a.stride == 1 && a.pad_t == 0 &&
            a.pad_l == 0 && a.Hin == a.Hout && a.Win == a.Wout && a.cinP % 32 == 0 && a.NP % 64 == 0 &&
            (size_t)a.NP * a.cinP * 2 < ((size_t)1 << 31);
 }
@@ -1323,9 +1297,8 @@ static bool gemm_ok(int prec, const DlConvArgs &a) {
 // 2.60 ms per 16-frame forward (462 -> 558 TFLOP/s), the ASPP 1x1s 3% faster; MobileNetV2's
 // 576 / 960 -> 96..320 projections (HBM-bound, NP % 128 = 64) 1-8% slower, so they stay on
 // dl_gemm_kernel
-static bool gemm128_ok(const DlConvArgs &a) {
-    const char *e = std::getenv("BUGSEG_DL_G128");
-    return !(e && *e == '0') && a.cinP >= 256 && a.NP >= 256 && a.NP % 128 == 0 && a.CS % 8 == 0;
+static bool gemm128_ok(const Knobs &k, const DlConvArgs &a) {
+    return k.dl_g128 && a.cinP >= 256 && a.NP >= 256 && a.NP % 128 == 0 && a.CS % 8 == 0;
 }
 
 // implicit-GEMM k x k conv on the glds tile: bf16, dense (not tap-packed, no fused depthwise), every
@@ -1335,10 +1308,8 @@ static bool gemm128_ok(const DlConvArgs &a) {
 // per-op HIP events): the implicit GEMM 1,723 -> 2,827 frames/s (3x3s 3,826 -> 1,715 us, ASPP atrous
 // 1,859 -> 847, root 825 -> 518); the 256 x 64 tile for the 64-channel root / block-1 convs then
 // 2,827 -> 2,939 (root 518 -> 390 us, 3x3s 1,715 -> 1,633)
-static bool igemm_ok(int prec, const DlConvArgs &a) {
-    const char *e = std::getenv("BUGSEG_DL_IG"), *e64 = std::getenv("BUGSEG_DL_IG64");
-    const bool ig64 = !(e64 && *e64 == '0');
-    return !(e && *e == '0') && (ig64 || a.NP % 128 == 0) && prec == PREC_BF16 && !a.dw_w && !a.tap_packed &&
+static bool igemm_ok(const Knobs &k, int prec, const DlConvArgs &a) {
+    return k.dl_ig && (k.dl_ig64 || a.NP % 128 == 0) && prec == PREC_BF16 && !a.dw_w && !a.tap_packed &&
            a.taps > 1 && a.zero && a.cinP == a.CS && a.cinP % 64 == 0 && a.NP % 64 == 0 &&
            (size_t)a.NP * a.taps * a.cinP * 2 < ((size_t)1 << 31);
 }
@@ -1355,11 +1326,23 @@ static void launch_g2(bool out_f32, const DlConvArgs &a, hipStream_t s) {
     }
 }
 
-hipError_t dl_launch_conv_group(int prec, const DlConvGroup &g, hipStream_t s) {
+template <int TM>   // dl_gemm_kernel on TM-pixel tiles
+static void launch_gm(bool out_f32, const DlConvArgs &a, hipStream_t s) {
+    const dim3 g(((a.M + TM - 1) / TM) * (a.NP / GM_TN));
+    if (a.res) {
+        if (out_f32) hipLaunchKernelGGL((dl_gemm_kernel<true, true, TM>), g, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((dl_gemm_kernel<false, true, TM>), g, dim3(256), 0, s, a);
+    } else {
+        if (out_f32) hipLaunchKernelGGL((dl_gemm_kernel<true, false, TM>), g, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((dl_gemm_kernel<false, false, TM>), g, dim3(256), 0, s, a);
+    }
+}
+
+hipError_t dl_launch_conv_group(const Knobs &k, int prec, const DlConvGroup &g, hipStream_t s) {
     if (g.n < 2 || g.n > DL_GROUP_MAX) return hipErrorNotSupported;
     for (int i = 0; i < g.n; ++i) {
         const DlConvArgs &a = g.a[i];
-        if (!igemm_ok(prec, a) || a.res || a.NP % 128 || a.M != g.a[0].M || a.NP != g.a[0].NP) return hipErrorNotSupported;
+        if (!igemm_ok(k, prec, a) || a.res || a.NP % 128 || a.M != g.a[0].M || a.NP != g.a[0].NP) return hipErrorNotSupported;
     }
     DlConvGroup h = g;
     h.tiles = ((g.a[0].M + G2_T - 1) / G2_T) * (g.a[0].NP / G2_T);
@@ -1367,58 +1350,26 @@ hipError_t dl_launch_conv_group(int prec, const DlConvGroup &g, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t dl_launch_conv(int prec, bool out_f32, const DlConvArgs &a, hipStream_t s) {
+hipError_t dl_launch_conv(const Knobs &k, int prec, bool out_f32, const DlConvArgs &a, hipStream_t s) {
     const bool dwf = a.dw_w != nullptr;
-    if (igemm_ok(prec, a)) {
+    if (igemm_ok(k, prec, a)) {
         if (a.NP % 128 == 0) launch_g2<true, 128>(out_f32, a, s);
         else launch_g2<true, 256>(out_f32, a, s);
         return hipGetLastError();
     }
-    if (gemm_ok(prec, a) && gemm128_ok(a)) {
+    if (gemm_ok(k, prec, a) && gemm128_ok(k, a)) {
         launch_g2<false, 128>(out_f32, a, s);
         return hipGetLastError();
     }
-    if (const char *e = std::getenv("BUGSEG_DL_G2ALL"); e && *e != '0' && gemm_ok(prec, a) && a.CS % 8 == 0) {
-        // (A/B knob) every other 1x1 on the glds tile: 1 = 128 x 128 where the outputs come in 128s,
-        // else 256 x 64; 2 = 256 x 64 always
-        if ((*e == '1' && a.NP % 128 == 0) || *e == '3') launch_g2<false, 128>(out_f32, a, s);
-        else launch_g2<false, 256>(out_f32, a, s);
-        return hipGetLastError();
-    }
-    if (gemm_ok(prec, a)) {
-        const dim3 g(((a.M + GM_TM - 1) / GM_TM) * (a.NP / GM_TN));
-        const char *pe = std::getenv("BUGSEG_DL_GPD2"), *te = std::getenv("BUGSEG_DL_GTM");
-        const bool pd2 = pe && *pe == '1' && a.cinP > GM_KT;
+    // (every other 1x1 on the glds tile, the knob BUGSEG_DL_G2ALL: tried, slower, removed)
+    if (gemm_ok(k, prec, a)) {
         // 128-pixel tiles below 2^19 output pixels (BUGSEG_DL_GTM=0 / 1 forces 256 / 128). Measured
         // (per-op HIP events): MobileNetV2 B = 64 9,240 -> 9,430 frames/s (the 65x65 projections
         // 110 -> 97 us, 212 -> 184 us; the 257^2 / 129^2 layers are slower with 128, hence the bound);
-        // ResNet-101 B = 16 and Xception-65 B = 32 within +-0.3%. PD2 (BUGSEG_DL_GPD2=1: a second stage
-        // in flight in registers) measured slower: 9,220 -> 8,935 (196-234 VGPRs: 2 workgroups per CU)
-        const bool tm128 = te ? *te == '1' : a.M <= (1 << 19);
-        if (tm128 && !pd2) {
-            const dim3 g1(((a.M + 127) / 128) * (a.NP / GM_TN));
-            if (a.res) {
-                if (out_f32) hipLaunchKernelGGL((dl_gemm_kernel<true, true, false, 128>), g1, dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((dl_gemm_kernel<false, true, false, 128>), g1, dim3(256), 0, s, a);
-            } else {
-                if (out_f32) hipLaunchKernelGGL((dl_gemm_kernel<true, false, false, 128>), g1, dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((dl_gemm_kernel<false, false, false, 128>), g1, dim3(256), 0, s, a);
-            }
-        } else if (pd2) {
-            if (a.res) {
-                if (out_f32) hipLaunchKernelGGL((dl_gemm_kernel<true, true, true>), g, dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((dl_gemm_kernel<false, true, true>), g, dim3(256), 0, s, a);
-            } else {
-                if (out_f32) hipLaunchKernelGGL((dl_gemm_kernel<true, false, true>), g, dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((dl_gemm_kernel<false, false, true>), g, dim3(256), 0, s, a);
-            }
-        } else if (a.res) {
-            if (out_f32) hipLaunchKernelGGL((dl_gemm_kernel<true, true>), g, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((dl_gemm_kernel<false, true>), g, dim3(256), 0, s, a);
-        } else {
-            if (out_f32) hipLaunchKernelGGL((dl_gemm_kernel<true, false>), g, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((dl_gemm_kernel<false, false>), g, dim3(256), 0, s, a);
-        }
+        // ResNet-101 B = 16 and Xception-65 B = 32 within +-0.3%. A second stage in flight in registers (the
+        // knob BUGSEG_DL_GPD2): tried, slower (9,220 -> 8,935; 196-234 VGPRs: 2 workgroups per CU), removed
+        if (k.dl_gtm >= 0 ? k.dl_gtm == 1 : a.M <= (1 << 19)) launch_gm<128>(out_f32, a, s);
+        else launch_gm<GM_TM>(out_f32, a, s);
         return hipGetLastError();
     }
     if (a.nb == 8 && prec == PREC_BF16 && !dwf) conv_nb<8>(prec, out_f32, false, a, s);
@@ -1427,42 +1378,34 @@ hipError_t dl_launch_conv(int prec, bool out_f32, const DlConvArgs &a, hipStream
     return hipGetLastError();
 }
 
-template <typename T, int R, int ACT, bool IRELU>
-static void launch_dw_t(const DlDwArgs &a, const dim3 g, hipStream_t s) {
-    if (a.stride == 1) hipLaunchKernelGGL((dl_dw_kernel<T, true, R, ACT, IRELU>), g, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((dl_dw_kernel<T, false, R, ACT, IRELU>), g, dim3(256), 0, s, a);
-}
-
 // (act, in_relu) forms: MobileNetV2 (ReLU6, -), Xception pre-activation (none, ReLU in), Xception
 // activated-inside / ASPP / decoder (ReLU, -)
-template <typename T, int R>
+template <typename T, bool S1, int R>
 static hipError_t launch_dw_a(const DlDwArgs &a, const dim3 g, hipStream_t s) {
-    if (a.act == 2 && !a.in_relu) launch_dw_t<T, R, 2, false>(a, g, s);
-    else if (a.act == 0 && a.in_relu) launch_dw_t<T, R, 0, true>(a, g, s);
-    else if (a.act == 1 && !a.in_relu) launch_dw_t<T, R, 1, false>(a, g, s);
-    else if (a.act == 0 && !a.in_relu) launch_dw_t<T, R, 0, false>(a, g, s);
+    if (a.act == 2 && !a.in_relu) hipLaunchKernelGGL((dl_dw_kernel<T, S1, R, 2, false>), g, dim3(256), 0, s, a);
+    else if (a.act == 0 && a.in_relu) hipLaunchKernelGGL((dl_dw_kernel<T, S1, R, 0, true>), g, dim3(256), 0, s, a);
+    else if (a.act == 1 && !a.in_relu) hipLaunchKernelGGL((dl_dw_kernel<T, S1, R, 1, false>), g, dim3(256), 0, s, a);
+    else if (a.act == 0 && !a.in_relu) hipLaunchKernelGGL((dl_dw_kernel<T, S1, R, 0, false>), g, dim3(256), 0, s, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
-template <int R>
+// S1: stride 1 (else 2); R: output rows per thread
+template <bool S1, int R>
 static hipError_t launch_dw_r(int prec, const DlDwArgs &a, hipStream_t s) {
-    const int ph = a.stride == 1 ? a.dil : 1;
+    const int ph = S1 ? a.dil : 1;
     const int n = a.B * ((a.Hout + R * ph - 1) / (R * ph) * ph) * a.Wout * (a.C >> 3);
     const dim3 g((n + 255) / 256);
-    return prec == PREC_BF16 ? launch_dw_a<__bf16, R>(a, g, s) : launch_dw_a<float, R>(a, g, s);
+    return prec == PREC_BF16 ? launch_dw_a<__bf16, S1, R>(a, g, s) : launch_dw_a<float, S1, R>(a, g, s);
 }
 
 // Output rows per thread (R). Measured (16 frames, 513x513, per-op HIP events, 17 launches): stride-1
 // layers R = 2 / 4 / 8: 680 / 576 / 534 us in total, R = 8 fastest in every layer (246 VGPRs, two waves
-// per SIMD); stride 2 keeps R = 2 (R = 4 / 8 within 1%). BUGSEG_DL_DWR=2|4|8 forces R for stride 1.
+// per SIMD); stride 2 keeps R = 2 (R = 4 / 8 within 1%). Stride 1 with R = 2 / 4 (the knob BUGSEG_DL_DWR):
+// tried, slower, removed.
 hipError_t dl_launch_dw(int prec, const DlDwArgs &a, hipStream_t s) {
     if (a.stride != 1 && (a.stride != 2 || a.dil != 1)) return hipErrorInvalidValue;   // TF: no strided atrous
-    static const int env = [] { const char *e = std::getenv("BUGSEG_DL_DWR"); return e ? std::atoi(e) : 0; }();
-    if (a.stride == 2) return launch_dw_r<2>(prec, a, s);
-    if (env == 2) return launch_dw_r<2>(prec, a, s);
-    if (env == 4) return launch_dw_r<4>(prec, a, s);
-    return launch_dw_r<8>(prec, a, s);
+    return a.stride == 1 ? launch_dw_r<true, 8>(prec, a, s) : launch_dw_r<false, 2>(prec, a, s);
 }
 
 hipError_t dl_launch_pool(int prec, const DlPoolArgs &a, hipStream_t s) {

@@ -40,6 +40,8 @@ struct DlIo {
 }  // namespace
 
 struct bugseg_dl {
+    explicit bugseg_dl(const Knobs &k) : knobs(k) {}
+    const Knobs knobs;            // the BUGSEG_* knobs as bugseg_dl_create read them (knobs.h)
     int device = 0, prec = 0;
     std::string err;
     void *dev_w = nullptr;
@@ -268,7 +270,7 @@ hipError_t run_op(bugseg_dl *c, const DlOp &o, const DlIo &io, hipStream_t s) {
     }
     case OP_CONV: {
         const DlConvArgs a = conv_args(c, o, io);
-        return dl_launch_conv(c->prec, f[24] != 0, a, s);
+        return dl_launch_conv(c->knobs, c->prec, f[24] != 0, a, s);
     }
     case OP_DW: {
         DlDwArgs a{};
@@ -336,7 +338,10 @@ int bugseg_dl_create(int device, int precision, bugseg_dl **out) {
     if (!out || (precision != BUGSEG_FP32 && precision != BUGSEG_BF16)) return dl_fail(nullptr, BUGSEG_EINVAL, "bad argument");
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return dl_fail(nullptr, BUGSEG_EINVAL, "no such HIP device");
-    auto *c = new bugseg_dl();
+    Knobs knobs;
+    std::string bad;
+    if (!read_knobs(knobs, bad)) return dl_fail(nullptr, BUGSEG_EINVAL, bad);
+    auto *c = new bugseg_dl(knobs);
     c->device = device;
     c->prec = precision == BUGSEG_BF16 ? PREC_BF16 : PREC_F32;
     {   // the class LUT lives as long as the context: identity until one is set
@@ -404,7 +409,7 @@ int validate_plan(bugseg_dl *c, int prec, size_t w_bytes, const int32_t *ops, in
         off[i] = total;
         total += (bb[i] + 255) & ~(size_t)255;
     }
-    bugseg_dl probe;
+    bugseg_dl probe{Knobs()};
     probe.prec = prec; probe.w_bytes = w_bytes; probe.buf_bytes = bb; probe.B = B; probe.Hc = Hc; probe.Wc = Wc;
     for (int i = 0; i < nops; ++i) {
         std::string why;
@@ -488,15 +493,13 @@ int check_classes(bugseg_dl *c, int H, int row0, int row1) {
 
 // Every op of the plan on stream s (callers have validated io against the plan).
 int run_plan(bugseg_dl *c, const DlIo &io, hipStream_t s) {
-    const char *ge = std::getenv("BUGSEG_DL_GROUP");
-    const bool group = !(ge && *ge == '0');
     for (size_t i = 0; i < c->ops.size(); ++i) {
-        const int n = group ? c->group_len[i] : 1;
+        const int n = c->knobs.dl_group ? c->group_len[i] : 1;
         if (n > 1) {   // same-shape convs as one launch (the ASPP's atrous branches)
             DlConvGroup grp{};
             grp.n = n;
             for (int k = 0; k < n; ++k) grp.a[k] = conv_args(c, c->ops[i + k], io);
-            const hipError_t e = dl_launch_conv_group(c->prec, grp, s);
+            const hipError_t e = dl_launch_conv_group(c->knobs, c->prec, grp, s);
             if (e == hipSuccess) { i += n - 1; continue; }
             if (e != hipErrorNotSupported) return dl_fail(c, BUGSEG_EHIP, "grouped launch at op " + std::to_string(i) + ": " + hipGetErrorString(e));
             (void)hipGetLastError();
@@ -586,6 +589,12 @@ int bugseg_dl_read_buffer(bugseg_dl *c, int buf, void *dst_dev, size_t bytes, vo
     DevGuard g(c->device);
     const hipError_t e = hipMemcpyAsync(dst_dev, bufp(c, buf), bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? BUGSEG_OK : dl_fail(c, BUGSEG_EHIP, hipGetErrorString(e));
+}
+
+int bugseg_dl_debug_knobs(const bugseg_dl *c, char *buf, int len) {
+    std::string err;
+    const int rc = dump_knobs(c ? &c->knobs : nullptr, buf, len, err);
+    return rc == BUGSEG_OK ? rc : dl_fail(const_cast<bugseg_dl *>(c), rc, err);
 }
 
 const char *bugseg_dl_last_error(const bugseg_dl *c) { return c ? c->err.c_str() : g_dl_err.c_str(); }

@@ -418,7 +418,6 @@ hipError_t launch_init(int prec, bool bgr, const ConvArgs &args, hipStream_t s) 
     int g = init_tiles(a);
     g = g < cap ? g : cap;
     g = g & ~7 ? g & ~7 : 8;
-    a.pool_scan = getenv("BUGSEG_INIT_POOL_SCAN") != nullptr;
     if (prec == PREC_BF16) {
         if (bgr) hipLaunchKernelGGL((init_kernel<__bf16, true>), dim3(g), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((init_kernel<__bf16, false>), dim3(g), dim3(256), 0, s, a);

@@ -271,10 +271,17 @@ int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_
  * forward sees the fill and not a correct row left by an earlier one. */
 int bugseg_debug_poison_arena(bugseg_ctx *ctx, int byte, void *stream);
 /* Test hook: a context fact. what = 0: the fused initial block normalises bytes with the exact affine
- * form (bf16 / fp16; 0 = the table), 1: fp32 range scaling switched off (BUGSEG_F32_RANGE=0 at load),
+ * form (bf16 / fp16; 0 = the table), 1: fp32 range scaling switched off (BUGSEG_F32_RANGE=0 at creation),
  * 2: the weights' exponent of packed convolution `arg` (fp32 range scaling; -1000 if no such conv).
  * Returns -1 for an unknown `what` or a NULL ctx. */
 int bugseg_debug_ctx_info(const bugseg_ctx *ctx, int what, int arg);
+/* The BUGSEG_* run-time knobs (environment variables; DESIGN.md lists them) are read once, when a context is
+ * created, and held there: nothing after bugseg_create / bugseg_dl_create reads the environment. A value outside
+ * a knob's rule (a boolean: 0 or 1; an integer: a decimal in the knob's range) makes the create call fail with
+ * BUGSEG_EINVAL, last_error(NULL) naming the variable and the value.
+ * Test hook: one NAME=value line per knob into buf[len], NUL-terminated: the values ctx holds, or with a NULL
+ * ctx those of the environment as it is now (host only). BUGSEG_EINVAL: a bad value, or buf too small. */
+int bugseg_debug_knobs(const bugseg_ctx *ctx, char *buf, int len);
 /* Measurement hook (bench.py's in-step kernel table): arm launch spans. spans = device memory of
  * 512 x uint64 per plan op for n_ops ops (NULL disarms): 64 slots 64 B apart, slot k = [k*8] entry,
  * [k*8+1] exit; every later launch of op i < n_ops folds the constant 100 MHz GPU clock into the slots
@@ -338,6 +345,9 @@ int bugseg_dl_launch_op(bugseg_dl *dl, int op, void *stream);
  * logits at the backbone resolution) to a device pointer, on `stream`. */
 int bugseg_dl_read_buffer(bugseg_dl *dl, int buf, void *dst_dev, size_t bytes, void *stream);
 const char *bugseg_dl_last_error(const bugseg_dl *dl);
+/* Test hook: bugseg_debug_knobs for a DeepLab context (NULL: the environment now; errors to
+ * bugseg_dl_last_error(NULL)). */
+int bugseg_dl_debug_knobs(const bugseg_dl *dl, char *buf, int len);
 /* Test hook (host only): the plan validation of bugseg_dl_set_plan against a weight blob of w_bytes;
  * errors go to bugseg_dl_last_error(NULL). */
 int bugseg_dl_debug_check_plan(const int32_t *ops, int nops, const uint64_t *buf_bytes, int nbufs, int B, int Hc, int Wc,

@@ -1,5 +1,5 @@
 """Debug: BEV rasteriser time per 32-frame batch on the bench's class maps (the kernel variant is
-chosen by BUGSEG_BEV_F, read once per process), for rocprofv3 counter passes (scripts/gpu_bevpmc.sh).
+chosen by BUGSEG_BEV_F, read when the shared context is created: set it before the first call), for rocprofv3 counter passes (scripts/gpu_bevpmc.sh).
 
 usage: python scripts/bev_probe.py [reps]"""
 import os

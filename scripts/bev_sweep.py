@@ -1,5 +1,6 @@
 """Debug: every form of the BEV rasteriser (bev_kernels.hip; BUGSEG_BEV_F = frames per thread of the
-gather kernel, BUGSEG_BEV_FG = frames per workgroup of the LDS-staged kernel; both read per call) at
+gather kernel, BUGSEG_BEV_FG = frames per workgroup of the LDS-staged kernel; a context holds the knobs
+it was created under, so every setting runs on a fresh shared context) at
 the bench shard (32 frames of 480x640, the bench's class maps), HIP-event time per launch (a graph of
 `reps` launches replayed: eager back-to-back calls are host-bound), and a
 check that every form gives the same grids.
@@ -38,6 +39,7 @@ for f, fg in [(None, None), ("FB2", None), ("1", None), ("2", None), ("1", "4"),
         os.environ.pop("BUGSEG_BEV_FG", None)
     else:
         os.environ["BUGSEG_BEV_FG"] = fg
+    N._shared.clear()                             # the next call creates a context under this setting
     for ls in (False, True):
         bev.laserscan_like_occupancy_grid = ls
         g = bev.create_occupancy_grid_device(seg, *grid)

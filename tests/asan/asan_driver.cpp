@@ -2,7 +2,8 @@
 // ASan + UBSan on the host code only (tests/asan/build.sh) and run by tests/test_asan_runtime.py on the
 // CPU. It feeds the BSG1 weight-blob parser + BN folding + packer (bugseg_debug_parse_pack = what
 // bugseg_load_weights does before the upload), the DeepLab plan validator (bugseg_dl_debug_check_plan
-// = bugseg_dl_set_plan before the allocation) and the polar-table builder with valid inputs, every
+// = bugseg_dl_set_plan before the allocation), the polar-table builder and the knob reader (the environment,
+// set in-process: bugseg_debug_knobs / bugseg_dl_debug_knobs with no context) with valid inputs, every
 // truncation of the blob's head and a sample of the rest, and seeded corruptions. Any out-of-bounds
 // access, use-after-free or undefined behaviour aborts the process (exit status != 0); a rejected input
 // is the expected outcome for a corrupted one.
@@ -123,6 +124,36 @@ int main(int argc, char **argv) {
         }
     tally(bugseg_debug_polar_tables(0, 5, 0, nullptr, 0, nullptr, 0, nullptr, nullptr));
     tally(bugseg_debug_polar_tables(40000, 5, 0, nullptr, 0, nullptr, 0, nullptr, nullptr));
+
+    // ---- the run-time knobs (csrc/knobs.h, read_knobs): the environment parsed in-process, with good, bad and empty
+    // values, into a full-size, a 1-byte and a missing buffer
+    static const char *const kKnob[][3] = {   // variable, value, "1" if the parse must succeed
+        {"BUGSEG_TILE_ORDER", "2", "1"}, {"BUGSEG_TILE_ORDER", "3", "0"}, {"BUGSEG_TILE_ORDER", "", "1"},
+        {"BUGSEG_NO_FUSE", "1", "1"}, {"BUGSEG_NO_FUSE", "yes", "0"}, {"BUGSEG_CLS_CONV", "0", "1"},
+        {"BUGSEG_BEV_FB", "x", "0"}, {"BUGSEG_BEV_FB", "2", "1"}, {"BUGSEG_BEV_F", "3", "0"}, {"BUGSEG_BEV_F", "4", "1"},
+        {"BUGSEG_BNECK_GRID", "-2", "1"}, {"BUGSEG_BNECK_GRID", "-", "0"}, {"BUGSEG_BNECK_GRID", "99999999999999999999", "0"},
+        {"BUGSEG_BNECK_VARIANT_C128", "5", "1"}, {"BUGSEG_BNECK_VARIANT_C64", "5", "0"}, {"BUGSEG_DL_GTM", "1", "1"},
+        {"BUGSEG_DL_GROUP", " 0", "0"},
+    };
+    for (const auto &k : kKnob) {
+        setenv(k[0], k[1], 1);
+        const bool want = k[2][0] == '1';
+        char big[4096], one[1] = {'#'};
+        for (int dl = 0; dl < 2; ++dl) {
+            const int rc = dl ? bugseg_dl_debug_knobs(nullptr, big, sizeof(big)) : bugseg_debug_knobs(nullptr, big, sizeof(big));
+            const char *err = dl ? bugseg_dl_last_error(nullptr) : bugseg_last_error(nullptr);
+            if ((rc == BUGSEG_OK) != want || (!want && (rc != BUGSEG_EINVAL || !std::strstr(err, k[0])))) {
+                std::fprintf(stderr, "knob %s=%s: rc %d, error '%s'\n", k[0], k[1], rc, err);
+                return 1;
+            }
+            tally(rc);
+            // too small, or no buffer at all: an error either way, and nothing is written
+            const int r1 = dl ? bugseg_dl_debug_knobs(nullptr, one, 1) : bugseg_debug_knobs(nullptr, one, 1);
+            const int r0 = dl ? bugseg_dl_debug_knobs(nullptr, nullptr, 64) : bugseg_debug_knobs(nullptr, nullptr, 64);
+            if (r1 != BUGSEG_EINVAL || r0 != BUGSEG_EINVAL || one[0] != '#') { std::fprintf(stderr, "knob dump into a short buffer\n"); return 1; }
+        }
+        unsetenv(k[0]);
+    }
 
     std::printf("asan driver ok: %ld inputs accepted, %ld rejected\n", accepted, rejected);
     return 0;

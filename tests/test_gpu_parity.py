@@ -190,19 +190,19 @@ def _bev_case(rows, cols, ww, wh, seed):
 def test_bev_occgrid_bit_exact(gpu, rows, cols, ww, wh, grid, seed, form, monkeypatch):
     """Every form of the rasteriser (bev_kernels.hip: the default band-staged kernel, 2 frames per
     band workgroup, the gather kernel, the block-staged one, 2 frames per thread; NEAR: the band
-    kernel's work items nearest band first, the earlier order, if this context builds the table) is bit-exact against
+    kernel's work items nearest band first, the earlier order) is bit-exact against
     the C restatement; class maps with labels past the 3-class range (up to 255: segmap + 1 wraps in
-    uint8 as np.add does, bev.py:177) included."""
-    if form == "G":
-        monkeypatch.setenv("BUGSEG_BEV_BAND", "0")
-    elif form == "FB2":
-        monkeypatch.setenv("BUGSEG_BEV_FB", "2")
-    elif form == "FG4":
-        monkeypatch.setenv("BUGSEG_BEV_FG", "4")
-    elif form == "F2":
-        monkeypatch.setenv("BUGSEG_BEV_F", "2")
-    elif form == "NEAR":
-        monkeypatch.setenv("BUGSEG_BEV_NEAR_FIRST", "1")
+    uint8 as np.add does, bev.py:177) included. A context holds the knobs it was created under, so each
+    case runs on a fresh shared context: its form, and for NEAR its table order, really runs."""
+    knob = {None: None, "G": ("BUGSEG_BEV_BAND", 0), "FB2": ("BUGSEG_BEV_FB", 2), "FG4": ("BUGSEG_BEV_FG", 4),
+            "F2": ("BUGSEG_BEV_F", 2), "NEAR": ("BUGSEG_BEV_NEAR_FIRST", 1)}[form]
+    if knob is not None:
+        monkeypatch.setenv(knob[0], str(knob[1]))
+    monkeypatch.setattr(N, "_shared", {})
+    held = N.shared_context(gpu.index).knobs()
+    assert held == N.knobs()                       # (None: the environment as it is now)
+    if knob is not None:
+        assert held[knob[0]] == knob[1]
     bev = _bev_case(rows, cols, ww, wh, seed)
     rng = np.random.default_rng(seed)
     # blocky class maps (realistic regions + speckles) and pure noise
@@ -311,7 +311,8 @@ def test_forward_bgr_equals_preprocess_then_forward(gpu, prec, pool_k):
 def test_init_affine_normalisation_equals_table(gpu, blocks, prec, monkeypatch):
     """bf16 / fp16: the fused initial block normalises each byte as one fmaf with per-channel constants
     the context found exact on the device (bugseg_runtime.cpp, init_kernels.hip naff_search_kernel);
-    the table form (BUGSEG_INIT_TABLE=1) gives the same logits bit for bit, at the bench shape."""
+    the table form (a context created under BUGSEG_INIT_TABLE=1) gives the same logits bit for bit, at the
+    bench shape."""
     B, H, W = 2, 480, 640
     bgr = torch.from_numpy(synthetic.uniform_frames(B, H, W)).cuda()
     m = ENET(weights=blocks, precision=prec)
@@ -321,28 +322,34 @@ def test_init_affine_normalisation_equals_table(gpu, blocks, prec, monkeypatch):
     a = torch.empty((B, 15, H, W), dtype=torch.float32, device=gpu)
     m.ctx.forward_bgr(bgr, B, H, W, N.OUT_LOGITS_F32, a)
     monkeypatch.setenv("BUGSEG_INIT_TABLE", "1")
+    t = ENET(weights=blocks, precision=prec)
+    assert (m.ctx.knobs()["BUGSEG_INIT_TABLE"], t.ctx.knobs()["BUGSEG_INIT_TABLE"]) == (0, 1)
+    assert t.ctx.debug_info(0) == 0                 # the table context never took the affine form
     b = torch.empty_like(a)
-    m.ctx.forward_bgr(bgr, B, H, W, N.OUT_LOGITS_F32, b)
+    t.ctx.forward_bgr(bgr, B, H, W, N.OUT_LOGITS_F32, b)
     assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("pool_k", [3, 2])
 def test_init_packed_pool_equals_scan(gpu, pool_k, monkeypatch):
     """fp16: the initial block's pool maxima as packed f16 pairs from 5-dword window rows
-    (init_kernels.hip) equal the per-tap scan (BUGSEG_INIT_POOL_SCAN=1) bit for bit — frame edges (the
-    excluded -inf taps) and pool_k 2's window included, raw-BGR and engine-input entries alike."""
+    (init_kernels.hip) equal the per-tap scan (a context created under BUGSEG_INIT_POOL_SCAN=1) bit for
+    bit — frame edges (the excluded -inf taps) and pool_k 2's window included, raw-BGR and engine-input
+    entries alike."""
     bl = enet_spec.build_enet(seed=19, initial_pool_k=pool_k)
-    m = ENET(weights=bl, precision="fp16")
     B, H, W = 2, 72, 104
     bgr = torch.from_numpy(synthetic.road_frames(B, H, W, seed=9)).cuda()
-    x = ENET.preprocess_device(bgr, N.PRE_ENGINE, ctx=m.ctx, width=W, height=H)
-    outs = []
+    outs, held = [], []
     for scan in (False, True):
         if scan:
             monkeypatch.setenv("BUGSEG_INIT_POOL_SCAN", "1")
+        m = ENET(weights=bl, precision="fp16")
+        held.append(m.ctx.knobs()["BUGSEG_INIT_POOL_SCAN"])
+        x = ENET.preprocess_device(bgr, N.PRE_ENGINE, ctx=m.ctx, width=W, height=H)
         a = torch.empty((B, 15, H, W), dtype=torch.float32, device=gpu)
         m.ctx.forward_bgr(bgr, B, H, W, N.OUT_LOGITS_F32, a)
         outs.append((a, m.predict_device(x, N.OUT_LOGITS_F32)))
+    assert held == [0, 1]
     assert torch.equal(outs[0][0], outs[1][0])
     assert torch.equal(outs[0][1], outs[1][1])
 
@@ -472,7 +479,7 @@ def test_class_fusion_under_range_scaling(gpu):
     try:
         m = ENET(weights=bl, precision="fp32")
         lg = torch.empty((B, m.num_classes, H, W), dtype=torch.float32, device=gpu)
-        m.ctx.forward_bgr(bgr, B, H, W, N.OUT_LOGITS_F32, lg)       # (the plan, and its fusion choice, is built here)
+        m.ctx.forward_bgr(bgr, B, H, W, N.OUT_LOGITS_F32, lg)       # (the fusion choice was made when the context was created)
     finally:
         del os.environ["BUGSEG_CLS_FUSE"]
     seg = torch.empty((B, H, W), dtype=torch.uint8, device=gpu)

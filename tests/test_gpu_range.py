@@ -139,7 +139,7 @@ def test_extreme_weight_scales(gpu, name, unit, factor):
 
 
 def test_without_scaling_the_undamped_case_fails(gpu, monkeypatch):
-    """Negative control: BUGSEG_F32_RANGE=0 (read at load_weights) packs the weights unscaled and runs
+    """Negative control: BUGSEG_F32_RANGE=0 (read when the context is created) packs the weights unscaled and runs
     every kernel at exponent 0; the undamped case then fails the criterion (its activations overflow
     the f16 parts) — the tests above measure the scaling, not a criterion any f32 run would pass."""
     monkeypatch.setenv("BUGSEG_F32_RANGE", "0")

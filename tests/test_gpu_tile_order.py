@@ -21,7 +21,7 @@ SHAPES = [(2, 72, 104), (2, 480, 640), (3, 128, 128), (3, 120, 160)]
 
 
 def _forward(weights, prec, bgr, order, monkeypatch, gpu):
-    """logits and 3-class map of a fresh context (the order is read when its plan is built). The context
+    """logits and 3-class map of a fresh context (the order is read when the context is created). The context
     first runs another input, and the outputs start poisoned: a tile the walk skipped would keep those
     values, not an earlier context's correct ones that the allocator handed back."""
     B, H, W = bgr.shape[:3]
