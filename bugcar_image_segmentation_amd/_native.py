@@ -28,6 +28,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_debug_stage3_windows", "bugseg_debug_plan_windows", "bugseg_debug_read_block_output",
             "bugseg_bev_occgrid", "bugseg_bev_workspace_bytes", "bugseg_bev_occgrid_ws", "bugseg_plan_info", "bugseg_plan_op", "bugseg_plan_launch_op",
             "bugseg_last_error",
+            "bugseg_road_filter_workspace_bytes", "bugseg_road_filter", "bugseg_debug_road_filter_ops",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
@@ -42,6 +43,12 @@ class BevParams(ctypes.Structure):
                 ("occ_h_px", ctypes.c_int), ("occ_w", ctypes.c_int), ("occ_h", ctypes.c_int),
                 ("left_x", ctypes.c_int), ("top_y", ctypes.c_int), ("ros_layout", ctypes.c_int),
                 ("variant", ctypes.c_int), ("laserscan", ctypes.c_int)]
+
+
+class RoadFilterParams(ctypes.Structure):
+    """bugseg_road_filter_params: image_processing_utils.road_filter_params computes them."""
+    _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("k", ctypes.c_int), ("y_top", ctypes.c_int),
+                ("min_count", ctypes.c_int)]
 
 
 class BugsegError(RuntimeError):
@@ -94,6 +101,9 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
             "bugseg_plan_launch_op": (i, [vp, i, i, i, i, vp]),
             "bugseg_last_error": (cp, [vp]),
+            "bugseg_road_filter_workspace_bytes": (sz, [ctypes.POINTER(RoadFilterParams), i]),
+            "bugseg_road_filter": (i, [vp, vp, i, ctypes.POINTER(RoadFilterParams), vp, vp, sz, vp]),
+            "bugseg_debug_road_filter_ops": (i, [vp, vp, i, ctypes.POINTER(RoadFilterParams), vp, vp, sz, i, i, vp]),
             "bugseg_dl_create": (i, [i, i, ctypes.POINTER(vp)]),
             "bugseg_dl_destroy": (i, [vp]),
             "bugseg_dl_load_weights": (i, [vp, vp, sz]),
@@ -213,7 +223,10 @@ class Context:
 
     def __del__(self):
         try:
-            self.close()
+            # (destroying synchronises the device and frees memory, which would end a capture in progress:
+            # a context the collector finalizes there is left to the process's end instead)
+            if not torch.cuda.is_current_stream_capturing():
+                self.close()
         except Exception:
             pass
 
@@ -295,6 +308,27 @@ class Context:
                 ws = torch.empty(nws, dtype=torch.uint8, device=seg.device)
         check(self.lib.bugseg_bev_occgrid_ws(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(),
                                              0 if ws is None else ws.data_ptr(), nws, stream_handle(st)), self.h)
+
+    def road_filter(self, seg, B, params: RoadFilterParams, out, stream=None, ops=None, workspace=None):
+        """bugseg_road_filter: the workspace comes from torch's caching allocator on the stream the work
+        runs on, as in bev (`workspace`: a uint8 device tensor to use instead). ops = (first, last) enqueues
+        only those launches (bugseg_debug_road_filter_ops, the benchmark's per-kernel times). Any refusal,
+        a bad argument included, raises BugsegError and launches nothing."""
+        st = stream if stream is not None else torch.cuda.current_stream(seg.device)
+        nws = int(self.lib.bugseg_road_filter_workspace_bytes(ctypes.byref(params), B))
+        ws = workspace
+        if ws is None and nws:
+            with torch.cuda.stream(st):
+                ws = torch.empty(nws, dtype=torch.uint8, device=seg.device)
+        wp, wn = (0, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
+        if ops is None:
+            rc = self.lib.bugseg_road_filter(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(), wp, wn,
+                                             stream_handle(st))
+        else:
+            rc = self.lib.bugseg_debug_road_filter_ops(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(),
+                                                       wp, wn, int(ops[0]), int(ops[1]), stream_handle(st))
+        if rc != OK:
+            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
 
     def plan_info(self, B, H, W, out_kind, bgr_input=False):
         """-> (launches, per-layer algorithmic bytes, plan compulsory bytes, flops) of one forward."""
@@ -394,7 +428,10 @@ class DeepLabContext:
 
     def __del__(self):
         try:
-            self.close()
+            # (destroying synchronises the device and frees memory, which would end a capture in progress:
+            # a context the collector finalizes there is left to the process's end instead)
+            if not torch.cuda.is_current_stream_capturing():
+                self.close()
         except Exception:
             pass
 

@@ -6,6 +6,8 @@
 
 #include "knobs.h"
 
+struct bugseg_ctx;
+
 namespace bugseg {
 
 // ---- implicit-GEMM convolution (conv_kernels.hip) -------------------------------------------
@@ -317,5 +319,11 @@ __host__ __device__ inline size_t bev_ctab_offset(int occ_w, int occ_h) {
 __host__ __device__ inline size_t bev_items_offset(int occ_w, int occ_h) {
     return (bev_ctab_offset(occ_w, occ_h) + (size_t)occ_w * occ_h * (BEV_WIN + 1) * 4 + 255) & ~(size_t)255;
 }
+
+// ---- what the runtime exports to entry points that live beside their kernels (road_kernels.hip: the
+// runtime itself references nothing of that file). ctx_fail: record `msg` as ctx's last error (the calling
+// thread's when ctx is null) and return `code`; ctx_device: the HIP device the context was created on.
+int ctx_fail(bugseg_ctx *ctx, int code, const char *msg);
+int ctx_device(const bugseg_ctx *ctx);
 
 }  // namespace bugseg

@@ -1578,6 +1578,11 @@ void linear_coeffs(int dsize, int ssize, double scale, int *ofs, short *a01) {
 
 }  // namespace
 
+namespace bugseg {
+int ctx_fail(bugseg_ctx *ctx, int code, const char *msg) { return fail(ctx, code, msg); }
+int ctx_device(const bugseg_ctx *ctx) { return ctx->device; }
+}  // namespace bugseg
+
 // =============================================================== C ABI
 extern "C" {
 

@@ -21,6 +21,7 @@ import torch
 
 from . import _native as N
 from . import enet_spec
+from .image_processing_utils import contour_noise_removal  # noqa: F401  (models.py:6)
 
 
 class InferenceModel(ABC):

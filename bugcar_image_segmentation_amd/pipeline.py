@@ -16,6 +16,8 @@ rasteriser run on a weightless engine context per shard.
 """
 from __future__ import annotations
 
+import gc
+
 import numpy as np
 import torch
 
@@ -32,7 +34,7 @@ class OccupancyPipeline:
     def __init__(self, model: "ENET | DeepLabV3", bev: bev_transform_tools, grid_w_m: float, grid_h_m: float, cell_m: float,
                  model_hw: tuple[int, int] | None = None, ros_layout: bool = False, streams: int = 1,
                  binary: bool = False, stream_priority: int = 0, chain_forwards: bool = False, shard_offset: int = 0,
-                 window_rows: bool = True):
+                 window_rows: bool = True, road_filter: bool = False):
         """binary=True is the predict_binary + create_occupancy_grid_binary pairing (models.py:70-82,
         bev.py:97-165): class maps through the binary LUT, the binary rasteriser; in the laserscan-like
         mode its output is the reference's pair, (2, B, ...) (bev.py:164). stream_priority is the HIP
@@ -52,7 +54,17 @@ class OccupancyPipeline:
         reference's conventions; binary=True only selects the binary rasteriser for what the LUT
         produces). model_hw then defaults to the net's crop and must fit inside it; every shard runs its
         own DeepLabV3.clone planned for that shard's frames; the row window applies to the final op
-        alone (the ASPP image pooling needs the whole frame); shard_offset is refused."""
+        alone (the ASPP image pooling needs the whole frame); shard_offset is refused.
+        road_filter=True runs contour_noise_removal (image_processing_utils.py:4-44) on
+        every shard's stream between the segmenter and the rasteriser: the class maps go through
+        Context.road_filter into a second u8 buffer, which the rasteriser reads. Its output is a {0, 1} map,
+        so it requires binary=True (ENET, or a DeepLabV3 whose LUT is class_lut_binary). The filter needs
+        whole maps: a row cut off above the window would open holes and change the closing near the
+        cut, so the forwards run full-frame whatever window_rows says."""
+        if road_filter and not binary:
+            raise ValueError("road_filter=True needs binary=True: contour_noise_removal reads and writes a {0, 1} road map")
+        self.road_filter = bool(road_filter)
+        self._road = None            # road_filter: (its parameters, the filtered maps the rasteriser reads)
         self.model = model
         self._dl = isinstance(model, DeepLabV3)
         self.binary = binary
@@ -86,7 +98,7 @@ class OccupancyPipeline:
         self._ctxs = [N.Context(model.ctx.device, N.FP32)] if self._dl else [model.ctx]
         self._engines = [model] if self._dl else []
         self._streams = []
-        self.window_rows = bool(window_rows)
+        self.window_rows = bool(window_rows) and not self.road_filter
         self._windowed = False       # the forwards of the run in progress are windowed
         self._spans = {}             # (context, calibration) -> the class-map rows the rasteriser reads
         self._x = None
@@ -147,6 +159,9 @@ class OccupancyPipeline:
             self._seg_raw = torch.zeros((B, self.H, self.W), dtype=torch.uint8, device=dev)
             self._seg_partial = None
             self._grid = torch.empty(self._grid_shape(B), dtype=torch.int8, device=dev)
+            if self.road_filter:
+                from .image_processing_utils import road_filter_params
+                self._road = (road_filter_params(self.H, self.W), torch.empty_like(self._seg_raw))
         return self._x, self._seg_raw, self._grid
 
     @property
@@ -255,10 +270,22 @@ class OccupancyPipeline:
             self.run(frames_bgr, out)
         elif self.streams > 1 and frames_bgr.shape[0] >= self.streams:
             self._shard_ctxs(dev)
+        # No finalizer may run inside the capture: a dead reference cycle (a pipeline and the HostStream that
+        # run_host keeps for it, say) still owns contexts, graphs and pinned buffers, and destroying those
+        # synchronises the device and frees memory, which HIP refuses while a stream captures and which ends the
+        # capture, or the process. The cyclic collector runs whenever allocation counts say so, so collect what
+        # is dead now and keep it off until the capture has ended.
+        gc.collect()
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            res = self.run(frames_bgr, out)
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph):
+                res = self.run(frames_bgr, out)
+        finally:
+            if gc_was_on:
+                gc.enable()
         return graph.replay, res
 
     def host_stream(self, batch: int, frame_hw: tuple[int, int] | None = None, depth: int = 2, graph: bool = True):
@@ -336,5 +363,12 @@ class OccupancyPipeline:
     def _run_shard(self, ctx, frames, x, seg, out, p, stream, forward=True):
         if forward:
             self._run_forward(ctx, frames, x, seg, stream)
+        if self.road_filter:
+            # the shard's frames of the filtered buffer: seg is a run of whole frames of _seg_raw
+            rp, flt = self._road
+            s = (seg.data_ptr() - self._seg_raw.data_ptr()) // (self.H * self.W)
+            flt = flt[s:s + frames.shape[0]]
+            ctx.road_filter(seg, frames.shape[0], rp, flt, stream)
+            seg = flt
         # the shard's own context: its laserscan scratch is never shared with another shard's stream
         ctx.bev(seg, frames.shape[0], p, out, stream)

@@ -208,6 +208,41 @@ size_t bugseg_bev_workspace_bytes(const bugseg_bev_params *p, int B);
 int bugseg_bev_occgrid_ws(bugseg_ctx *ctx, const uint8_t *seg_dev, int B, const bugseg_bev_params *p,
                           int8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* contour_noise_removal (image_processing_utils.py:4-44), the clean-up of a binary road map between
+ * ENET.predict_binary and create_occupancy_grid_binary: close small gaps with a k x k square, keep the
+ * road regions that reach the bottom band of the image, fill their small holes, drop everything else.
+ * The host arithmetic (image_processing_utils.py:6-8, 19-27, 31, 38) is done by the Python shim exactly as
+ * the reference does it and arrives here as integers:
+ *   k          side of the closing square, int(min(rows, cols) / 50); anchor k / 2 in both passes, taps
+ *              outside the image ignored in both (cv2.morphologyEx's default border)
+ *   y_top      first row of the bottom band, int(rows * (1 - 0.1))
+ *   min_count  fewest band pixels of a filled contour that is kept, floor(cols * (rows - y_top) * 0.4) + 1
+ * The exact semantics (regions, nesting, ring, even-odd output) are stated in DESIGN.md 6.16. */
+typedef struct { int rows, cols, k, y_top, min_count; } bugseg_road_filter_params;
+
+/* Bytes of the device workspace bugseg_road_filter needs for B frames (image_processing_utils.py:4-44 keeps
+ * its intermediates in host arrays: closed, cnt_map, masked): 17 bytes per pixel plus alignment; 0 for
+ * parameters the call would refuse for their shape. */
+size_t bugseg_road_filter_workspace_bytes(const bugseg_road_filter_params *p, int B);
+
+/* image_processing_utils.py:4-44 over a batch: seg_dev (B, rows, cols) u8, any non-zero value is road
+ * -> out_dev (B, rows, cols) u8 in {0, 1}. out_dev must not overlap seg_dev. The workspace is caller-owned
+ * and used only by the work this call enqueues on `stream` (as bugseg_bev_occgrid_ws: the caller's
+ * allocator orders its reuse); its prior contents do not matter. A fixed sequence of eight launches; the
+ * call never synchronises, needs no weights and no tables, and may be captured into a graph on its first
+ * call. BUGSEG_EINVAL: B < 1 (or above 65535, the launch grid's limit), k outside [1, 64], y_top outside
+ * [0, rows), min_count < 1, rows * cols too large for an int32 pixel index, a NULL or short workspace,
+ * overlapping buffers. */
+int bugseg_road_filter(bugseg_ctx *ctx, const uint8_t *seg_dev, int B, const bugseg_road_filter_params *p,
+                       uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Profiling hook (bench_road_filter.py; image_processing_utils.py:4-44 has no counterpart): enqueue only
+ * launches [first_op, last_op) of bugseg_road_filter's eight (last_op = -1: to the end): 0 close, 1 tile
+ * labels, 2 border merge, 3 flatten, 4 counts, 5 subtree sums, 6 keep, 7 output. */
+int bugseg_debug_road_filter_ops(bugseg_ctx *ctx, const uint8_t *seg_dev, int B, const bugseg_road_filter_params *p,
+                                 uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, int first_op,
+                                 int last_op, void *stream);
+
 /* Plan introspection for the bench / roofline, for the engine-input entry (bgr_input = 0) or
  * bugseg_enet_forward_bgr (bgr_input = 1), context precision:
  *   n_launches  kernel launches of one forward;
