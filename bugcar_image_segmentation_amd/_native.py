@@ -33,7 +33,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
             "bugseg_debug_parse_pack", "bugseg_debug_polar_tables", "bugseg_debug_ctx_info", "bugseg_debug_tile_walk", "bugseg_debug_set_spans", "bugseg_debug_pool_indices",
-            "bugseg_dl_debug_check_plan", "bugseg_debug_knobs", "bugseg_dl_debug_knobs")
+            "bugseg_dl_debug_check_plan", "bugseg_debug_knobs", "bugseg_dl_debug_knobs", "bugseg_debug_fused_forms")
 DL_OP_FIELDS = 32
 
 
@@ -124,6 +124,7 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_dl_debug_check_plan": (i, [vp, i, vp, i, i, i, i, i, sz]),
             "bugseg_debug_knobs": (i, [vp, vp, i]),
             "bugseg_dl_debug_knobs": (i, [vp, vp, i]),
+            "bugseg_debug_fused_forms": (i, [vp, i]),
         }
         for name, (res, args) in proto.items():
             f = getattr(lib, name)
@@ -155,6 +156,23 @@ def knobs(ctx=None, size: int = 4096, dl: bool = False) -> dict[str, int]:
     else:
         check(lib.bugseg_debug_knobs(ctx, buf, size), ctx)
     return {k: int(v) for k, v in (line.split("=") for line in buf.value.decode().splitlines())}
+
+
+FORM_COLS = ("kind", "precision", "C", "asym", "variant", "transposed", "cin", "windowed", "lut_kind", "threads",
+             "lds_bytes", "TH", "TW", "NW", "RD", "keep")
+
+
+def fused_forms() -> list[dict[str, int]]:
+    """Test hook (bugseg_debug_fused_forms, host only): one {column: value} row per built form of the fused
+    bottleneck (kind 0) and upsampling (kind 1) kernels, columns FORM_COLS (include/bugseg.h)."""
+    lib = load_library()
+    n = lib.bugseg_debug_fused_forms(None, 0)
+    if n < 0:
+        check(n)
+    rows = (ctypes.c_int32 * (n * len(FORM_COLS)))()
+    if lib.bugseg_debug_fused_forms(rows, n) != n:
+        raise RuntimeError("bugseg_debug_fused_forms: the form count changed between two calls")
+    return [dict(zip(FORM_COLS, rows[k * len(FORM_COLS):(k + 1) * len(FORM_COLS)])) for k in range(n)]
 
 
 def tile_walk(ntiles: int, grid: int, rev: int) -> list[list[int]]:

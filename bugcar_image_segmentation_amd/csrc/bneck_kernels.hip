@@ -34,6 +34,7 @@
 #include <cstdlib>
 
 #include <type_traits>
+#include <vector>
 
 #include "bugseg_internal.h"
 // output stores: the per-kernel cache-policy choice (OUT_AUX_SEL: sc1 write-through for C >= 64).
@@ -124,33 +125,163 @@ template <> struct BShape<16, 1> { static constexpr int TH = 20, TW = 16, NW = 4
 #ifndef BNECK_F32_HL64
 #define BNECK_F32_HL64 1
 #endif
-__host__ __device__ constexpr bool bneck_hl(int es, int C, bool dn) {
-    return BNECK_F32_HL && es == 4 && (C == 128 || (C == 64 && BNECK_F32_HL64)) && !dn;
-}
-__host__ __device__ constexpr bool bneck_pl(int es, int C, bool dn) { return bneck_hl(es, C, dn) && C == 64; }
-__host__ __device__ constexpr int bneck_padw(int es, int C, bool wide, bool dn) {
-    return bneck_hl(es, C, dn) ? 8 : es == 2 && (C != 128 || wide) ? 16 : 16 / es;
-}
-__host__ __device__ constexpr int bneck_pstr(int es, int IS, bool wide) {
-    return es != 2 ? (BNECK_F32_HL && es == 4 && IS == 32 ? 40 : IS + 16 / es) : IS == 32 ? (wide ? 48 : 40) : IS;
-}
-static bool bneck_wide(int C, int v, bool asym) {
-#define BW_CASE(CC, VV) if (C == CC && v == VV) return BShape<CC, VV>::WIDE && !asym;
-    BW_CASE(128, 0) BW_CASE(128, 1) BW_CASE(128, 2) BW_CASE(128, 3) BW_CASE(128, 4) BW_CASE(64, 0) BW_CASE(64, 1) BW_CASE(64, 2) BW_CASE(16, 0) BW_CASE(16, 1)
-#undef BW_CASE
-    return false;
-}
+#ifndef BNECK_REG3_C64
+#define BNECK_REG3_C64 0
+#endif
+// fp32 (parity mode) C = 64 with the register epilogue: no staging region, so the LDS footprint is the
+// halo's (8 x 16 tile: 42.7 -> 39.7 KB, 3 -> 4 workgroups per CU); its quads are 16-B chunks already.
+// Measured slower (round 3: 94.1 -> 104.7 us per launch: a pixel's 256 B leave as four 64-B pieces)
+// fp32 C = 64 (non-down) with the register epilogue AND whole-line stores (LINES below; round 6, A/B knob):
+// the residual is loaded in the same line layout and traded back with the same DPP row rotation.
+// Bit-identical (44 fp32 parity cases) but measured slower: 8 x 16 138.8 -> 147.5 us per 64-frame launch
+// (124 VGPRs, no spills; the half-staged LDS epilogue, HSTG, stays)
+#ifndef BNECK_F32_LINES64
+#define BNECK_F32_LINES64 0
+#endif
+#ifndef BNECK_REG3_C64_F32
+#define BNECK_REG3_C64_F32 0
+#endif
+// fp32 C = 64: the staged epilogue one 32-channel half at a time (HSTG below). Measured (round 3, fp32,
+// B = 32): the 8 x 16 form 94.2 -> 89.4 us per launch (3 -> 4 workgroups per CU), fp32 bench
+// 13,890 -> 14,065-14,095 frames/s; bit-identical (GPU-tested)
+#ifndef BNECK_F32_HSTG
+#define BNECK_F32_HSTG 1
+#endif
+#ifndef BNECK_KEEP
+#define BNECK_KEEP 1
+#endif
+// KEEP: the residual is the block input phase 1 already loaded. Phase 1 then walks the tile's
+// interior as phase 3's fragments (a run of one tile row, on the wave that will expand it) and the
+// halo border separately, and each wave keeps its interior fragments' x in registers through
+// phase 2 instead of re-reading them (an L2 / Infinity-Cache round trip per fragment; PMC: the
+// C128 launches fetched 1.67x their compulsory bytes with the re-read). 2-byte storage, symmetric
+// plain blocks, with the staged (C = 64) or the row-pair-swapped (C = 128) epilogue.
+#ifndef BNECK_KEEP_ASYM
+// the asymmetric form keeps its residual too (round 4: with the single-pass 5x1 it spills 3 VGPRs and
+// runs 26.7 vs 26.5 us per launch re-reading, i.e. equal, for ~25 MB less HBM traffic per launch;
+// round 3, before that rewrite, it had spilled more and run 26.2 -> 27.2 us)
+#define BNECK_KEEP_ASYM 1
+#endif
+#ifndef BNECK_KEEP_C64
+// C = 64, 2-byte: the residual kept (16 x 16 and 8 x 16 tiles; the 20 x 16 tile's five fragments per wave
+// exceed the kept-register budget). Round 2 (B = 32, two streams) measured it slower: 41.0 vs 38.0 us per
+// launch. Round 6 (B = 64, one stream): the 20 x 16 form re-reads its residual from HBM (PMC 228 MB read
+// per launch, 1.45x the 157 MB compulsory) while 16 x 16 kept reads 160 MB (1.02x) in 70.9 vs 71.8 us —
+// so it is on, and the tile picker charges the 20 x 16 form for its re-read (bugseg_runtime.cpp)
+#define BNECK_KEEP_C64 1
+#endif
+#ifndef BNECK_KEEP_F32
+#define BNECK_KEEP_F32 1
+#endif
+#ifndef BNECK_KEEP_F32_ASYM
+#define BNECK_KEEP_F32_ASYM 1
+#endif
+
+// One compile-time description per bottleneck form: what the kernel body and the launcher both need — the tile
+// shape, the layout choices and the LDS MAP, the byte offset of every region of the dynamic allocation and its
+// size. bneck_body takes every region pointer from here and the launchers take LDS_BYTES from here (through
+// the form table at the end of this file), so the size a launch asks for and the addresses its kernel writes
+// have one definition, and a -D A/B build of a knob below moves both. TR, SCL and WIN (bneck_body) do not
+// change the layout and are not parameters. CI > 0: the down form; FC >= 0: the class-fused form.
+template <typename T, int C, bool ASYM, int V, int CI = 0, int FC = -1>
+struct BneckForm {
+    static constexpr int ES = (int)sizeof(T);
+    static constexpr int TH = BShape<C, V>::TH, TW = BShape<C, V>::TW, NW = BShape<C, V>::NW, NT = NW * 64;
+    static constexpr bool RD = BShape<C, V>::RD, DN = CI > 0, CLS = FC >= 0;
+    static_assert(!(RD && ASYM), "row-dilated tiles are for 3x3 blocks");
+    static constexpr int I = DN ? CI / 4 : C / 4;     // internal channels (ENet: input / 4)
+    static constexpr int IS = I < 8 ? 8 : I;          // stored internal channels (8-channel groups)
+    static constexpr int NR1 = (I + 15) / 16;         // 16-row fragments of t0 / t1
+    static constexpr int NR3 = C / 16;                // 16-row fragments of out
+    static constexpr int G1 = DN ? CI / 2 : C / 8, KS1 = (G1 + 3) / 4;   // proj k groups / steps (down: 4 taps x CI)
+    static constexpr int G2 = (ASYM ? 5 : 9) * IS / 8, KS2 = (G2 + 3) / 4;   // middle conv: taps x stored channels
+    static constexpr int RY = ASYM ? 2 : 1;           // halo rows / columns of the middle conv (tile coordinates)
+    static constexpr int RX = RD ? 0 : RY;            // row-dilated tiles span the width: no column halo
+    static constexpr int HWW = TW + 2 * RX, HR = (TH + 2 * RY) * HWW;   // tile + halo: width, pixels
+    static constexpr int NPX = TH * TW;
+    static constexpr int NF2 = ((NPX + 15) / 16 + NW - 1) / NW;   // 16-pixel tile fragments per wave
+    static constexpr int NPA = TH * (TW + 4);         // asymmetric: pixels of t1a (the 1x5's halo)
+    // strides (see "LDS strides" above)
+    static constexpr bool WIDE = BShape<C, V>::WIDE && !ASYM;
+    static constexpr bool HLW = BNECK_F32_HL && ES == 4 && (C == 128 || (C == 64 && BNECK_F32_HL64)) && !DN;   // HL weight rows
+    // HL (fp32 C = 128, round 5): in LDS a 32-element k-step of a split weight row, and a t0 / t1a pixel's
+    // 32 channels, hold the four 8-channel groups' hi parts (16 B each) and then their lo parts, instead of
+    // hi + lo per group — so each of a lane's two 16-B reads is 4 dwords at 4 kq dwords apart, as in bf16,
+    // and rows of 8 / 40 dwords mod 64 make every ds_read_b128 lane group conflict-free (SQ: 41% of the
+    // LDS cycles of these forms were bank conflicts with 32-B groups). The weight staging permutes the
+    // 16-B chunks (the packed matrices in HBM keep the shared layout); the same parts feed the same products
+    static constexpr bool HL = HLW && !(C == 64 && ASYM);   // (no C64 asymmetric block in ENet)
+    static constexpr bool PL = HLW && C == 64 && !ASYM;     // fp32 C = 64: t0 as hi / lo planes
+    static_assert(!HL || IS == 32 || (PL && IS == 16), "HL: split t0 of 32 channels (PL: 16)");
+    static constexpr int PADW = HLW ? 8 : ES == 2 && (C != 128 || WIDE) ? 16 : 16 / ES;   // weight-row pad (elements)
+    static constexpr int PSTR = PL ? 8                                                     // LDS pixel stride (elements; PL: per plane)
+                                : ES != 2 ? (BNECK_F32_HL && IS == 32 ? 40 : IS + 16 / ES) : IS == 32 ? (WIDE ? 48 : 40) : IS;
+    static constexpr int K1S = KS1 * 32 + PADW, K2S = KS2 * 32 + PADW, K3S = 32 + PADW;   // weight row strides (elements)
+    static constexpr int ZP = HL ? 32 : 16;           // zero-pad elements just below ts (masked-off B fragments read them)
+    // phase-3 chunking (see phase 3): bf16 with an even number of 16-row blocks swaps row pairs
+    // into 16-B chunks; bf16 C = 16 stores 8-B quads (HALF); fp32 quads are 16-B chunks
+    // REG3: the register epilogue (C = 128 and 16). C = 64 keeps the LDS-staged epilogue: its 128-B
+    // pixels would be written as half lines by the register layout, which measured slower there
+    // (44.7 vs 43.0 us per launch with t1 in registers).
+    // (the down form's C = 64 launch measured faster with the register epilogue: 53 vs 55 us)
+    static constexpr bool REG3 = C != 64 || DN || BNECK_REG3_C64 || (ES == 4 && (BNECK_REG3_C64_F32 || BNECK_F32_LINES64));
+    static constexpr bool SWAP = REG3 && ES == 2 && NR3 % 2 == 0;
+    static constexpr int EPC = 16 / ES;               // elements per 16-B chunk
+    // HSTG (fp32 C = 64, staged epilogue): the fragment is staged one 32-channel half at a time — a
+    // pixel's half is 128 B, one whole line, so the stores stay full-line while the staging region
+    // halves (the 8 x 16 tile: 42.7 -> 39.7 KB of LDS, 3 -> 4 workgroups per CU)
+    static constexpr bool HSTG = !REG3 && ES == 4 && C == 64 && BNECK_F32_HSTG;
+    static constexpr int OSTR = (HSTG ? C / 2 : C) + EPC;    // staged epilogue: row stride (16-B padded)
+    // KEEPF (round 4): the fp32 C = 128 forms keep their residual too. One workgroup per CU (LDS), so
+    // 256 VGPRs per lane: the 96 of the kept x replace the 64 of the residual ring. A lane's k-step s
+    // chunk holds channels 32 s + 8 kq .. + 7 as two quads; phase 3 wants quad 16 r + 4 kq .. + 3 of
+    // row block r: a row swap then a half swap per dword gather rows 2 s and 2 s + 1 (as in bf16)
+    static constexpr bool KEEPF = BNECK_KEEP_F32 && !DN && ES == 4 && (!ASYM || BNECK_KEEP_F32_ASYM) && C == 128 && REG3 && !SWAP;
+    static constexpr bool KEEP = (BNECK_KEEP && !DN && ES == 2 && (!ASYM || BNECK_KEEP_ASYM) && (SWAP || !REG3) && (C != 64 || BNECK_KEEP_C64) &&
+                                  NF2 * KS1 * 4 <= (C == 128 ? 48 : 32)) || KEEPF;   // kept VGPRs within the occupancy budget
+    // otile (class fusion) pixel stride (elements): 80 B (fp32) / 48 B — 5 / 3 16-B units, so the 16-B reads
+    // of any 16 consecutive pixels fall in distinct bank groups
+    static constexpr int OPS = ES == 4 ? 20 : 24;
+
+    // ---- the LDS map (byte offsets into the dynamic allocation) ----
+    // the three (asymmetric: four) weight matrices, rows of K?S elements. They start at 0 and follow each other
+    // in whole 16-B slots: the LDS-DMA staging addresses slot q of the run as smem + 16 q
+    static constexpr int NP1 = NR1 * 16;
+    static constexpr int W1 = 0, W2 = W1 + NP1 * K1S * ES, W2B = W2 + NP1 * K2S * ES, W3 = W2B + (ASYM ? NP1 * K2S * ES : 0);
+    // the per-channel epilogue constants, k = 0 .. 8: b1 s1 b2 s2 b2b s2b (NP1 floats each), b3 s3 s_out (C each)
+    static constexpr int CONSTS = W3 + C * K3S * ES;
+    static constexpr int cst_len(int k) { return k < 6 ? NP1 : C; }   // floats of array k
+    static constexpr int cst(int k) { return k == 0 ? CONSTS : cst(k - 1) + cst_len(k - 1) * 4; }
+    static constexpr int ZPAD = cst(9), TS = ZPAD + ZP * ES;
+    // the ts region: t0 (PL: its hi plane, then its lo plane), overwritten by t1a / t1, then by the staged
+    // epilogue's NW fragments of 16 rows (REG3 off), then by the launch's NW range maxima (fp32)
+    static constexpr int PLO = PL ? HR * PSTR : 0;    // PL: the lo plane's offset from the hi plane (elements)
+    static constexpr int T0_ELEMS = HR * PSTR + PLO, STAGE_ELEMS = REG3 ? 0 : NW * 16 * OSTR;
+    static constexpr int TS_ELEMS = T0_ELEMS > STAGE_ELEMS ? T0_ELEMS : STAGE_ELEMS;
+    // whatever follows starts past all of it. fp32 asymmetric: WMX, NW per-wave max |t1a| slots. Class fusion:
+    // the tile's block output, the class weights as [8 (block, tap)][64 lanes] 16-B slots (fp32: the hi parts,
+    // then a plane of the lo parts), the class bias (64 rows), per-wave tile maxima
+    static constexpr int WMX = TS + TS_ELEMS * ES, OTILE = WMX;
+    static constexpr int CWL = OTILE + (CLS ? NPX * OPS * ES : 0), CBL = CWL + (CLS ? (ES == 4 ? 1024 : 512) * 16 : 0);
+    static constexpr int CMX = CBL + 64 * 4;
+    static constexpr int END = CLS ? CMX + NW * 4 : ASYM && ES == 4 ? WMX + NW * 4 : WMX;
+    // Two forms ask for more than their map ends at, as their launches always have: the host formula this map
+    // replaced sized the 2-byte down C = 64 form for a staged epilogue it does not have, and the fp32
+    // asymmetric C = 64 form (built; no ENet block uses it) for the HL zero pad. Kept so that no launch's LDS
+    // size moved when the map came in; dropping them is a change to measure on its own
+    static constexpr int SPARE = (DN && C == 64 && ES == 2 && NW * 16 * (C + EPC) > TS_ELEMS ? (NW * 16 * (C + EPC) - TS_ELEMS) * ES : 0) +
+                                 ((HLW ? 32 : 16) - ZP) * ES;
+    static constexpr int LDS_BYTES = END + SPARE;
+    static_assert(K1S * ES % 16 == 0 && K2S * ES % 16 == 0 && K3S * ES % 16 == 0, "weight rows are whole 16-B slots");
+    static_assert(CONSTS % 16 == 0 && NP1 * 4 % 16 == 0 && C * 4 % 16 == 0 && ZPAD % 16 == 0 && TS % 16 == 0 && WMX % 16 == 0 &&
+                  CWL % 16 == 0 && CBL % 16 == 0 && CMX % 16 == 0, "every region starts on a 16-B boundary");
+    static_assert(!ASYM || NPA * PSTR <= T0_ELEMS, "t1a fits in the t0 region");
+    static_assert(NW * 4 <= TS_ELEMS * ES, "the range maxima fit in the ts region");
+    static_assert(!(ASYM && ES == 4 && CLS), "WMX and OTILE are the same bytes");
+    static_assert(LDS_BYTES <= 160 * 1024, "a CU has 160 KB of LDS");
+};
 
 int bneck_variants(int C) { return C == 128 ? 6 : C == 16 ? 2 : 3; }   // C128 variant 5: bneck2_kernels.hip (fp32)
-
-void bneck_shape(int C, int v, int &th, int &tw, int &nw, int *rd) {
-    if (C == 128 && v == BNECK2_V) { th = 16; tw = 16; nw = 16; if (rd) *rd = 0; return; }
-#define BS_CASE(CC, VV) if (C == CC && v == VV) { th = BShape<CC, VV>::TH; tw = BShape<CC, VV>::TW; nw = BShape<CC, VV>::NW; if (rd) *rd = BShape<CC, VV>::RD; return; }
-    BS_CASE(128, 0) BS_CASE(128, 1) BS_CASE(128, 2) BS_CASE(128, 3) BS_CASE(128, 4) BS_CASE(64, 0) BS_CASE(64, 1) BS_CASE(64, 2) BS_CASE(16, 0) BS_CASE(16, 1)
-#undef BS_CASE
-    th = tw = nw = 0;
-    if (rd) *rd = 0;
-}
 
 // CI > 0: the DOWNSAMPLING bottleneck with a CI-channel input at twice the
 // output resolution: the projection is the 2x2 stride-2 conv (K = 4 CI), the middle conv the block's
@@ -160,10 +291,7 @@ void bneck_shape(int C, int v, int &th, int &tw, int &nw, int *rd) {
 // CI >= 32, two taps in-lane + one v_permlane32_swap for CI = 16) and leaves the pooled values in a
 // small global scratch (a.pool) that phase 3 reads back as its residual (L2 hits).
 // fp32 (parity mode): registers unconstrained (LDS bounds the C = 64 / 128 forms first), except C = 16,
-// held to 4 waves per SIMD (5 spilled with the split t0 storage below; unconstrained: 16 AGPRs on top of 91 VGPRs)
-#ifndef BNECK_F32_SPLIT_T0
-#define BNECK_F32_SPLIT_T0 1
-#endif
+// held to 4 waves per SIMD (5 spilled with the split t0 storage; unconstrained: 16 AGPRs on top of 91 VGPRs)
 #ifndef BNECK_F32_OCC16
 #define BNECK_F32_OCC16 4   // (5 spilled 32 B with the split t0: 102.0 vs 90.8 us per launch at 4)
 #endif
@@ -193,12 +321,12 @@ template <typename T, int C, bool ASYM, int V, bool TR, int CI, bool SCL, int FC
 __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     using Raw = typename Tr<T>::Raw;
     using WRaw = typename WTr<T>::Raw;   // weight operand (fp32 mode: split-f16 parts)
-    constexpr int TH = BShape<C, V>::TH, TW = BShape<C, V>::TW, NW = BShape<C, V>::NW, NT = NW * 64;
-    constexpr int I = CI > 0 ? CI / 4 : C / 4;      // internal channels (ENet: input / 4)
-    constexpr int IS = I < 8 ? 8 : I;                 // stored internal channels (8-channel groups)
-    constexpr int NR1 = (I + 15) / 16;                // 16-row fragments of t0 / t1
-    constexpr int NR3 = C / 16;                       // 16-row fragments of out
-    constexpr bool DN = CI > 0;                       // (I above already depends on it)
+    // the form: shape, layout choices and the LDS map (BneckForm above); what follows here is the body's own
+    using F = BneckForm<T, C, ASYM, V, CI, FC>;
+    constexpr int TH = F::TH, TW = F::TW, NW = F::NW, NT = F::NT, IS = F::IS, NR1 = F::NR1, NR3 = F::NR3;
+    constexpr int G1 = F::G1, KS1 = F::KS1, G2 = F::G2, KS2 = F::KS2, HWW = F::HWW, HR = F::HR, NPX = F::NPX, NF2 = F::NF2, NPA = F::NPA;
+    constexpr int PSTR = F::PSTR, PLO = F::PLO, K1S = F::K1S, K2S = F::K2S, K3S = F::K3S, ZP = F::ZP, EPC = F::EPC, OSTR = F::OSTR, OPS = F::OPS;
+    constexpr bool DN = F::DN, RD = F::RD, CLS = F::CLS, HL = F::HL, PL = F::PL, REG3 = F::REG3, SWAP = F::SWAP, HSTG = F::HSTG, KEEPF = F::KEEPF, KEEP = F::KEEP;
     // output store policy (mfma_common.h): sc1 for C >= 64; the fp32 C = 64 (non-down) form streams its
     // output non-temporally (nt) — round 5, B = 64, one stream: the blocks reading it (down C128, up C16)
     // 14-18 us faster per launch. nt measured worse for the fp32 C16 form (itself +4 us), the down forms
@@ -229,30 +357,16 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #endif
     constexpr int OAUX = OUT_AUX_SEL(NTO ? 2 : (sizeof(T) == 4 && C == 128) ? BNECK_AUX_F32_C128
                                      : (C >= 64 && CI != 16) ? 16 : sizeof(T) == 4 ? BNECK_AUX_F32_LOW : 0);
-    static_assert(!DN || (!ASYM && !TR && !BShape<C, V>::RD && (CI == 16 || CI % 32 == 0)), "down mode: plain tiles");
-    constexpr int G1 = DN ? CI / 2 : C / 8, KS1 = (G1 + 3) / 4;   // proj k groups / steps (down: 4 taps x CI)
+    static_assert(!DN || (!ASYM && !TR && !RD && (CI == 16 || CI % 32 == 0)), "down mode: plain tiles");
     constexpr int CG1 = CI / 8;                       // down: 8-channel groups per tap
-    constexpr int TAPS = ASYM ? 5 : 9;
-    constexpr int G2 = TAPS * IS / 8, KS2 = (G2 + 3) / 4;
     constexpr int G3 = IS / 8;                        // expand k groups (<= 4: one step)
-    constexpr bool RD = BShape<C, V>::RD;
-    static_assert(!(RD && ASYM), "row-dilated tiles are for 3x3 blocks");
     static_assert(!WIN || (sizeof(T) == 4 && C == 128 && CI == 0 && FC < 0 && !TR && (ASYM || (RD && TW % 16 == 0))),
                   "windowed C128 forms: fp32, asymmetric plain tiles or row-dilated tiles");
     constexpr bool WRD = WIN && RD;                   // row-dilated window: fragments past its last row are skipped
-    constexpr int RY = ASYM ? 2 : 1;                  // halo rows / columns of the middle conv (tile coordinates)
-    constexpr int RX = RD ? 0 : RY;                   // row-dilated tiles span the width: no column halo
-    constexpr int HWW = TW + 2 * RX, HR = (TH + 2 * RY) * HWW;
+    constexpr int RY = F::RY, RX = F::RX;             // halo rows / columns of the middle conv (tile coordinates)
     constexpr int NF1 = (HR + 15) / 16;               // 16-pixel fragments of tile + halo
-    constexpr bool WIDE = BShape<C, V>::WIDE && !ASYM;
-    constexpr int PADW = bneck_padw((int)sizeof(T), C, WIDE, CI > 0);   // weight-row pad (elements)
-    constexpr bool PL = bneck_pl((int)sizeof(T), C, CI > 0) && !ASYM;  // fp32 C = 64: t0 as hi / lo planes
-    constexpr int PSTR = PL ? 8 : bneck_pstr((int)sizeof(T), IS, WIDE);  // LDS pixel stride (elements; PL: per plane)
-    constexpr int NPX = TH * TW;
-    constexpr int NFT = (NPX + 15) / 16;              // 16-pixel fragments of the tile
-    constexpr int NF2 = (NFT + NW - 1) / NW;          // ... per wave (the last may be partial / absent)
+    constexpr int NFT = (NPX + 15) / 16;              // 16-pixel fragments of the tile (NF2 per wave: the last may be partial / absent)
     constexpr int TWA = TW + 4;                       // asymmetric: width of t1a (the 1x5's halo)
-    constexpr int NPA = TH * TWA;
     constexpr int NFA = (NPA + 15) / 16;
     constexpr int NF2A = (NFA + NW - 1) / NW;
 #ifndef BNECK_CH1_K2
@@ -267,28 +381,6 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #ifndef BNECK_ASYM_UNROLL
 #define BNECK_ASYM_UNROLL 1    // k-steps of the asymmetric 5x1 / 1x5 passes unrolled together (A/B knob)
 #endif
-#ifndef BNECK_REG3_C64
-#define BNECK_REG3_C64 0
-#endif
-// fp32 (parity mode) C = 64 with the register epilogue: no staging region, so the LDS footprint is the
-// halo's (8 x 16 tile: 42.7 -> 39.7 KB, 3 -> 4 workgroups per CU); its quads are 16-B chunks already.
-// Measured slower (round 3: 94.1 -> 104.7 us per launch: a pixel's 256 B leave as four 64-B pieces)
-// fp32 C = 64 (non-down) with the register epilogue AND whole-line stores (LINES below; round 6, A/B knob):
-// the residual is loaded in the same line layout and traded back with the same DPP row rotation.
-// Bit-identical (44 fp32 parity cases) but measured slower: 8 x 16 138.8 -> 147.5 us per 64-frame launch
-// (124 VGPRs, no spills; the half-staged LDS epilogue, HSTG, stays)
-#ifndef BNECK_F32_LINES64
-#define BNECK_F32_LINES64 0
-#endif
-#ifndef BNECK_REG3_C64_F32
-#define BNECK_REG3_C64_F32 0
-#endif
-// fp32 C = 64: the staged epilogue one 32-channel half at a time (HSTG below). Measured (round 3, fp32,
-// B = 32): the 8 x 16 form 94.2 -> 89.4 us per launch (3 -> 4 workgroups per CU), fp32 bench
-// 13,890 -> 14,065-14,095 frames/s; bit-identical (GPU-tested)
-#ifndef BNECK_F32_HSTG
-#define BNECK_F32_HSTG 1
-#endif
 #ifndef BNECK_CH1_C64
 #define BNECK_CH1_C64 6   // the symmetric 16x16 C64 form: all of a wave's 5-6 phase-1 fragments in one round trip (37.3 -> 36.0 us)
 #endif
@@ -300,40 +392,14 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #endif
     constexpr int CH1 = KS1 >= 8 ? (sizeof(T) == 4 ? BNECK_CH1_K8_F32 : BNECK_CH1_K8) : KS1 >= 4 ? (NF1 + NW - 1) / NW
                     : KS1 == 2 ? (C == 64 && V == 0 && !DN && !ASYM ? BNECK_CH1_C64 : BNECK_CH1_K2) : 8;   // phase-1 fragments whose loads fly together
-    // phase-3 chunking (see phase 3): bf16 with an even number of 16-row blocks swaps row pairs
-    // into 16-B chunks; bf16 C = 16 stores 8-B quads (HALF); fp32 quads are 16-B chunks
-    // REG3: the register epilogue (C = 128 and 16). C = 64 keeps the LDS-staged epilogue: its 128-B
-    // pixels would be written as half lines by the register layout, which measured slower there
-    // (44.7 vs 43.0 us per launch with t1 in registers).
-    // (the down form's C = 64 launch measured faster with the register epilogue: 53 vs 55 us)
-    constexpr bool REG3 = C != 64 || DN || BNECK_REG3_C64 || (sizeof(T) == 4 && (BNECK_REG3_C64_F32 || BNECK_F32_LINES64));
-    constexpr bool SWAP = REG3 && sizeof(T) == 2 && NR3 % 2 == 0;
     constexpr bool HALF = REG3 && sizeof(T) == 2 && NR3 % 2 != 0;
-    constexpr int EPC = 16 / (int)sizeof(T);          // elements per 16-B chunk
     constexpr int CPP = C / EPC;                      // 16-B chunks per pixel
     constexpr int CPF = 16 * CPP;                     // (staged) 16-B chunks of one 16-pixel fragment
     constexpr int CPL = (CPF + 63) / 64;              // ... per lane
-    // HSTG (fp32 C = 64, staged epilogue): the fragment is staged one 32-channel half at a time — a
-    // pixel's half is 128 B, one whole line, so the stores stay full-line while the staging region
-    // halves (the 8 x 16 tile: 42.7 -> 39.7 KB of LDS, 3 -> 4 workgroups per CU)
-    constexpr bool HSTG = !REG3 && sizeof(T) == 4 && C == 64 && BNECK_F32_HSTG;
-    constexpr int OSTR = (HSTG ? C / 2 : C) + EPC;    // staged epilogue: row stride (16-B padded)
     constexpr int RQ3 = !REG3 ? CPL : SWAP ? NR3 / 2 : NR3;   // residual chunks per lane per fragment
     static_assert(TW % 16 == 0, "a fragment is a run of one tile row");
 #ifndef BNECK_NBE
 #define BNECK_NBE -1     // border fragments loaded with the kept ones (-1: per form, see phase 1)
-#endif
-#ifndef BNECK_KEEP
-#define BNECK_KEEP 1
-#endif
-    // KEEP: the residual is the block input phase 1 already loaded. Phase 1 then walks the tile's
-    // interior as phase 3's fragments (a run of one tile row, on the wave that will expand it) and the
-    // halo border separately, and each wave keeps its interior fragments' x in registers through
-    // phase 2 instead of re-reading them (an L2 / Infinity-Cache round trip per fragment; PMC: the
-    // C128 launches fetched 1.67x their compulsory bytes with the re-read). 2-byte storage, symmetric
-    // plain blocks, with the staged (C = 64) or the row-pair-swapped (C = 128) epilogue.
-#ifndef BNECK_GLDS
-#define BNECK_GLDS 1
 #endif
 #ifndef BNECK_CONST_GLDS
 #define BNECK_CONST_GLDS 1   // epilogue constants by LDS-DMA: 0 off, 1 for C != 128 (C64 38.0 -> 36.5 us; C128 23.1 -> 23.5), 2 all
@@ -341,34 +407,6 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #ifndef BNECK_GLDS_PARTIAL
 #define BNECK_GLDS_PARTIAL 1   // KEEP: the first tile waits for the weights only, not for its x loads
 #endif
-    constexpr bool GLDS = BNECK_GLDS;                 // weights staged by global_load_lds (see the staging)
-#ifndef BNECK_KEEP_ASYM
-// the asymmetric form keeps its residual too (round 4: with the single-pass 5x1 it spills 3 VGPRs and
-// runs 26.7 vs 26.5 us per launch re-reading, i.e. equal, for ~25 MB less HBM traffic per launch;
-// round 3, before that rewrite, it had spilled more and run 26.2 -> 27.2 us)
-#define BNECK_KEEP_ASYM 1
-#endif
-#ifndef BNECK_KEEP_C64
-// C = 64, 2-byte: the residual kept (16 x 16 and 8 x 16 tiles; the 20 x 16 tile's five fragments per wave
-// exceed the kept-register budget). Round 2 (B = 32, two streams) measured it slower: 41.0 vs 38.0 us per
-// launch. Round 6 (B = 64, one stream): the 20 x 16 form re-reads its residual from HBM (PMC 228 MB read
-// per launch, 1.45x the 157 MB compulsory) while 16 x 16 kept reads 160 MB (1.02x) in 70.9 vs 71.8 us —
-// so it is on, and the tile picker charges the 20 x 16 form for its re-read (bugseg_runtime.cpp)
-#define BNECK_KEEP_C64 1
-#endif
-#ifndef BNECK_KEEP_F32
-#define BNECK_KEEP_F32 1
-#endif
-#ifndef BNECK_KEEP_F32_ASYM
-#define BNECK_KEEP_F32_ASYM 1
-#endif
-    // KEEPF (round 4): the fp32 C = 128 forms keep their residual too. One workgroup per CU (LDS), so
-    // 256 VGPRs per lane: the 96 of the kept x replace the 64 of the residual ring. A lane's k-step s
-    // chunk holds channels 32 s + 8 kq .. + 7 as two quads; phase 3 wants quad 16 r + 4 kq .. + 3 of
-    // row block r: a row swap then a half swap per dword gather rows 2 s and 2 s + 1 (as in bf16)
-    constexpr bool KEEPF = BNECK_KEEP_F32 && !DN && sizeof(T) == 4 && (!ASYM || BNECK_KEEP_F32_ASYM) && C == 128 && REG3 && !SWAP;
-    constexpr bool KEEP = (BNECK_KEEP && !DN && sizeof(T) == 2 && (!ASYM || BNECK_KEEP_ASYM) && (SWAP || !REG3) && (C != 64 || BNECK_KEEP_C64) &&
-                           NF2 * KS1 * 4 <= (C == 128 ? 48 : 32)) || KEEPF;   // kept VGPRs within the occupancy budget
     static_assert(!KEEP || !REG3 || (KEEPF ? 2 * KS1 == RQ3 : KS1 == RQ3), "kept x: one 16-B chunk per k-step and row pair");
 #ifndef BNECK_EARLY_FREE
 #define BNECK_EARLY_FREE 0   // A/B knob, off: bit-identical (GPU parity green) but measured neutral to slower (round 5:
@@ -422,27 +460,13 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     // the bytes saved buy little, while the out tile and class weights in LDS (fp32 63.5 KB per workgroup:
     // 2 instead of 4 per CU) and the class phase's serial 32x32 MFMA chains behind a per-tile barrier cost
     // the bottleneck its latency hiding. Opt-in (BUGSEG_CLS_FUSE=1, bugseg_runtime.cpp Plan::cls_ok).
-    constexpr bool CLS = FC >= 0;
     static_assert(!CLS || (C == 16 && !ASYM && !DN && !TR && REG3 && !KEEP && !SWAP && TH == 16 && TW == 16 && NW == 4),
                   "class fusion: the 16 x 16 C16 form");
-    // otile pixel stride (elements): 80 B (fp32) / 48 B — 5 / 3 16-B units, so the 16-B reads of any 16
-    // consecutive pixels fall in distinct bank groups
-    constexpr int OPS = sizeof(T) == 4 ? 20 : 24;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // fp32 (parity mode): t0 / t1a live in LDS as split-f16 parts (mfma_common.h st4s: the weights'
     // layout, 32 B per 8 channels as the f32 values take), split once when written rather than at every
     // one of the middle conv's 9 (asymmetric: 5 + 5) operand reads. Bit-identical (the same parts).
-    using SRaw = typename std::conditional<sizeof(T) == 4 && BNECK_F32_SPLIT_T0, RawS, Raw>::type;
-    // HL (fp32 C = 128, round 5): in LDS a 32-element k-step of a split weight row, and a t0 / t1a pixel's
-    // 32 channels, hold the four 8-channel groups' hi parts (16 B each) and then their lo parts, instead of
-    // hi + lo per group — so each of a lane's two 16-B reads is 4 dwords at 4 kq dwords apart, as in bf16,
-    // and rows of 8 / 40 dwords mod 64 make every ds_read_b128 lane group conflict-free (SQ: 41% of the
-    // LDS cycles of these forms were bank conflicts with 32-B groups). The weight staging permutes the
-    // 16-B chunks (the packed matrices in HBM keep the shared layout); the same parts feed the same products
-    constexpr bool HL = bneck_hl((int)sizeof(T), C, CI > 0) && !(C == 64 && ASYM);   // (no C64 asymmetric block in ENet)
-    static_assert(!HL || (BNECK_F32_SPLIT_T0 && (IS == 32 || (PL && IS == 16)) && BNECK_GLDS), "HL: split t0 of 32 channels (PL: 16), LDS-DMA staging");
-    constexpr int PLO = PL ? HR * PSTR : 0;           // PL: the lo plane's offset from the hi plane (elements)
-    constexpr int ZP = HL ? 32 : 16;                  // zero-pad elements below ts
+    using SRaw = typename std::conditional<sizeof(T) == 4, RawS, Raw>::type;
     auto st4t = [](T *p, int ch, float4 v) {
         if constexpr (PL) {
             // p = plane pixel base + ch: hi parts of channels ch .. ch + 3 into the hi plane, lo into the lo plane
@@ -457,7 +481,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             *reinterpret_cast<f16x4 *>(b) = (f16x4){hh[0], hh[1], hh[2], hh[3]};
             *reinterpret_cast<f16x4 *>(b + PLO * 4) = (f16x4){ll[0], ll[1], ll[2], ll[3]};
         } else if constexpr (HL) st4hl(reinterpret_cast<float *>(p) - ch, ch, v);
-        else if constexpr (sizeof(T) == 4 && BNECK_F32_SPLIT_T0) st4s(reinterpret_cast<float *>(p) - (ch & 7), ch & 7, v);
+        else if constexpr (sizeof(T) == 4) st4s(reinterpret_cast<float *>(p) - (ch & 7), ch & 7, v);
         else st4(p, v);
     };
 
@@ -474,7 +498,6 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably uniform: scalar fragment math
     // first channel of this lane's phase-3 chunk t
     auto chunk_ch = [&](int t) -> int { return SWAP ? (2 * t + (kq & 1)) * 16 + 8 * (kq >> 1) : t * 16 + kq * 4; };
-    const int K1S = KS1 * 32 + PADW, K2S = KS2 * 32 + PADW, K3S = 32 + PADW;
     // A operand: group kq of the k-step at p (a weight row + 32 s)
     auto ldw = [&](WRaw &r, const T *p) {
         if constexpr (HL) {
@@ -484,100 +507,54 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             ld8(r, p + kq * 8);
         }
     };
-    T *w1 = reinterpret_cast<T *>(smem);
-    T *w2 = w1 + NR1 * 16 * K1S;
-    T *w2b = w2 + NR1 * 16 * K2S;                     // asymmetric second conv (1x5)
-    T *w3 = w2b + (ASYM ? NR1 * 16 * K2S : 0);
-    // per-channel epilogue constants live in LDS too: a global load per use was most of this
-    // kernel's vector-memory instructions and a latency the epilogues waited on
-    constexpr int NP1 = NR1 * 16;
-    float *cb1 = reinterpret_cast<float *>(w3 + C * K3S), *cs1 = cb1 + NP1, *cb2 = cs1 + NP1, *cs2 = cb2 + NP1;
-    float *cb2b = cs2 + NP1, *cs2b = cb2b + NP1, *cb3 = cs2b + NP1, *cs3 = cb3 + C, *cso = cs3 + C;
-    // 16 zero elements: masked-off B fragments read them (an address select, not a divergent branch)
-    T *zpad = reinterpret_cast<T *>(cso + C);
-    T *ts = zpad + ZP;                                // t0 / t1a / t1 region
-    float *wmx = reinterpret_cast<float *>(ts + HR * PSTR);   // fp32 asymmetric: NW per-wave max |t1a| slots
-    // CLS: the tile's block output, the class weights as [8 (block, tap)][64 lanes] 16-B slots (fp32: the
-    // hi parts, then a plane of the lo parts), the class bias (64 rows), per-wave tile maxima (fp32)
-    T *otile = ts + HR * PSTR;
-    uint4 *cwl = reinterpret_cast<uint4 *>(otile + (CLS ? NPX * OPS : 0));
-    float *cbl = reinterpret_cast<float *>(cwl + (CLS ? (sizeof(T) == 4 ? 1024 : 512) : 0));
-    float *cmx = cbl + 64;
+    // the regions of the LDS map (BneckForm): the weights, ...
+    T *w1 = reinterpret_cast<T *>(smem + F::W1), *w2 = reinterpret_cast<T *>(smem + F::W2);
+    T *w2b = reinterpret_cast<T *>(smem + F::W2B), *w3 = reinterpret_cast<T *>(smem + F::W3);   // w2b: asymmetric second conv (1x5)
+    // ... the per-channel epilogue constants (in LDS too: a global load per use was most of this
+    // kernel's vector-memory instructions and a latency the epilogues waited on), ...
+    constexpr int NP1 = F::NP1;
+    // (each pointer stepped from the one before by the map's array lengths, not taken from smem: how the
+    // compiler allocates the registers of the C = 16 / 64 forms follows the shape of this arithmetic)
+    constexpr int LI = F::cst_len(0), LO = F::cst_len(6);   // floats per array: the internal layers' (NP1), the output's (C)
+    float *cb1 = reinterpret_cast<float *>(smem + F::cst(0)), *cs1 = cb1 + LI, *cb2 = cs1 + LI, *cs2 = cb2 + LI;
+    float *cb2b = cs2 + LI, *cs2b = cb2b + LI, *cb3 = cs2b + LI, *cs3 = cb3 + LO, *cso = cs3 + LO;
+    // ... the zero pad (masked-off B fragments read it: an address select, not a divergent branch), the
+    // t0 / t1a / t1 region, and what follows it: the fp32 asymmetric max |t1a| slots or the class fusion's regions
+    T *zpad = reinterpret_cast<T *>(smem + F::ZPAD), *ts = reinterpret_cast<T *>(smem + F::TS);
+    float *wmx = reinterpret_cast<float *>(smem + F::WMX), *cbl = reinterpret_cast<float *>(smem + F::CBL), *cmx = reinterpret_cast<float *>(smem + F::CMX);
+    T *otile = reinterpret_cast<T *>(smem + F::OTILE);
+    uint4 *cwl = reinterpret_cast<uint4 *>(smem + F::CWL);
     {
-        // C = 16 (small weights, many short tiles): every load of the staging is issued before the
-        // first LDS store (one L2 round trip at kernel start instead of one per 16-B chunk a thread
-        // copies). Measured slower for C = 64 / 128 (48.8 / 31.8 vs 42 / 26.4 us: all workgroups
-        // requesting every weight line at once), so those keep the chunk loop below.
-        constexpr int CPR1 = KS1 * 32 * (int)sizeof(T) / 16, CPR2 = KS2 * 32 * (int)sizeof(T) / 16, CPR3 = 32 * (int)sizeof(T) / 16;
-        constexpr int N1 = NR1 * 16 * CPR1, N2 = NR1 * 16 * CPR2, N3 = C * CPR3;
-        constexpr int TOT = N1 + N2 * (ASYM ? 2 : 1) + N3;
-        constexpr int PER = (TOT + NT - 1) / NT;
-        uint4 buf[C == 16 ? PER : 1];
-        auto locate = [&](int i, const uint4 *&src, unsigned char *&dst) -> bool {
-            int r, c;
-            if (i < N1) { r = i / CPR1; c = i - r * CPR1; src = (const uint4 *)a.w1 + i; dst = (unsigned char *)(w1 + r * K1S) + c * 16; return true; }
-            i -= N1;
-            if (i < N2) { r = i / CPR2; c = i - r * CPR2; src = (const uint4 *)a.w2 + i; dst = (unsigned char *)(w2 + r * K2S) + c * 16; return true; }
-            i -= N2;
-            if (ASYM && i < N2) { r = i / CPR2; c = i - r * CPR2; src = (const uint4 *)a.w2b + i; dst = (unsigned char *)(w2b + r * K2S) + c * 16; return true; }
-            if (ASYM) i -= N2;
-            if (i < N3) { r = i / CPR3; c = i - r * CPR3; src = (const uint4 *)a.w3 + i; dst = (unsigned char *)(w3 + r * K3S) + c * 16; return true; }
-            return false;
-        };
-        if constexpr (GLDS) {
-            // global_load_lds: the weight region of LDS is a run of 16-B slots (rows of K?S elements:
-            // CPR? data chunks + the pad); each wave instruction fills 64 consecutive slots, a lane
-            // fetching its slot's chunk (pad slots re-read the row's first chunk: never read). No
-            // VGPR round trip and nothing waited for here: the loads fly with the first tile's x
-            // loads and the first tile waits for all of them before its first barrier.
-            (void)buf;
-            constexpr int ES = (int)sizeof(T);
-            constexpr int SR1 = (KS1 * 32 + PADW) * ES / 16, SR2 = (KS2 * 32 + PADW) * ES / 16, SR3 = (32 + PADW) * ES / 16;
-            constexpr int S1 = NR1 * 16 * SR1, S2 = NR1 * 16 * SR2, S3 = C * SR3;
-            constexpr int NSL = S1 + S2 * (ASYM ? 2 : 1) + S3;
-            static_assert((KS1 * 32 + PADW) * ES % 16 == 0 && (KS2 * 32 + PADW) * ES % 16 == 0 && (32 + PADW) * ES % 16 == 0,
-                          "weight rows are whole 16-B slots");
-            for (int base = wave * 64; base < NSL; base += NT) {      // wave-uniform
-                const int q = base + lane;
-                const uint4 *src;
-                auto pick = [&](const void *w, int k, int SR, int CPR) {   // slot k of one matrix
-                    const int r = k / SR, c = k - r * SR;
-                    // HL: LDS chunk d of each 8-chunk k-step is hi (d < 4) / lo part of group d % 4, packed
-                    // chunk 2 (d % 4) + (d >= 4)
-                    const int cs = HL ? (c & ~7) | ((c & 7) < 4 ? 2 * (c & 7) : 2 * (c & 3) + 1) : c;
-                    src = (const uint4 *)w + r * CPR + (c < CPR ? cs : 0);
-                };
-                constexpr int O3 = S1 + S2 * (ASYM ? 2 : 1);   // first slot of w3
-                if (q < S1) pick(a.w1, q, SR1, CPR1);
-                else if (q < S1 + S2) pick(a.w2, q - S1, SR2, CPR2);
-                else if (q < O3) pick(a.w2b, q - S1 - S2, SR2, CPR2);
-                else pick(a.w3, q - O3, SR3, CPR3);
-                if (base + lane < NSL)
-                    __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)src,
-                                                     (__attribute__((address_space(3))) void *)(smem + (size_t)base * 16), 16, 0, 0);
-            }
-        } else if constexpr (C == 16) {
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                const uint4 *src;
-                unsigned char *dst;
-                if (locate(tid + k * NT, src, dst)) buf[k] = *src;
-            }
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                const uint4 *src;
-                unsigned char *dst;
-                if (locate(tid + k * NT, src, dst)) *reinterpret_cast<uint4 *>(dst) = buf[k];
-            }
-        } else {
-            (void)buf;
-            for (int i = tid; i < TOT; i += NT) {
-                const uint4 *src;
-                unsigned char *dst;
-                if (locate(i, src, dst)) *reinterpret_cast<uint4 *>(dst) = *src;
-            }
+        // The weights by LDS-DMA (global_load_lds): the weight region of LDS is a run of 16-B slots (rows of
+        // K?S elements: CPR? data chunks + the pad); each wave instruction fills 64 consecutive slots, a lane
+        // fetching its slot's chunk (pad slots re-read the row's first chunk: never read). No VGPR round trip
+        // and nothing waited for here: the loads fly with the first tile's x loads and the first tile waits
+        // for all of them before its first barrier. (It replaced a load -> LDS store copy per thread, which
+        // the HL layouts, permuted here for free, never had.)
+        constexpr int ES = F::ES;
+        constexpr int CPR1 = KS1 * 32 * ES / 16, CPR2 = KS2 * 32 * ES / 16, CPR3 = 32 * ES / 16;   // data chunks per row
+        constexpr int SR1 = K1S * ES / 16, SR2 = K2S * ES / 16, SR3 = K3S * ES / 16;               // slots per row
+        constexpr int S1 = NP1 * SR1, S2 = NP1 * SR2, O3 = F::W3 / 16, NSL = F::CONSTS / 16;       // O3: first slot of w3
+        static_assert(F::W1 == 0 && F::W2 == S1 * 16 && F::W2B == (S1 + S2) * 16, "the weights are one run of slots from 0");
+        for (int base = wave * 64; base < NSL; base += NT) {      // wave-uniform
+            const int q = base + lane;
+            const uint4 *src;
+            auto pick = [&](const void *w, int k, int SR, int CPR) {   // slot k of one matrix
+                const int r = k / SR, c = k - r * SR;
+                // HL: LDS chunk d of each 8-chunk k-step is hi (d < 4) / lo part of group d % 4, packed
+                // chunk 2 (d % 4) + (d >= 4)
+                const int cs = HL ? (c & ~7) | ((c & 7) < 4 ? 2 * (c & 7) : 2 * (c & 3) + 1) : c;
+                src = (const uint4 *)w + r * CPR + (c < CPR ? cs : 0);
+            };
+            if (q < S1) pick(a.w1, q, SR1, CPR1);
+            else if (q < S1 + S2) pick(a.w2, q - S1, SR2, CPR2);
+            else if (q < O3) pick(a.w2b, q - S1 - S2, SR2, CPR2);
+            else pick(a.w3, q - O3, SR3, CPR3);
+            if (base + lane < NSL)
+                __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)src,
+                                                 (__attribute__((address_space(3))) void *)(smem + (size_t)base * 16), 16, 0, 0);
         }
-        if constexpr (GLDS && (BNECK_CONST_GLDS == 2 || (BNECK_CONST_GLDS == 1 && C != 128))) {
+        if constexpr (BNECK_CONST_GLDS == 2 || (BNECK_CONST_GLDS == 1 && C != 128)) {
             // the epilogue constants by LDS-DMA as well (one dword per lane, 64 per instruction,
             // spread over the waves): a plain load -> LDS store here would wait (vmcnt, in order)
             // for the weight DMA issued above and serialise the staging ahead of the x loads
@@ -901,7 +878,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
         // barrier makes every wave's visible); KEEP issues its x loads ahead of that wait
         const bool first = it == slot;
         if constexpr (!KEEP) {
-            if (GLDS && first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();   // weights staged (first tile) / previous tile done with ts (and the patch)
             if constexpr (F32 && !SCL) {
                 // the range words arrived with the loads issued before them: bail out to the scaled body
@@ -995,7 +972,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             // waits for the weight LDS-DMA only: it was issued before this wave's x loads, and vmcnt
             // retires in order, so "at most nld outstanding" leaves the x loads in flight for the
             // projections to consume one fragment at a time
-            if (GLDS && first) {
+            if (first) {
                 int nld = 0;
                 constexpr int LPS = sizeof(T) == 4 ? 2 : 1;   // 16-B loads per k-step chunk (fp32: two)
 #pragma unroll
@@ -1802,72 +1779,85 @@ extern "C" int bugseg_debug_set_stamps(void *p) {
 }
 #endif
 
-// the C = 64 2-byte forms that keep their residual in registers (BNECK_KEEP_C64): all but 20 x 16
-bool bneck_keeps_c64(int prec, int v) { return BNECK_KEEP_C64 && prec != PREC_F32 && v != 1; }
+// ---- the built forms -----------------------------------------------------------------------------
+// Every kernel this file instantiates is named once, in bneck_forms() below; an entry carries what the
+// launchers and the runtime's tile picker ask about a form, read off its BneckForm. A form that is not in the
+// table is not built.
+struct BneckEntry {
+    int prec, C, asym, v, tr, cin, win, lut;   // the key (lut: the class-fused form's LUT kind, else -1)
+    const void *fun;
+    int threads, lds, th, tw, nw, rd, keep;
+};
+template <typename T> constexpr int prec_of = std::is_same<T, float>::value ? PREC_F32 : std::is_same<T, __bf16>::value ? PREC_BF16 : PREC_F16;
+template <typename F> static BneckEntry entry(int prec, int C, int asym, int v, int tr, int cin, int win, int lut, const void *fun) {
+    return {prec, C, asym, v, tr, cin, win, lut, fun, F::NT, F::LDS_BYTES, F::TH, F::TW, F::NW, F::RD, F::KEEP};
+}
+template <typename T, int C, bool ASYM, int V, bool TR = false, int CI = 0> static BneckEntry plain() {
+    return entry<BneckForm<T, C, ASYM, V, CI>>(prec_of<T>, C, ASYM, V, TR, CI, 0, -1, (const void *)bneck_kernel<T, C, ASYM, V, TR, CI>);
+}
+template <int V, bool ASYM> static BneckEntry windowed() {   // (fp32 C = 128)
+    return entry<BneckForm<float, 128, ASYM, V>>(PREC_F32, 128, ASYM, V, 0, 0, 1, -1, (const void *)bneck_win_kernel<float, 128, ASYM, V>);
+}
+template <typename T, int FC> static BneckEntry fused_cls() {   // (C = 16, 16 x 16)
+    return entry<BneckForm<T, 16, false, 0, 0, FC>>(prec_of<T>, 16, 0, 0, 0, 0, 0, FC, (const void *)bneck_cls_kernel<T, FC>);
+}
+template <typename T> static void add_forms(std::vector<BneckEntry> &t) {
+    // every plain tile shape, symmetric and asymmetric
+    t.insert(t.end(), {plain<T, 128, false, 0>(), plain<T, 128, true, 0>(), plain<T, 128, false, 1>(), plain<T, 128, true, 1>(),
+                       plain<T, 128, false, 4>(), plain<T, 128, true, 4>(), plain<T, 64, false, 0>(), plain<T, 64, true, 0>(),
+                       plain<T, 64, false, 1>(), plain<T, 64, true, 1>(), plain<T, 64, false, 2>(), plain<T, 64, true, 2>(),
+                       plain<T, 16, false, 0>(), plain<T, 16, true, 0>()});
+    // C = 16, 20 x 16: 2-byte storage only (the fp32 instance spills 9 VGPRs)
+    if constexpr (sizeof(T) == 2) t.push_back(plain<T, 16, false, 1>());
+    // C = 128: the transposed 20 x 16 tile and the row-dilated tiles
+    t.insert(t.end(), {plain<T, 128, false, 1, true>(), plain<T, 128, false, 2>(), plain<T, 128, false, 3>()});
+    // downsampling forms: ENet's down1 (16 -> 64 at 120x160) and down2 (64 -> 128 at 60x80)
+    t.insert(t.end(), {plain<T, 64, false, 0, false, 16>(), plain<T, 128, false, 1, false, 64>()});
+    t.insert(t.end(), {fused_cls<T, 0>(), fused_cls<T, 1>(), fused_cls<T, 2>()});
+}
+static const std::vector<BneckEntry> &bneck_forms() {
+    static const std::vector<BneckEntry> table = [] {
+        std::vector<BneckEntry> t;
+        add_forms<float>(t);
+        add_forms<__bf16>(t);
+        add_forms<_Float16>(t);
+        // the row-windowed forms: asymmetric 16 x 16, 20 x 16, 8 x 16 (the small-batch form) and row-dilated 4 x 80
+        t.insert(t.end(), {windowed<0, true>(), windowed<1, true>(), windowed<4, true>(), windowed<2, false>()});
+        return t;
+    }();
+    return table;
+}
+template <typename Pred> static const BneckEntry *find_form(Pred p) {   // nullptr: no such form is built
+    for (const BneckEntry &e : bneck_forms())
+        if (p(e)) return &e;
+    return nullptr;
+}
+static const BneckEntry *bneck_form(int prec, int C, bool asym, int v, bool tr, int cin, bool win, int lut = -1) {
+    return find_form([&](const BneckEntry &e) {
+        return e.prec == prec && e.C == C && e.asym == asym && e.v == v && e.tr == tr && e.cin == cin && e.win == win && e.lut == lut;
+    });
+}
 
+void bneck_shape(int C, int v, int &th, int &tw, int &nw, int *rd) {
+    if (C == 128 && v == BNECK2_V) { th = 16; tw = 16; nw = 16; if (rd) *rd = 0; return; }
+    const BneckEntry *e = find_form([&](const BneckEntry &f) { return f.C == C && f.v == v; });   // (BShape<C, V>)
+    th = e ? e->th : 0; tw = e ? e->tw : 0; nw = e ? e->nw : 0;
+    if (rd) *rd = e ? e->rd : 0;
+}
+
+// the C = 64 2-byte forms that keep their residual in registers (BNECK_KEEP_C64): all but 20 x 16
+bool bneck_keeps_c64(int prec, int v) {
+    const BneckEntry *e = bneck_form(prec, 64, false, v, false, 0, false);
+    return e && e->keep;
+}
+
+// (neither the orientation nor the row window changes a form's LDS map, nor does the class-fused form's LUT kind)
 size_t bneck_lds_bytes(int prec, int C, bool asym, int v, int cin, bool cls) {
     if (C == 128 && v == BNECK2_V) return prec == PREC_F32 && !asym && cin == 0 ? bneck2_lds_bytes() : (size_t)1 << 30;
-    int TH, TW, NW, RD;
-    bneck_shape(C, v, TH, TW, NW, &RD);
-    const int es = prec_es(prec), pad = 16 / es;
-    const int I = cin > 0 ? cin / 4 : C / 4, IS = I < 8 ? 8 : I, NR1 = (I + 15) / 16;
-    const int KS1 = ((cin > 0 ? cin / 2 : C / 8) + 3) / 4, KS2 = ((asym ? 5 : 9) * IS / 8 + 3) / 4;
-    const int R = asym ? 2 : 1, RX = RD ? 0 : R;
-    const bool wide = bneck_wide(C, v, asym);
-    const int padw = bneck_padw(es, C, wide, cin > 0);
-    const int zp = bneck_hl(es, C, cin > 0) ? 32 : 16;
-    const size_t wts = (size_t)NR1 * 16 * (KS1 * 32 + padw) + (size_t)NR1 * 16 * (KS2 * 32 + padw) * (asym ? 2 : 1) +
-                       (size_t)C * (32 + padw);
-    const size_t halo = (size_t)(TH + 2 * R) * (TW + 2 * RX) * (bneck_pl(es, C, cin > 0) && !asym ? 16 : bneck_pstr(es, IS, wide));
-    const bool staged = C == 64 && !BNECK_REG3_C64 && !(es == 4 && (BNECK_REG3_C64_F32 || (BNECK_F32_LINES64 && cin == 0)));
-    const bool hstg = staged && es == 4 && BNECK_F32_HSTG;            // fp32 C = 64: one 32-channel half at a time
-    const size_t stage = staged ? (size_t)NW * 16 * ((hstg ? C / 2 : C) + pad) : 0;    // staged epilogue (REG3 off)
-    const size_t consts = ((size_t)6 * NR1 * 16 + 3 * (size_t)C) * sizeof(float);
-    // class fusion (C = 16): the out tile, the class weights, bias and the per-wave tile maxima
-    const size_t clsb = cls ? (size_t)TH * TW * (es == 4 ? 20 : 24) * es + (es == 4 ? 16384 : 8192) + 64 * 4 + (size_t)NW * 4 : 0;
-    return (wts + zp + (halo > stage ? halo : stage)) * es + consts +   // + the zero pad
-           (asym && es == 4 ? (size_t)NW * sizeof(float) : 0) + clsb;      // + fp32 asymmetric max slots
-}
-
-// kernel symbol of (precision, C, asym, variant, transposed); nullptr if not built
-template <typename T>
-static const void *kfun(int C, bool asym, int v, bool tr) {
-#define BK_CASE(CC, VV) \
-    if (C == CC && v == VV && !tr) return asym ? (const void *)bneck_kernel<T, CC, true, VV, false> : (const void *)bneck_kernel<T, CC, false, VV, false>;
-    BK_CASE(128, 0) BK_CASE(128, 1) BK_CASE(128, 4) BK_CASE(64, 0) BK_CASE(64, 1) BK_CASE(64, 2) BK_CASE(16, 0)
-#undef BK_CASE
-    // (2-byte storage only: the fp32 instance spills 9 VGPRs)
-    if constexpr (sizeof(T) == 2)
-        if (C == 16 && v == 1 && !tr) return asym ? nullptr : (const void *)bneck_kernel<T, 16, false, 1, false>;
-    if (C == 128 && v == 1 && tr && !asym) return (const void *)bneck_kernel<T, 128, false, 1, true>;
-    if (C == 128 && v == 2 && !tr && !asym) return (const void *)bneck_kernel<T, 128, false, 2, false>;
-    if (C == 128 && v == 3 && !tr && !asym) return (const void *)bneck_kernel<T, 128, false, 3, false>;
-    return nullptr;
-}
-// downsampling forms: ENet's down1 (16 -> 64 at 120x160) and down2 (64 -> 128 at 60x80)
-template <typename T>
-static const void *kfun_down(int C, int v, int cin) {
-    if (C == 64 && v == 0 && cin == 16) return (const void *)bneck_kernel<T, 64, false, 0, false, 16>;
-    if (C == 128 && v == 1 && cin == 64) return (const void *)bneck_kernel<T, 128, false, 1, false, 64>;
-    return nullptr;
-}
-
-static const void *bneck_fun(int prec, int C, bool asym, int v, bool tr, int cin, bool win = false) {
-    if (win) {
-        if (prec != PREC_F32 || C != 128 || tr || cin > 0) return nullptr;
-        if (asym && v == 0) return (const void *)bneck_win_kernel<float, 128, true, 0>;
-        if (asym && v == 1) return (const void *)bneck_win_kernel<float, 128, true, 1>;
-        if (asym && v == 4) return (const void *)bneck_win_kernel<float, 128, true, 4>;   // (the small-batch form)
-        if (!asym && v == 2) return (const void *)bneck_win_kernel<float, 128, false, 2>;
-        return nullptr;
-    }
-    if (cin > 0)
-        return asym || tr ? nullptr
-               : prec == PREC_BF16 ? kfun_down<__bf16>(C, v, cin)
-               : prec == PREC_F16  ? kfun_down<_Float16>(C, v, cin)
-                                   : kfun_down<float>(C, v, cin);
-    return prec == PREC_BF16 ? kfun<__bf16>(C, asym, v, tr) : prec == PREC_F16 ? kfun<_Float16>(C, asym, v, tr)
-                                                            : kfun<float>(C, asym, v, tr);
+    const BneckEntry *e = find_form([&](const BneckEntry &f) {
+        return f.prec == prec && f.C == C && f.asym == asym && f.v == v && f.cin == cin && (f.lut >= 0) == cls;
+    });
+    return e ? (size_t)e->lds : (size_t)1 << 30;
 }
 
 int bneck_slots_per_cu(const Knobs &k, int prec, int C, bool asym, int v, bool tr, int cin, bool win) {
@@ -1878,23 +1868,18 @@ int bneck_slots_per_cu(const Knobs &k, int prec, int C, bool asym, int v, bool t
         return prec == PREC_F32 && !asym && !tr && cin == 0 && k.bneck2 ? bneck2_slots_per_cu() : 0;
     }
     // (cached per device and form: launch_bneck asks on every launch; bugseg_runtime.cpp occupancy_per_cu)
-    const void *f = bneck_fun(prec, C, asym, v, tr, cin, win);
-    int th, tw, nw;
-    bneck_shape(C, v, th, tw, nw, nullptr);
-    if (!f || allow_dynamic_lds(f) != hipSuccess) return 0;
-    return occupancy_per_cu(f, nw * 64, bneck_lds_bytes(prec, C, asym, v, cin));
+    const BneckEntry *e = bneck_form(prec, C, asym, v, tr, cin, win);
+    if (!e || allow_dynamic_lds(e->fun) != hipSuccess) return 0;
+    return occupancy_per_cu(e->fun, e->threads, (size_t)e->lds);
 }
 
 hipError_t launch_bneck(const Knobs &k, int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin, bool win) {
     if (C == 128 && v == BNECK2_V)
         return prec == PREC_F32 && !asym && !a.tr && cin == 0 && !win ? launch_bneck2(k, a, s) : hipErrorInvalidValue;
-    const void *f = bneck_fun(prec, C, asym, v, a.tr != 0, cin, win);
+    const BneckEntry *f = bneck_form(prec, C, asym, v, a.tr != 0, cin, win);
     if (!f) return hipErrorInvalidValue;
-    int th, tw, nw;
-    bneck_shape(C, v, th, tw, nw, nullptr);
-    const size_t lds = bneck_lds_bytes(prec, C, asym, v, cin);
-    if (lds > 64 * 1024) {
-        hipError_t e = allow_dynamic_lds(f);
+    if (f->lds > 64 * 1024) {
+        hipError_t e = allow_dynamic_lds(f->fun);
         if (e != hipSuccess) return e;
     }
     // grid: one round of resident workgroups (each walks ntiles / grid tiles, staging its weights
@@ -1912,30 +1897,34 @@ hipError_t launch_bneck(const Knobs &k, int prec, int C, bool asym, int v, const
     int g = a.ntiles < cap ? a.ntiles : cap;
     g = (g + 7) & ~7;
     void *args[] = {const_cast<BneckArgs *>(&a)};
-    return hipLaunchKernel(f, dim3(g), dim3(nw * 64), args, lds, s);
-}
-
-template <typename T>
-static const void *kfun_cls(int lk) {
-    return lk == 1 ? (const void *)bneck_cls_kernel<T, 1> : lk == 2 ? (const void *)bneck_cls_kernel<T, 2>
-                   : (const void *)bneck_cls_kernel<T, 0>;
+    return hipLaunchKernel(f->fun, dim3(g), dim3(f->threads), args, (size_t)f->lds, s);
 }
 
 hipError_t launch_bneck_cls(const Knobs &k, int prec, const BneckArgs &a, hipStream_t s) {
     const int lk = a.lut && (a.lut_kind == 1 || a.lut_kind == 2) ? a.lut_kind : 0;
-    const void *f = prec == PREC_BF16 ? kfun_cls<__bf16>(lk) : prec == PREC_F16 ? kfun_cls<_Float16>(lk) : kfun_cls<float>(lk);
-    const size_t lds = bneck_lds_bytes(prec, 16, false, 0, 0, true);
-    if (lds > 64 * 1024) {
-        hipError_t e = allow_dynamic_lds(f);
+    const BneckEntry *f = bneck_form(prec, 16, false, 0, false, 0, false, lk);
+    if (!f) return hipErrorInvalidValue;
+    if (f->lds > 64 * 1024) {
+        hipError_t e = allow_dynamic_lds(f->fun);
         if (e != hipSuccess) return e;
     }
     // one round of resident workgroups, as launch_bneck
-    const int spc = occupancy_per_cu(f, 256, lds), n_cu = device_cus();
+    const int spc = occupancy_per_cu(f->fun, f->threads, (size_t)f->lds), n_cu = device_cus();
     const int cap = k.bneck_grid > 0 ? k.bneck_grid : spc > 0 && n_cu > 0 ? spc * n_cu : 2048;
     int g = a.ntiles < cap ? a.ntiles : cap;
     g = (g + 7) & ~7;
     void *args[] = {const_cast<BneckArgs *>(&a)};
-    return hipLaunchKernel(f, dim3(g), dim3(256), args, lds, s);
+    return hipLaunchKernel(f->fun, dim3(g), dim3(f->threads), args, (size_t)f->lds, s);
+}
+
+int bneck_form_rows(int32_t *rows, int cap) {
+    const std::vector<BneckEntry> &t = bneck_forms();
+    for (int n = 0; n < (int)t.size() && n < cap; ++n) {
+        const BneckEntry &e = t[(size_t)n];
+        const int32_t vals[FORM_COLS] = {0, e.prec, e.C, e.asym, e.v, e.tr, e.cin, e.win, e.lut, e.threads, e.lds, e.th, e.tw, e.nw, e.rd, e.keep};
+        std::copy(vals, vals + FORM_COLS, rows + (size_t)n * FORM_COLS);
+    }
+    return (int)t.size();
 }
 
 }  // namespace bugseg

@@ -208,7 +208,7 @@ bool bneck_keeps_c64(int prec, int v);
 // rd (optional): 1 for a row-dilated full-width variant (tiles_x = 1, phases = d, needs W <= tw)
 void bneck_shape(int C, int v, int &th, int &tw, int &nw, int *rd = nullptr);
 // cin > 0: the downsampling form (bneck_kernels.hip) with a cin-channel input; built for (64, v0,
-// cin 16) and (128, v1, cin 64)
+// cin 16) and (128, v1, cin 64). The form's BneckForm::LDS_BYTES; 1 << 30 for a form that is not built
 size_t bneck_lds_bytes(int prec, int C, bool asym, int v, int cin = 0, bool cls = false);
 // resident workgroups per CU (occupancy API); 0 if (C, asym, v, tr, cin) is not built (BNECK2_V: or not Knobs::bneck2)
 // win: the row-windowed form (BneckArgs::oy_end), built for fp32 C = 128 asymmetric 16 x 16 / 20 x 16 / 8 x 16
@@ -245,6 +245,11 @@ struct UpArgs {
 };
 bool up_supported(int cin, int it, int cout);
 hipError_t launch_up(int prec, int cin, int it, int cout, const UpArgs &a, hipStream_t s);
+// bugseg_debug_fused_forms (include/bugseg.h): one FORM_COLS-word row per built bottleneck / up form into
+// rows[0 .. cap) (host only); returns how many forms there are, whatever cap is
+constexpr int FORM_COLS = 16;
+int bneck_form_rows(int32_t *rows, int cap);
+int up_form_rows(int32_t *rows, int cap);
 
 // ---- preprocess / layout (prep_kernels.hip) --------------------------------------------------
 struct PreArgs {

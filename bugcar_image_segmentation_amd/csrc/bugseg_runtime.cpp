@@ -2348,6 +2348,13 @@ int bugseg_debug_tile_walk(int ntiles, int grid, int rev, int32_t *seq, size_t s
     return per;
 }
 
+int bugseg_debug_fused_forms(int32_t *rows, int n_rows) {
+    if (n_rows < 0 || (!rows && n_rows > 0)) return fail(nullptr, BUGSEG_EINVAL, "fused forms: NULL rows");
+    const int nb = bneck_form_rows(rows, n_rows);
+    const int left = n_rows > nb ? n_rows - nb : 0;
+    return nb + up_form_rows(left ? rows + (size_t)nb * FORM_COLS : nullptr, left);
+}
+
 int bugseg_debug_row_windows(int H, int W, int row0, int row1, int tile_rows_c64, int tile_rows_c16, int32_t *win) {
     (void)W;                                          // (the windows are whole rows: the width plays no part)
     if (!win) return fail(nullptr, BUGSEG_EINVAL, "NULL argument");

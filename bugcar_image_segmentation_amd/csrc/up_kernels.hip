@@ -19,26 +19,54 @@
 // channels (see to_bop). Every intermediate is rounded to the storage type exactly where the unfused
 // launches store it, and each GEMM adds its bias where the unfused launch with that row count does
 // (bias_in_acc), so the fused block is bit-identical to the unfused plan.
+#include <algorithm>
+
 #include "bugseg_internal.h"
 #include "mfma_common.h"
 
 namespace bugseg {
-
 
 // threads per workgroup: the 2-byte CIN = 128 form (46 KB of weights in LDS: 3 workgroups per CU) runs
 // 8 waves per workgroup (UP_NT128), so the weights staged once per CU serve twice the waves
 #ifndef UP_NT128
 #define UP_NT128 512
 #endif
-template <typename T, int CIN>
-__host__ __device__ constexpr int up_threads() { return sizeof(T) == 2 && CIN >= 128 ? UP_NT128 : 256; }
+// One compile-time description per form, shared by the kernel and its launcher: the workgroup size, the rows
+// of the three GEMMs and the LDS map (byte offsets of the weights of the three GEMMs and of their per-row
+// constants, and the size of the dynamic allocation).
+template <typename T, int CIN, int I, int COUT>
+struct UpForm {
+    static constexpr int ES = (int)sizeof(T);
+    static constexpr int NT = ES == 2 && CIN >= 128 ? UP_NT128 : 256;
+    static constexpr int NR1 = (COUT + I) / 16;       // GEMM 1 rows: main then e1
+    static constexpr int NR2 = 4 * I / 16;            // tconv rows (4 phases)
+    static constexpr int NR3 = COUT / 16;             // expansion rows
+    // row pads: bf16 16 elements (row strides 8 / 24 / 40 dwords mod 64: conflict-free ds_read_b128
+    // groups, bneck_kernels.hip PADW), fp32 16 B
+    // (unpadded rows with XOR-swizzled chunks for CIN = 128 measured no faster in the 2-stream bench,
+    // round 3, and were removed)
+    static constexpr int UPAD = ES == 2 ? 16 : 16 / ES;
+    static constexpr int K1S = CIN + UPAD, K2S = 32 + UPAD, K3S = 32 + UPAD;   // weight row strides (elements)
+    static constexpr int W1 = 0, W2 = W1 + NR1 * 16 * K1S * ES, W3 = W2 + NR2 * 16 * K2S * ES;
+    // constants k = 0 .. 6: b1 s1 (NR1 * 16 floats each), b2 s2 (NR2 * 16), b3 s3 s_out (NR3 * 16)
+    static constexpr int CONSTS = W3 + NR3 * 16 * K3S * ES;
+    static constexpr int cst(int k) {
+        int off = CONSTS;
+        for (int j = 0; j < k; ++j) off += (j < 2 ? NR1 : j < 4 ? NR2 : NR3) * 16 * 4;
+        return off;
+    }
+    static constexpr int LDS_BYTES = cst(7);
+    static_assert(K1S * ES % 16 == 0 && K2S * ES % 16 == 0 && CONSTS % 16 == 0, "every region starts on a 16-B boundary");
+    static_assert(LDS_BYTES <= 160 * 1024, "a CU has 160 KB of LDS");
+};
 
 template <typename T, int CIN, int I, int COUT>
-__global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN >= 128 ? (UP_NT128 == 512 ? 4 : 2) : 3) : 1)) up_kernel(const UpArgs a) {
+__global__ void __launch_bounds__((UpForm<T, CIN, I, COUT>::NT), (sizeof(T) == 2 ? (CIN >= 128 ? (UP_NT128 == 512 ? 4 : 2) : 3) : 1)) up_kernel(const UpArgs a) {
     span_enter(a.span);
     using Raw = typename Tr<T>::Raw;
     using WRaw = typename WTr<T>::Raw;   // weight operand (fp32 mode: split-f16 parts)
-    constexpr int ES = (int)sizeof(T);
+    using F = UpForm<T, CIN, I, COUT>;
+    constexpr int ES = F::ES;
 // fp32, the 128 -> 64 block: non-temporal output stores (round 5, B = 64, one stream: the bottleneck that
 // reads them 13 us faster, this launch 7 us slower; the 64 -> 16 block lost 26 us for 7, so it keeps
 // the default) — A/B knob UP_NT_F32 (0 off, 1 that block, 2 both)
@@ -54,11 +82,9 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
     constexpr int OAUX = (sizeof(T) == 4 && (UP_NT_F32 == 2 || (UP_NT_F32 == 1 && CIN >= 128))) || (sizeof(T) == 2 && UP_NT_2B && CIN >= 128) ? 2
                        : sizeof(T) == 4 && CIN < 128 ? UP_AUX_F32_LOW
                        : OUT_AUX_SEL(CIN >= 128 ? 16 : 0);   // sc1 output stores (mfma_common.h)
-    constexpr int NR1 = (COUT + I) / 16;              // GEMM 1 rows: main then e1
+    constexpr int NR1 = F::NR1, NR2 = F::NR2, NR3 = F::NR3;   // rows of GEMM 1 (main then e1), the tconv, the expansion
     constexpr int NM = COUT / 16, NE = I / 16;        // row fragments of main / e1 (per tconv phase)
     constexpr int KS1 = CIN / 32;                     // GEMM 1 k-steps
-    constexpr int NR2 = 4 * I / 16;                   // tconv rows (4 phases)
-    constexpr int NR3 = COUT / 16;                    // expansion rows
     static_assert(COUT % 16 == 0 && I % 16 == 0 && CIN % 32 == 0 && I <= 32, "up_kernel shape");
     constexpr bool SWAP = ES == 2 && NR3 % 2 == 0;    // 16-B output chunks by lane-pair swaps (bneck phase 3)
 // fp32, COUT = 64 (a pixel = two 128-B lines): LINES stores whole lines. An accumulator quad is 16 B
@@ -84,23 +110,15 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
     static_assert(NM <= 4 && NE <= 4, "main / e1 launches must carry their bias in the accumulator");
     constexpr bool B1ACC = true;
     constexpr bool B2ACC = bias_in_acc(NR2, 1), B3ACC = bias_in_acc(NR3, 1);   // one k step each (K = I <= 32)
-    // LDS: weights of the three GEMMs (+16 B row pad) and their per-row constants
-    // row pads: bf16 16 elements (row strides 8 / 24 / 40 dwords mod 64: conflict-free ds_read_b128
-    // groups, bneck_kernels.hip bneck_padw), fp32 16 B
-    // (unpadded rows with XOR-swizzled chunks for CIN = 128 measured no faster in the 2-stream bench,
-    // round 3, and were removed)
-    constexpr int UPAD = ES == 2 ? 16 : 16 / ES;
-    constexpr int K1S = CIN + UPAD, K2S = 32 + UPAD, K3S = 32 + UPAD;
+    // LDS (UpForm's map): weights of the three GEMMs (+16 B row pad) and their per-row constants
+    constexpr int K1S = F::K1S, K2S = F::K2S, K3S = F::K3S;
     // element offset of the 8-element chunk c of a weight row (a lane's fragment read)
     auto wch = [](int, int c, int) -> int { return c * 8; };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    T *w1s = reinterpret_cast<T *>(smem);
-    T *w2s = w1s + NR1 * 16 * K1S;
-    T *w3s = w2s + NR2 * 16 * K2S;
-    float *cb1 = reinterpret_cast<float *>(w3s + NR3 * 16 * K3S), *cs1 = cb1 + NR1 * 16;
-    float *cb2 = cs1 + NR1 * 16, *cs2 = cb2 + NR2 * 16;
-    float *cb3 = cs2 + NR2 * 16, *cs3 = cb3 + NR3 * 16, *cso = cs3 + NR3 * 16;
-    constexpr int NT = up_threads<T, CIN>();
+    T *w1s = reinterpret_cast<T *>(smem + F::W1), *w2s = reinterpret_cast<T *>(smem + F::W2), *w3s = reinterpret_cast<T *>(smem + F::W3);
+    auto cst = [&](int k) { return reinterpret_cast<float *>(smem + F::cst(k)); };
+    float *cb1 = cst(0), *cs1 = cst(1), *cb2 = cst(2), *cs2 = cst(3), *cb3 = cst(4), *cs3 = cst(5), *cso = cst(6);
+    constexpr int NT = F::NT;
     const int tid = threadIdx.x;
     {
         auto stage = [&](T *dst, const void *src, int rows, int kpad, int kstride) {
@@ -361,64 +379,51 @@ __global__ void __launch_bounds__((up_threads<T, CIN>()), (sizeof(T) == 2 ? (CIN
     span_exit(a.span);
 }
 
-template <typename T, int CIN, int I, int COUT>
-static size_t up_lds() {
-    constexpr int ES = (int)sizeof(T);
-    constexpr int NR1 = (COUT + I) / 16, NR2 = 4 * I / 16, NR3 = COUT / 16;
-    constexpr int UPAD = ES == 2 ? 16 : 16 / ES;      // = up_kernel's
-    return (size_t)(NR1 * 16 * (CIN + UPAD) + NR2 * 16 * (32 + UPAD) + NR3 * 16 * (32 + UPAD)) * ES +
-           (size_t)(2 * NR1 * 16 + 2 * NR2 * 16 + 3 * NR3 * 16) * sizeof(float);
+// the built forms: every up_kernel instantiation is named here, once
+struct UpEntry { int prec, cin, it, cout; const void *fun; int threads, lds; };
+template <typename T, int CI, int II, int CO> static UpEntry up_entry(int prec) {
+    using F = UpForm<T, CI, II, CO>;
+    return {prec, CI, II, CO, (const void *)up_kernel<T, CI, II, CO>, F::NT, F::LDS_BYTES};
+}
+static const UpEntry UP_FORMS[] = {up_entry<float, 128, 32, 64>(PREC_F32), up_entry<__bf16, 128, 32, 64>(PREC_BF16),
+                                   up_entry<_Float16, 128, 32, 64>(PREC_F16), up_entry<float, 64, 16, 16>(PREC_F32),
+                                   up_entry<__bf16, 64, 16, 16>(PREC_BF16), up_entry<_Float16, 64, 16, 16>(PREC_F16)};
+static const UpEntry *up_form(int prec, int cin, int it, int cout) {
+    for (const UpEntry &e : UP_FORMS)
+        if (e.prec == prec && e.cin == cin && e.it == it && e.cout == cout) return &e;
+    return nullptr;
 }
 
-bool up_supported(int cin, int it, int cout) {
-    return (cin == 128 && it == 32 && cout == 64) || (cin == 64 && it == 16 && cout == 16);
-}
-
-template <int CI, int II, int CO>
-static hipError_t launch_shape(int prec, const UpArgs &a, dim3 g, hipStream_t s) {
-    if (prec == PREC_BF16) {
-        const size_t lds = up_lds<__bf16, CI, II, CO>();
-        hipLaunchKernelGGL((up_kernel<__bf16, CI, II, CO>), g, dim3(up_threads<__bf16, CI>()), lds, s, a);
-    } else if (prec == PREC_F16) {
-        const size_t lds = up_lds<_Float16, CI, II, CO>();
-        hipLaunchKernelGGL((up_kernel<_Float16, CI, II, CO>), g, dim3(up_threads<_Float16, CI>()), lds, s, a);
-    } else {
-        const size_t lds = up_lds<float, CI, II, CO>();
-        if (lds > 64 * 1024) {
-            hipError_t e = allow_dynamic_lds((const void *)up_kernel<float, CI, II, CO>);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((up_kernel<float, CI, II, CO>), g, dim3(up_threads<float, CI>()), lds, s, a);
-    }
-    return hipGetLastError();
-}
-
-// workgroups resident at once (occupancy API, per kernel instance), cached
-template <typename T, int CI, int II, int CO>
-static int up_resident() {
-    // (cached per device: bugseg_runtime.cpp occupancy_per_cu; the >64 KB LDS opt-in first, or the
-    // occupancy API sees a kernel that cannot launch)
-    if (up_lds<T, CI, II, CO>() > 64 * 1024) (void)allow_dynamic_lds((const void *)up_kernel<T, CI, II, CO>);
-    const int per = occupancy_per_cu((const void *)up_kernel<T, CI, II, CO>, up_threads<T, CI>(), up_lds<T, CI, II, CO>());
-    return device_cus() * (per > 0 ? per : 2);
-}
+bool up_supported(int cin, int it, int cout) { return up_form(PREC_F32, cin, it, cout) != nullptr; }
 
 hipError_t launch_up(int prec, int cin, int it, int cout, const UpArgs &a, hipStream_t s) {
-    const int nfrag = (a.M + 15) / 16;
-    const int wpg = (cin == 128 && prec != PREC_F32 ? UP_NT128 : 256) / 64;   // waves per workgroup (up_threads)
+    const UpEntry *f = up_form(prec, cin, it, cout);
+    if (!f) return hipErrorInvalidValue;
+    // (the >64 KB LDS opt-in first, or the occupancy API sees a kernel that cannot launch)
+    if (f->lds > 64 * 1024) {
+        hipError_t e = allow_dynamic_lds(f->fun);
+        if (e != hipSuccess) return e;
+    }
+    const int nfrag = (a.M + 15) / 16, wpg = f->threads / 64;   // 16-pixel fragments, one per wave at a time
     int g = (nfrag + wpg - 1) / wpg;
-    // one resident round of workgroups, each streaming over its fragments (prefetch in the kernel)
-    const int res = cin == 128 ? (prec == PREC_BF16  ? up_resident<__bf16, 128, 32, 64>()
-                                  : prec == PREC_F16 ? up_resident<_Float16, 128, 32, 64>()
-                                                     : up_resident<float, 128, 32, 64>())
-                               : (prec == PREC_BF16  ? up_resident<__bf16, 64, 16, 16>()
-                                  : prec == PREC_F16 ? up_resident<_Float16, 64, 16, 16>()
-                                                     : up_resident<float, 64, 16, 16>());
+    // one resident round of workgroups (occupancy API, per kernel instance; cached per device:
+    // bugseg_runtime.cpp occupancy_per_cu), each streaming over its fragments (prefetch in the kernel)
+    const int per = occupancy_per_cu(f->fun, f->threads, (size_t)f->lds);
+    const int res = device_cus() * (per > 0 ? per : 2);
     if (g > res) g = res;
     if (g < 1) g = 1;
-    if (cin == 128 && it == 32 && cout == 64) return launch_shape<128, 32, 64>(prec, a, dim3(g), s);
-    if (cin == 64 && it == 16 && cout == 16) return launch_shape<64, 16, 16>(prec, a, dim3(g), s);
-    return hipErrorInvalidValue;
+    void *args[] = {const_cast<UpArgs *>(&a)};
+    return hipLaunchKernel(f->fun, dim3(g), dim3(f->threads), args, (size_t)f->lds, s);
+}
+
+int up_form_rows(int32_t *rows, int cap) {
+    int n = 0;
+    for (const UpEntry &e : UP_FORMS) {
+        const int32_t vals[FORM_COLS] = {1, e.prec, e.cout, 0, 0, 0, e.cin, 0, -1, e.threads, e.lds, 0, 0, e.threads / 64, 0, 0};
+        if (n < cap) std::copy(vals, vals + FORM_COLS, rows + (size_t)n * FORM_COLS);
+        ++n;
+    }
+    return n;
 }
 
 }  // namespace bugseg

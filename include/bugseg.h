@@ -217,7 +217,7 @@ int bugseg_bev_occgrid_ws(bugseg_ctx *ctx, const uint8_t *seg_dev, int B, const 
  *              outside the image ignored in both (cv2.morphologyEx's default border)
  *   y_top      first row of the bottom band, int(rows * (1 - 0.1))
  *   min_count  fewest band pixels of a filled contour that is kept, floor(cols * (rows - y_top) * 0.4) + 1
- * The exact semantics (regions, nesting, ring, even-odd output) are stated in DESIGN.md 6.16. */
+ * The exact semantics (regions, nesting, ring, even-odd output) are stated in DESIGN.md 6.17. */
 typedef struct { int rows, cols, k, y_top, min_count; } bugseg_road_filter_params;
 
 /* Bytes of the device workspace bugseg_road_filter needs for B frames (image_processing_utils.py:4-44 keeps
@@ -317,6 +317,13 @@ int bugseg_debug_ctx_info(const bugseg_ctx *ctx, int what, int arg);
  * Test hook: one NAME=value line per knob into buf[len], NUL-terminated: the values ctx holds, or with a NULL
  * ctx those of the environment as it is now (host only). BUGSEG_EINVAL: a bad value, or buf too small. */
 int bugseg_debug_knobs(const bugseg_ctx *ctx, char *buf, int len);
+/* Test hook (host only): the built forms of the fused ENet bottleneck and upsampling kernels,
+ * one row of 16 words each into rows[0 .. n_rows * 16): kind (0 bottleneck, 1 upsampling), precision, C (the
+ * block's output channels), asymmetric, tile variant, transposed, cin (the down form's / the up block's input
+ * channels, else 0), row-windowed, class-LUT kind (-1: no class fusion), threads per workgroup, dynamic LDS
+ * bytes, tile rows, tile columns, waves, row-dilated, residual kept in registers. Returns the number of forms
+ * (rows beyond n_rows are not written), or BUGSEG_EINVAL for a NULL rows with n_rows > 0. */
+int bugseg_debug_fused_forms(int32_t *rows, int n_rows);
 /* Measurement hook (bench.py's in-step kernel table): arm launch spans. spans = device memory of
  * 512 x uint64 per plan op for n_ops ops (NULL disarms): 64 slots 64 B apart, slot k = [k*8] entry,
  * [k*8+1] exit; every later launch of op i < n_ops folds the constant 100 MHz GPU clock into the slots

@@ -155,6 +155,18 @@ int main(int argc, char **argv) {
         unsetenv(k[0]);
     }
 
+    // ---- the fused-form table (bugseg_debug_fused_forms): into heap buffers of exactly the rows asked for, so a
+    // row written past n_rows is a heap overflow here
+    {
+        const int n = bugseg_debug_fused_forms(nullptr, 0);
+        if (n <= 0 || bugseg_debug_fused_forms(nullptr, 1) != BUGSEG_EINVAL) { std::fprintf(stderr, "fused forms: count %d\n", n); return 1; }
+        for (int rows : {1, n - 1, n}) {
+            std::vector<int32_t> buf((size_t)rows * 16);
+            if (bugseg_debug_fused_forms(buf.data(), rows) != n) { std::fprintf(stderr, "fused forms: %d rows\n", rows); return 1; }
+        }
+        tally(BUGSEG_OK);
+    }
+
     std::printf("asan driver ok: %ld inputs accepted, %ld rejected\n", accepted, rejected);
     return 0;
 }
