@@ -29,6 +29,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_bev_occgrid", "bugseg_bev_workspace_bytes", "bugseg_bev_occgrid_ws", "bugseg_plan_info", "bugseg_plan_op", "bugseg_plan_launch_op",
             "bugseg_last_error",
             "bugseg_road_filter_workspace_bytes", "bugseg_road_filter", "bugseg_debug_road_filter_ops",
+            "bugseg_clahe_workspace_bytes", "bugseg_clahe_bgr", "bugseg_debug_clahe_stage", "bugseg_debug_clahe_table",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
@@ -49,6 +50,12 @@ class RoadFilterParams(ctypes.Structure):
     """bugseg_road_filter_params: image_processing_utils.road_filter_params computes them."""
     _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("k", ctypes.c_int), ("y_top", ctypes.c_int),
                 ("min_count", ctypes.c_int)]
+
+
+class ClaheParams(ctypes.Structure):
+    """bugseg_clahe_params: image_processing_utils.clahe_params builds and checks them."""
+    _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("tiles_x", ctypes.c_int), ("tiles_y", ctypes.c_int),
+                ("clip_limit", ctypes.c_float)]
 
 
 class BugsegError(RuntimeError):
@@ -104,6 +111,10 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_road_filter_workspace_bytes": (sz, [ctypes.POINTER(RoadFilterParams), i]),
             "bugseg_road_filter": (i, [vp, vp, i, ctypes.POINTER(RoadFilterParams), vp, vp, sz, vp]),
             "bugseg_debug_road_filter_ops": (i, [vp, vp, i, ctypes.POINTER(RoadFilterParams), vp, vp, sz, i, i, vp]),
+            "bugseg_clahe_workspace_bytes": (sz, [ctypes.POINTER(ClaheParams), i]),
+            "bugseg_clahe_bgr": (i, [vp, vp, i, ctypes.POINTER(ClaheParams), vp, vp, sz, vp]),
+            "bugseg_debug_clahe_stage": (i, [vp, vp, i, ctypes.POINTER(ClaheParams), i, vp, vp, sz, vp]),
+            "bugseg_debug_clahe_table": (i, [i, vp, sz]),
             "bugseg_dl_create": (i, [i, i, ctypes.POINTER(vp)]),
             "bugseg_dl_destroy": (i, [vp]),
             "bugseg_dl_load_weights": (i, [vp, vp, sz]),
@@ -345,6 +356,28 @@ class Context:
         else:
             rc = self.lib.bugseg_debug_road_filter_ops(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(),
                                                        wp, wn, int(ops[0]), int(ops[1]), stream_handle(st))
+        if rc != OK:
+            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
+
+    def clahe(self, frames, B, params: ClaheParams, out, stream=None, stage=None, workspace=None):
+        """bugseg_clahe_bgr: (B, rows, cols, 3) u8 BGR frames -> `out`, the same shape. The workspace (the tile
+        look-up tables) comes from torch's caching allocator on the stream the work runs on, as in road_filter
+        (`workspace`: a uint8 device tensor to use instead). stage = 0..4 enqueues that stage alone
+        (bugseg_debug_clahe_stage: the tests' and the benchmark's view of the parts; `out` may be None for
+        stage 3). Any refusal, a bad argument included, raises BugsegError and launches nothing."""
+        st = stream if stream is not None else torch.cuda.current_stream(frames.device)
+        nws = int(self.lib.bugseg_clahe_workspace_bytes(ctypes.byref(params), B))
+        ws = workspace
+        if ws is None and nws and stage not in (0, 1, 2):
+            with torch.cuda.stream(st):
+                ws = torch.empty(nws, dtype=torch.uint8, device=frames.device)
+        wp, wn = (0, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
+        op = 0 if out is None else out.data_ptr()
+        if stage is None:
+            rc = self.lib.bugseg_clahe_bgr(self.h, frames.data_ptr(), B, ctypes.byref(params), op, wp, wn, stream_handle(st))
+        else:
+            rc = self.lib.bugseg_debug_clahe_stage(self.h, frames.data_ptr(), B, ctypes.byref(params), int(stage), op,
+                                                   wp, wn, stream_handle(st))
         if rc != OK:
             raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
 

@@ -330,5 +330,9 @@ __host__ __device__ inline size_t bev_items_offset(int occ_w, int occ_h) {
 // thread's when ctx is null) and return `code`; ctx_device: the HIP device the context was created on.
 int ctx_fail(bugseg_ctx *ctx, int code, const char *msg);
 int ctx_device(const bugseg_ctx *ctx);
+// ctx_clahe_tables: the context's device copy of clahe_kernels.hip's conversion tables; the first call
+// uploads `host` (`bytes` long) on the context's private setup stream and waits for it there, so it works
+// while `stream` is being captured (as the resize tables). Freed with the context. BUGSEG_OK or an error.
+int ctx_clahe_tables(bugseg_ctx *ctx, const void *host, size_t bytes, void *stream, const void **dev);
 
 }  // namespace bugseg

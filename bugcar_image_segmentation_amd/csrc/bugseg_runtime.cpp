@@ -300,6 +300,8 @@ struct bugseg_ctx {
     std::vector<BevTab> bev_tabs;
     // memory retired while a stream was capturing (a graph may reference it): freed at destroy
     std::vector<void *> graveyard;
+    // clahe_kernels.hip's conversion tables (ctx_clahe_tables): uploaded on first use, read-only afterwards
+    void *clahe_tabs = nullptr;
 };
 
 namespace {
@@ -1581,6 +1583,25 @@ void linear_coeffs(int dsize, int ssize, double scale, int *ofs, short *a01) {
 namespace bugseg {
 int ctx_fail(bugseg_ctx *ctx, int code, const char *msg) { return fail(ctx, code, msg); }
 int ctx_device(const bugseg_ctx *ctx) { return ctx->device; }
+int ctx_clahe_tables(bugseg_ctx *ctx, const void *host, size_t bytes, void *stream, const void **dev) {
+    (void)stream;       // never touched: the upload runs and is waited for on the private setup stream
+    if (!ctx->clahe_tabs) {
+        DeviceGuard g(ctx->device);
+        RelaxCapture relax;
+        hipStream_t st = setup_stream(ctx);
+        void *t = nullptr;
+        hipError_t e = st ? hipMalloc(&t, bytes) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipMemcpyAsync(t, host, bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            if (t) (void)hipFree(t);
+            return fail(ctx, BUGSEG_EHIP, std::string("clahe table upload failed: ") + hipGetErrorString(e));
+        }
+        ctx->clahe_tabs = t;
+    }
+    *dev = ctx->clahe_tabs;
+    return BUGSEG_OK;
+}
 }  // namespace bugseg
 
 // =============================================================== C ABI
@@ -1688,6 +1709,7 @@ int bugseg_destroy(bugseg_ctx *ctx) {
     for (auto &s : ctx->ls_scratch) if (s.p) (void)hipFree(s.p);
     for (auto &t : ctx->bev_tabs) if (t.tab) (void)hipFree(t.tab);
     for (void *p : ctx->graveyard) (void)hipFree(p);
+    if (ctx->clahe_tabs) (void)hipFree(ctx->clahe_tabs);
     if (ctx->setup) (void)hipStreamDestroy(ctx->setup);
     delete ctx;
     return BUGSEG_OK;

@@ -71,7 +71,7 @@ class HostStream:
                 # the graphs hold the addresses of the pipeline's internal buffers: keep those alive even
                 # if the pipeline re-allocates its own for another batch size
                 self._keep = (pipe._x, pipe._seg_raw, pipe._grid, dict(getattr(pipe, "_pairs", {})),
-                              getattr(pipe, "_road", None))
+                              getattr(pipe, "_road", None), getattr(pipe, "_clahe", None))
         self._in_done = [torch.cuda.Event() for _ in range(n)]      # slot's copy-in finished
         self._in_used = [False] * n
         self._step_done = [torch.cuda.Event() for _ in range(n)]

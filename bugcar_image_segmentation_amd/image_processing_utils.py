@@ -1,13 +1,19 @@
 """image_processing_utils.py of the reference, on the native engine: `contour_noise_removal`
 (image_processing_utils.py:4-44), the clean-up of a binary road map between `ENET.predict_binary` and
-`create_occupancy_grid_binary`. The reference's `clahe`, `find_intersection_line` and `create_skeleton`
-are not provided.
+`create_occupancy_grid_binary`, and `clahe` (image_processing_utils.py:46-61), the contrast fix applied to a
+camera frame before `ENET.preprocess`. The reference's `find_intersection_line` and `create_skeleton` are
+not provided.
 
-What it computes is stated in DESIGN.md §6.16: the map is closed with a k x k square, and of the closed
-map's regions only the road regions that reach the bottom tenth of the image are kept, their small holes
-filled. The reference does this on the host with OpenCV (morphologyEx, findContours, one fillPoly per
-contour); here it is a fixed sequence of integer kernels over a batch (csrc/road_kernels.hip), bit-exact
-against the restatement in tests/road_filter_ref.py. There is no CPU fallback.
+What contour_noise_removal computes is stated in DESIGN.md §6.16: the map is closed with a k x k square, and
+of the closed map's regions only the road regions that reach the bottom tenth of the image are kept, their
+small holes filled. The reference does this on the host with OpenCV (morphologyEx, findContours, one fillPoly
+per contour); here it is a fixed sequence of integer kernels over a batch (csrc/road_kernels.hip), bit-exact
+against the restatement in tests/road_filter_ref.py.
+
+What clahe computes is stated in DESIGN.md §6.18: BGR -> Lab in 8 bits, contrast-limited adaptive histogram
+equalisation of L over an 8 x 8 grid of tiles with clipLimit 3.0, Lab -> BGR. The reference does this with
+cv2.cvtColor and cv2.createCLAHE; here it is two launches over a batch (csrc/clahe_kernels.hip), bit-exact
+against the restatement in tests/clahe_ref.py. There is no CPU fallback for either.
 """
 from __future__ import annotations
 
@@ -85,3 +91,66 @@ def contour_noise_removal(segmap):
     if not t.is_cuda:
         t = t.to(torch.device("cuda", torch.cuda.current_device()))
     return contour_noise_removal_device(t)[0].cpu().numpy().copy()      # owned: no torch storage behind it
+
+
+CLAHE_CLIP_LIMIT = 3.0          # image_processing_utils.py:53
+CLAHE_TILE_GRID = (8, 8)        # image_processing_utils.py:53, (tiles_x, tiles_y)
+CLAHE_MAX_TILES = 16
+
+
+def clahe_params(h: int, w: int, clip_limit: float = CLAHE_CLIP_LIMIT, tile_grid=CLAHE_TILE_GRID) -> N.ClaheParams:
+    """bugseg_clahe_params for (h, w) frames, with the checks the library makes, before any device work:
+    ValueError for a grid outside [1, 16] per side, a side smaller than twice its tile count (the reflected
+    border of a frame that the grid does not divide needs that room), a clip limit that is not positive and
+    finite."""
+    h, w = int(h), int(w)
+    try:
+        tx, ty = (int(v) for v in tile_grid)
+    except (TypeError, ValueError):
+        raise ValueError(f"tile_grid must be (tiles_x, tiles_y), got {tile_grid!r}") from None
+    if not (1 <= tx <= CLAHE_MAX_TILES and 1 <= ty <= CLAHE_MAX_TILES):
+        raise ValueError(f"clahe tiles must be in [1, {CLAHE_MAX_TILES}] per side, got {tx} x {ty}")
+    if h < 2 * ty or w < 2 * tx:
+        raise ValueError(f"clahe needs a frame of at least {2 * ty} x {2 * tx} for a {tx} x {ty} grid, got {h} x {w}")
+    c = float(clip_limit)
+    if not (0.0 < c <= float(np.finfo(np.float32).max) and np.float32(c) > 0):      # (the struct holds a float32)
+        raise ValueError(f"clip_limit must be positive and finite, got {clip_limit!r}")
+    p = N.ClaheParams()
+    p.rows, p.cols, p.tiles_x, p.tiles_y, p.clip_limit = h, w, tx, ty, c
+    return p
+
+
+def clahe_device(frames: torch.Tensor, out: torch.Tensor | None = None, clip_limit: float = CLAHE_CLIP_LIMIT,
+                 tile_grid=CLAHE_TILE_GRID) -> torch.Tensor:
+    """Batched clahe on device tensors: (B, h, w, 3) or (h, w, 3) uint8 BGR frames -> (B, h, w, 3) uint8 BGR,
+    on the current stream. `out` must not overlap the input."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
+        raise ValueError("frames must be a uint8 device tensor")
+    f = frames if frames.dim() == 4 else frames.unsqueeze(0)
+    if f.dim() != 4 or f.shape[3] != 3:
+        raise ValueError("frames must have shape (B, h, w, 3) or (h, w, 3)")
+    f = f.contiguous()
+    B, h, w = f.shape[:3]
+    p = clahe_params(h, w, clip_limit, tile_grid)
+    if B < 1:
+        raise ValueError("frames holds no frame")
+    if out is None:
+        out = torch.empty_like(f)
+    elif tuple(out.shape) != tuple(f.shape) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != f.device:
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(f.shape)} on {f.device}")
+    with torch.cuda.device(f.device):
+        N.shared_context(f.device.index).clahe(f, B, p, out, torch.cuda.current_stream(f.device))
+    return out
+
+
+def clahe(img):
+    """image_processing_utils.py:46-61: an (h, w, 3) uint8 BGR frame (NumPy array or torch tensor) -> an owned
+    NumPy uint8 (h, w, 3) BGR frame."""
+    t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+    if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+        raise ValueError("img must be an (h, w, 3) uint8 BGR frame")     # cv2.COLOR_BGR2LAB of 8-bit input
+    clahe_params(t.shape[0], t.shape[1])                        # the size check, before any device work
+    N.require_gpu()
+    if not t.is_cuda:
+        t = t.to(torch.device("cuda", torch.cuda.current_device()))
+    return clahe_device(t)[0].cpu().numpy().copy()              # owned: no torch storage behind it

@@ -34,7 +34,7 @@ class OccupancyPipeline:
     def __init__(self, model: "ENET | DeepLabV3", bev: bev_transform_tools, grid_w_m: float, grid_h_m: float, cell_m: float,
                  model_hw: tuple[int, int] | None = None, ros_layout: bool = False, streams: int = 1,
                  binary: bool = False, stream_priority: int = 0, chain_forwards: bool = False, shard_offset: int = 0,
-                 window_rows: bool = True, road_filter: bool = False):
+                 window_rows: bool = True, road_filter: bool = False, clahe: bool = False):
         """binary=True is the predict_binary + create_occupancy_grid_binary pairing (models.py:70-82,
         bev.py:97-165): class maps through the binary LUT, the binary rasteriser; in the laserscan-like
         mode its output is the reference's pair, (2, B, ...) (bev.py:164). stream_priority is the HIP
@@ -60,7 +60,13 @@ class OccupancyPipeline:
         Context.road_filter into a second u8 buffer, which the rasteriser reads. Its output is a {0, 1} map,
         so it requires binary=True (ENET, or a DeepLabV3 whose LUT is class_lut_binary). The filter needs
         whole maps: a row cut off above the window would open holes and change the closing near the
-        cut, so the forwards run full-frame whatever window_rows says."""
+        cut, so the forwards run full-frame whatever window_rows says.
+        clahe=True runs image_processing_utils.clahe (image_processing_utils.py:46-61) on every
+        shard's stream first, on the camera-size frames, before the resize of models.py:87: Context.clahe
+        writes the enhanced frames into a pipeline-owned (B, H0, W0, 3) buffer, which the forward then reads
+        (and which _seg re-runs after a windowed run). The caller's frames are not changed."""
+        self.clahe = bool(clahe)
+        self._clahe = None           # clahe: (its parameters, the caller's frames, the enhanced frames the forward reads)
         if road_filter and not binary:
             raise ValueError("road_filter=True needs binary=True: contour_noise_removal reads and writes a {0, 1} road map")
         self.road_filter = bool(road_filter)
@@ -182,7 +188,9 @@ class OccupancyPipeline:
                         if rows[0] < rows[1]:
                             self._engines[i].ctx.classes_from_logits(e - s, self.H, self.W, self._seg_raw[s:e], rows, st)
                     continue
-                self._run_forward(self._ctxs[i], frames[s:e], self._x[s:e], self._seg_raw[s:e], st, window=False)
+                # (with clahe the frames kept are the enhanced ones: they are not enhanced again)
+                self._run_forward(self._ctxs[i], frames[s:e], self._x[s:e], self._seg_raw[s:e], st, window=False,
+                                  enhance=False)
         return self._seg_raw
 
     def _params(self):
@@ -203,6 +211,10 @@ class OccupancyPipeline:
         if grid.shape != self._grid_shape(B):       # the calibration's laserscan flag changed
             self._grid = grid = torch.empty(self._grid_shape(B), dtype=torch.int8, device=frames_bgr.device)
         frames = frames_bgr.contiguous()
+        if self.clahe:
+            # every shard enhances its own frames on its own stream (_run_forward); from here on `frames` is
+            # the enhanced buffer
+            frames = self._clahe_bufs(frames)
         out = grid if out is None else out
         if tuple(out.shape) != tuple(grid.shape) or out.dtype != torch.int8 or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous int8 tensor of shape {tuple(grid.shape)}")
@@ -245,6 +257,16 @@ class OccupancyPipeline:
         if self._windowed:
             self._seg_partial = (frames, bounds)
         return out
+
+    def _clahe_bufs(self, frames):
+        from .image_processing_utils import clahe_params
+        old = self._clahe
+        if old is None or old[2].shape != frames.shape or old[2].device != frames.device:
+            enh = torch.empty_like(frames)
+            self._clahe = (clahe_params(frames.shape[1], frames.shape[2]), frames, enh)
+        else:
+            self._clahe = (old[0], frames, old[2])
+        return self._clahe[2]
 
     def _pair_buf(self, i, shape, dev):
         if not hasattr(self, "_pairs"):
@@ -325,8 +347,13 @@ class OccupancyPipeline:
             self._spans[key] = None if (r0 <= 0 and r1 >= self.H) or r0 >= r1 else (r0, r1)
         return self._spans[key]
 
-    def _run_forward(self, ctx, frames, x, seg, stream, split=0, window=True):
+    def _run_forward(self, ctx, frames, x, seg, stream, split=0, window=True, enhance=True):
         B, H0, W0 = frames.shape[:3]
+        if self.clahe and enhance:
+            # the shard's frames of the caller's batch: frames is a run of whole frames of the enhanced buffer
+            cp, src, enh = self._clahe
+            s = (frames.data_ptr() - enh.data_ptr()) // (H0 * W0 * 3)
+            ctx.clahe(src[s:s + B], B, cp, frames, stream)
         if (H0, W0) != (self.H, self.W):
             # resize only (models.py:87); colour swap + normalisation are fused into the initial block
             ctx.preprocess(frames, B, H0, W0, self.H, self.W, N.PRE_BGR_U8, x, stream)

@@ -243,6 +243,45 @@ int bugseg_debug_road_filter_ops(bugseg_ctx *ctx, const uint8_t *seg_dev, int B,
                                  uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, int first_op,
                                  int last_op, void *stream);
 
+/* clahe (image_processing_utils.py:46-61), the contrast fix applied to a camera frame before
+ * ENET.preprocess: BGR -> Lab (8 bit), CLAHE on L over a tiles_x x tiles_y grid (the reference: 8 x 8,
+ * clip_limit 3.0), Lab -> BGR. The exact semantics (OpenCV's integer BGR -> Lab, clahe.cpp's histogram
+ * clipping and float32 blend, this project's integer Lab -> BGR) are stated in DESIGN.md 6.18. */
+typedef struct { int rows, cols, tiles_x, tiles_y; float clip_limit; } bugseg_clahe_params;
+
+/* Bytes of the device workspace bugseg_clahe_bgr needs for B frames: the tile look-up tables,
+ * (B, tiles_y, tiles_x, 256) u8; 0 for parameters the call would refuse for their shape. */
+size_t bugseg_clahe_workspace_bytes(const bugseg_clahe_params *p, int B);
+
+/* image_processing_utils.py:46-61 over a batch: bgr_dev (B, rows, cols, 3) u8 BGR -> out_dev, the same
+ * shape. out_dev must not overlap bgr_dev. The workspace is caller-owned and used only by the work this
+ * call enqueues on `stream` (as bugseg_road_filter); its prior contents do not matter. Two launches: the
+ * tile look-up tables (one workgroup per frame and tile), then the per-pixel pass; no Lab image is written
+ * to memory. The call never synchronises `stream` and may be captured into a graph on its first call (the
+ * context's conversion tables, 34 KB, are uploaded on the context's private stream on first use).
+ * BUGSEG_EINVAL, and nothing is launched: B < 1 (or above 65535, the launch grid's limit), tiles outside
+ * [1, 16], a side smaller than twice its tile count (the reflected border needs the room), clip_limit not
+ * positive or not finite, B * rows * cols * 3 too large for an int32 index, a NULL or short workspace,
+ * overlapping buffers. */
+int bugseg_clahe_bgr(bugseg_ctx *ctx, const uint8_t *bgr_dev, int B, const bugseg_clahe_params *p,
+                     uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Tests and bench_clahe.py (image_processing_utils.py:46-61 has no counterpart): one stage of
+ * bugseg_clahe_bgr, run by the device functions the product runs.
+ *   0  BGR -> Lab: out_dev (B, rows, cols, 3) u8 Lab; no workspace
+ *   1  the tile look-up tables of in_dev's frames: out_dev (B, tiles_y, tiles_x, 256) u8; no workspace
+ *   2  Lab -> BGR of in_dev read as a Lab image: out_dev (B, rows, cols, 3) u8 BGR; no workspace
+ *   3  launch 1 only: the look-up tables into the workspace; out_dev is not used
+ *   4  launch 2 only: the look-up tables are already in the workspace */
+int bugseg_debug_clahe_stage(bugseg_ctx *ctx, const uint8_t *in_dev, int B, const bugseg_clahe_params *p, int stage,
+                             uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Host only, no GPU: copy out conversion table `which` as the library built it; `bytes` must be its size.
+ * 0 gamma u16[256], 1 cube root u16[3072], 2 RGB -> XYZ / white i32[9] (Q12), 3 fy by L i32[256] (Q16),
+ * 4 Y by L i32[256] (Q20), 5 finv over f i32[2306] (Q20), 6 XYZ -> RGB * white i32[9] (Q16),
+ * 7 inverse gamma u8[16385]. */
+int bugseg_debug_clahe_table(int which, void *dst, size_t bytes);
+
 /* Plan introspection for the bench / roofline, for the engine-input entry (bgr_input = 0) or
  * bugseg_enet_forward_bgr (bgr_input = 1), context precision:
  *   n_launches  kernel launches of one forward;
