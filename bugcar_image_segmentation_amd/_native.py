@@ -30,6 +30,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_last_error",
             "bugseg_road_filter_workspace_bytes", "bugseg_road_filter", "bugseg_debug_road_filter_ops",
             "bugseg_clahe_workspace_bytes", "bugseg_clahe_bgr", "bugseg_debug_clahe_stage", "bugseg_debug_clahe_table",
+            "bugseg_canny_workspace_bytes", "bugseg_canny", "bugseg_debug_canny_stage",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
@@ -56,6 +57,11 @@ class ClaheParams(ctypes.Structure):
     """bugseg_clahe_params: image_processing_utils.clahe_params builds and checks them."""
     _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("tiles_x", ctypes.c_int), ("tiles_y", ctypes.c_int),
                 ("clip_limit", ctypes.c_float)]
+
+
+class CannyParams(ctypes.Structure):
+    """bugseg_canny_params: image_processing_utils.canny_params builds and checks them."""
+    _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("low", ctypes.c_int), ("high", ctypes.c_int)]
 
 
 class BugsegError(RuntimeError):
@@ -115,6 +121,9 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_clahe_bgr": (i, [vp, vp, i, ctypes.POINTER(ClaheParams), vp, vp, sz, vp]),
             "bugseg_debug_clahe_stage": (i, [vp, vp, i, ctypes.POINTER(ClaheParams), i, vp, vp, sz, vp]),
             "bugseg_debug_clahe_table": (i, [i, vp, sz]),
+            "bugseg_canny_workspace_bytes": (sz, [ctypes.POINTER(CannyParams), i]),
+            "bugseg_canny": (i, [vp, vp, i, ctypes.POINTER(CannyParams), vp, vp, sz, vp]),
+            "bugseg_debug_canny_stage": (i, [vp, vp, i, ctypes.POINTER(CannyParams), i, vp, vp, sz, vp]),
             "bugseg_dl_create": (i, [i, i, ctypes.POINTER(vp)]),
             "bugseg_dl_destroy": (i, [vp]),
             "bugseg_dl_load_weights": (i, [vp, vp, sz]),
@@ -378,6 +387,28 @@ class Context:
         else:
             rc = self.lib.bugseg_debug_clahe_stage(self.h, frames.data_ptr(), B, ctypes.byref(params), int(stage), op,
                                                    wp, wn, stream_handle(st))
+        if rc != OK:
+            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
+
+    def canny(self, images, B, params: CannyParams, out, stream=None, stage=None, workspace=None):
+        """bugseg_canny: (B, rows, cols) u8 images -> `out`, the same shape, in {0, 255}. The workspace comes
+        from torch's caching allocator on the stream the work runs on, as in road_filter (`workspace`: a uint8
+        device tensor to use instead). stage = 0 or 1 enqueues that half alone (bugseg_debug_canny_stage: 0
+        writes the non-maximum-suppression map to `out`, 1 reads `images` as such a map). Any refusal, a bad
+        argument included, raises BugsegError and launches nothing."""
+        st = stream if stream is not None else torch.cuda.current_stream(images.device)
+        nws = int(self.lib.bugseg_canny_workspace_bytes(ctypes.byref(params), B))
+        ws = workspace
+        if ws is None and nws:
+            with torch.cuda.stream(st):
+                ws = torch.empty(nws, dtype=torch.uint8, device=images.device)
+        wp, wn = (0, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
+        if stage is None:
+            rc = self.lib.bugseg_canny(self.h, images.data_ptr(), B, ctypes.byref(params), out.data_ptr(), wp, wn,
+                                       stream_handle(st))
+        else:
+            rc = self.lib.bugseg_debug_canny_stage(self.h, images.data_ptr(), B, ctypes.byref(params), int(stage),
+                                                   out.data_ptr(), wp, wn, stream_handle(st))
         if rc != OK:
             raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
 

@@ -1,8 +1,8 @@
 """image_processing_utils.py of the reference, on the native engine: `contour_noise_removal`
 (image_processing_utils.py:4-44), the clean-up of a binary road map between `ENET.predict_binary` and
 `create_occupancy_grid_binary`, and `clahe` (image_processing_utils.py:46-61), the contrast fix applied to a
-camera frame before `ENET.preprocess`. The reference's `find_intersection_line` and `create_skeleton` are
-not provided.
+camera frame before `ENET.preprocess`, `find_intersection_line` (image_processing_utils.py:63-91) and
+`create_skeleton` (image_processing_utils.py:95-105) with the `cv2.Canny` it needs (`canny`, `canny_device`).
 
 What contour_noise_removal computes is stated in DESIGN.md §6.16: the map is closed with a k x k square, and
 of the closed map's regions only the road regions that reach the bottom tenth of the image are kept, their
@@ -13,7 +13,14 @@ against the restatement in tests/road_filter_ref.py.
 What clahe computes is stated in DESIGN.md §6.18: BGR -> Lab in 8 bits, contrast-limited adaptive histogram
 equalisation of L over an 8 x 8 grid of tiles with clipLimit 3.0, Lab -> BGR. The reference does this with
 cv2.cvtColor and cv2.createCLAHE; here it is two launches over a batch (csrc/clahe_kernels.hip), bit-exact
-against the restatement in tests/clahe_ref.py. There is no CPU fallback for either.
+against the restatement in tests/clahe_ref.py.
+
+What canny computes is stated in DESIGN.md §6.19: 3 x 3 Sobel with the border replicated, |dx| + |dy|,
+non-maximum suppression, hysteresis between two thresholds (cv2.Canny with apertureSize 3 and L2gradient
+False, the only form the reference uses). Here it is five launches over a batch (csrc/canny_kernels.hip),
+bit-exact against the restatements in tests/canny_ref.py. create_skeleton is the outline of the camera's field
+of view in the occupancy grid: the edges of the grid of an all-free map. find_intersection_line is host
+arithmetic. There is no CPU fallback for the device functions.
 """
 from __future__ import annotations
 
@@ -154,3 +161,108 @@ def clahe(img):
     if not t.is_cuda:
         t = t.to(torch.device("cuda", torch.cuda.current_device()))
     return clahe_device(t)[0].cpu().numpy().copy()              # owned: no torch storage behind it
+
+
+CANNY_LOW, CANNY_HIGH = 50, 150         # image_processing_utils.py:104
+
+
+def canny_params(h: int, w: int, threshold1, threshold2, apertureSize: int = 3, L2gradient: bool = False) -> N.CannyParams:
+    """bugseg_canny_params for (h, w) images, with every check before any device work: ValueError for an
+    aperture other than 3, the L2 gradient, an empty image, a threshold that is NaN or infinite. The struct
+    holds low = floor(threshold1) and high = floor(threshold2), swapped if low > high (DESIGN.md §6.19,
+    step 1), clamped to the int32 range (no magnitude exceeds 2040, so the clamp changes no result)."""
+    h, w = int(h), int(w)
+    if apertureSize != 3:
+        raise ValueError(f"canny supports apertureSize 3 only, got {apertureSize!r}")
+    if L2gradient:
+        raise ValueError("canny supports L2gradient=False only")
+    if h < 1 or w < 1:
+        raise ValueError(f"canny needs an image of at least 1 x 1, got {h} x {w}")
+    t = []
+    for v in (threshold1, threshold2):
+        f = float(v)
+        if not np.isfinite(f):
+            raise ValueError(f"canny thresholds must be finite, got {v!r}")
+        t.append(int(min(max(np.floor(f), -2.0 ** 31), 2.0 ** 31 - 1)))
+    low, high = t
+    if low > high:
+        low, high = high, low
+    p = N.CannyParams()
+    p.rows, p.cols, p.low, p.high = h, w, low, high
+    return p
+
+
+def canny_device(images: torch.Tensor, threshold1, threshold2, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Batched cv2.Canny(image, threshold1, threshold2) on device tensors: (B, h, w) or (h, w) uint8 images
+    -> (B, h, w) uint8 in {0, 255}, on the current stream. `out` must not overlap the input."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype != torch.uint8:
+        raise ValueError("images must be a uint8 device tensor")
+    im = images if images.dim() == 3 else images.unsqueeze(0)
+    if im.dim() != 3:
+        raise ValueError("images must have shape (B, h, w) or (h, w)")
+    im = im.contiguous()
+    B, h, w = im.shape
+    p = canny_params(h, w, threshold1, threshold2)
+    if B < 1:
+        raise ValueError("images holds no frame")
+    if out is None:
+        out = torch.empty((B, h, w), dtype=torch.uint8, device=im.device)
+    elif tuple(out.shape) != (B, h, w) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != im.device:
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {(B, h, w)} on {im.device}")
+    with torch.cuda.device(im.device):
+        N.shared_context(im.device.index).canny(im, B, p, out, torch.cuda.current_stream(im.device))
+    return out
+
+
+def canny(img, threshold1, threshold2, apertureSize: int = 3, L2gradient: bool = False):
+    """cv2.Canny(img, threshold1, threshold2, apertureSize=3, L2gradient=False): an (h, w) uint8 image (NumPy
+    array or torch tensor) -> an owned NumPy uint8 (h, w) edge map in {0, 255}."""
+    t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+    if t.dim() != 2 or t.dtype != torch.uint8:
+        raise ValueError("img must be an (h, w) uint8 image")            # cv2.Canny's 8-bit single-channel input
+    canny_params(t.shape[0], t.shape[1], threshold1, threshold2, apertureSize, L2gradient)   # before any device work
+    N.require_gpu()
+    if not t.is_cuda:
+        t = t.to(torch.device("cuda", torch.cuda.current_device()))
+    return canny_device(t, threshold1, threshold2)[0].cpu().numpy().copy()      # owned: no torch storage behind it
+
+
+def find_intersection_line(line1, line2):
+    """image_processing_utils.py:63-91, host arithmetic: each line is two points ((x1, y1), (x2, y2)); the
+    result is the NumPy pair (x, y) where they meet, or None. A line is a x + b y = c with b = -1,
+    a = (y2 - y1) / (x2 - x1), c = (x1 y2 - x2 y1) / (x2 - x1); a vertical line is a = 1, b = 0, c = x1.
+
+    As in the reference, None is returned whenever the two a are equal: for parallel lines and two vertical
+    lines, and also for a vertical line against a line of slope 1 (both have a = 1), although those two meet."""
+    first, second = _line_abc(line1), _line_abc(line2)
+    if first[0] == second[0]:
+        return None
+    return np.linalg.solve(np.array([first[:2], second[:2]]), np.array([first[2], second[2]]))
+
+
+def _line_abc(line):
+    """(a, b, c) of a x + b y = c through the two points of `line`, in find_intersection_line's convention."""
+    (px, py), (qx, qy) = line[0], line[1]
+    run = qx - px
+    if run == 0:
+        return 1, 0, px                                  # vertical: x = px
+    return (qy - py) / run, -1, (px * qy - qx * py) / run
+
+
+def create_skeleton(perspective_transformer, input_shape, occupancy_grid_width_in_m, occupancy_grid_height_in_m,
+                    cell_size_in_m):
+    """image_processing_utils.py:95-105 with a call shape that works: the reference passes
+    create_occupancy_grid seven arguments, five of them attributes the transformer does not have; here they
+    are create_occupancy_grid's three real ones. input_shape = (width, height) of the segmentation map. The
+    occupancy grid of an all-free (height, width) map is built on the device, its int8 cells are read as uint8
+    (unknown, -1, becomes 255) and canny_device(., 50, 150) outlines the camera's field of view in it; only the
+    result leaves the device -> NumPy uint8 (h, w) in {0, 255}. A map shape that the transformer was not
+    calibrated for fails its own assertion."""
+    width, height = input_shape
+    N.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    free_img = torch.ones((int(height), int(width)), dtype=torch.uint8, device=dev)      # image_processing_utils.py:97
+    occ_grid = perspective_transformer.create_occupancy_grid_device(free_img, occupancy_grid_width_in_m,
+                                                                    occupancy_grid_height_in_m, cell_size_in_m)
+    edges = canny_device(occ_grid.contiguous().view(torch.uint8), CANNY_LOW, CANNY_HIGH)
+    return edges[0].cpu().numpy().copy()

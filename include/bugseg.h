@@ -282,6 +282,38 @@ int bugseg_debug_clahe_stage(bugseg_ctx *ctx, const uint8_t *in_dev, int B, cons
  * 7 inverse gamma u8[16385]. */
 int bugseg_debug_clahe_table(int which, void *dst, size_t bytes);
 
+/* Canny edge detection as create_skeleton uses it (image_processing_utils.py:95-105: cv2.Canny with
+ * apertureSize 3 and the L1 gradient magnitude), batched: 3 x 3 Sobel with the border replicated, |dx| + |dy|,
+ * non-maximum suppression, hysteresis. low and high are the thresholds after the host's floor() and, if
+ * low > high, swap (image_processing_utils.canny_params). The exact semantics are stated in DESIGN.md 6.19;
+ * everything is integer arithmetic. */
+typedef struct { int rows, cols, low, high; } bugseg_canny_params;
+
+/* Bytes of the device workspace bugseg_canny needs for B frames: 5 bytes per pixel (one map byte, one
+ * int32 label) plus alignment; 0 for parameters the call would refuse for their shape. */
+size_t bugseg_canny_workspace_bytes(const bugseg_canny_params *p, int B);
+
+/* img_dev (B, rows, cols) u8 -> out_dev (B, rows, cols) u8 in {0, 255}. out_dev must not overlap img_dev.
+ * The workspace is caller-owned and used only by the work this call enqueues on `stream` (as
+ * bugseg_road_filter); its prior contents do not matter. A fixed sequence of five launches: gradient and
+ * non-maximum suppression fused (no gradient or magnitude image is written to memory), then hysteresis as
+ * 8-connected component labelling (per-tile union-find, merge across tile borders, marking of the roots of
+ * strong pixels, output). The call never synchronises, needs no weights and no tables, and may be captured
+ * into a graph on its first call. BUGSEG_EINVAL, and nothing is launched: B < 1 (or above 65535, the launch
+ * grid's limit), rows < 1 or cols < 1, B * rows * cols too large for an int32 index, a frame with 2^24 or
+ * more 16 x 64 tiles (their threads pass a launch grid's 2^32 - 1; only frames thinner than a tile can
+ * have that many and still fit the index: 1 x cols above 2^30 - 64, rows x 1 above 2^28 - 16), a NULL or
+ * short workspace, overlapping buffers. */
+int bugseg_canny(bugseg_ctx *ctx, const uint8_t *img_dev, int B, const bugseg_canny_params *p,
+                 uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Tests and bench_canny.py: one half of bugseg_canny, run by the device functions the product runs; the
+ * refusals are bugseg_canny's.
+ *   0  launch 0 only: out_dev is the (B, rows, cols) map, 2 strong, 0 weak, 1 none
+ *   1  hysteresis only: in_dev is read as such a map (any byte other than 2 and 0 is none), out_dev the edges */
+int bugseg_debug_canny_stage(bugseg_ctx *ctx, const uint8_t *in_dev, int B, const bugseg_canny_params *p, int stage,
+                             uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* Plan introspection for the bench / roofline, for the engine-input entry (bgr_input = 0) or
  * bugseg_enet_forward_bgr (bgr_input = 1), context precision:
  *   n_launches  kernel launches of one forward;
