@@ -30,7 +30,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_last_error",
             "bugseg_road_filter_workspace_bytes", "bugseg_road_filter", "bugseg_debug_road_filter_ops",
             "bugseg_clahe_workspace_bytes", "bugseg_clahe_bgr", "bugseg_debug_clahe_stage", "bugseg_debug_clahe_table",
-            "bugseg_canny_workspace_bytes", "bugseg_canny", "bugseg_debug_canny_stage",
+            "bugseg_canny_workspace_bytes", "bugseg_canny", "bugseg_debug_canny_stage", "bugseg_confusion",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
@@ -62,6 +62,13 @@ class ClaheParams(ctypes.Structure):
 class CannyParams(ctypes.Structure):
     """bugseg_canny_params: image_processing_utils.canny_params builds and checks them."""
     _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("low", ctypes.c_int), ("high", ctypes.c_int)]
+
+
+class ConfusionParams(ctypes.Structure):
+    """bugseg_confusion_params: evaluate.confusion_params builds and checks them."""
+    _fields_ = [("pred_rows", ctypes.c_int), ("pred_cols", ctypes.c_int), ("gt_rows", ctypes.c_int),
+                ("gt_cols", ctypes.c_int), ("num_classes", ctypes.c_int), ("pred_lut", ctypes.c_uint8 * 256),
+                ("gt_lut", ctypes.c_uint8 * 256)]
 
 
 class BugsegError(RuntimeError):
@@ -124,6 +131,7 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_canny_workspace_bytes": (sz, [ctypes.POINTER(CannyParams), i]),
             "bugseg_canny": (i, [vp, vp, i, ctypes.POINTER(CannyParams), vp, vp, sz, vp]),
             "bugseg_debug_canny_stage": (i, [vp, vp, i, ctypes.POINTER(CannyParams), i, vp, vp, sz, vp]),
+            "bugseg_confusion": (i, [vp, vp, vp, i, ctypes.POINTER(ConfusionParams), vp, vp]),
             "bugseg_dl_create": (i, [i, i, ctypes.POINTER(vp)]),
             "bugseg_dl_destroy": (i, [vp]),
             "bugseg_dl_load_weights": (i, [vp, vp, sz]),
@@ -409,6 +417,17 @@ class Context:
         else:
             rc = self.lib.bugseg_debug_canny_stage(self.h, images.data_ptr(), B, ctypes.byref(params), int(stage),
                                                    out.data_ptr(), wp, wn, stream_handle(st))
+        if rc != OK:
+            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
+
+    def confusion(self, pred, gt, B, params: ConfusionParams, acc, stream=None):
+        """bugseg_confusion: (B, pred_rows, pred_cols) u8 predictions against (B, gt_rows, gt_cols) u8 labels,
+        added into `acc`, an int64 device tensor of num_classes^2 + 1 words (the matrix row by row, rows =
+        labels, then the skipped pixels). One launch, no workspace. Any refusal, a bad argument included,
+        raises BugsegError and launches nothing."""
+        st = stream if stream is not None else torch.cuda.current_stream(gt.device)
+        rc = self.lib.bugseg_confusion(self.h, pred.data_ptr(), gt.data_ptr(), B, ctypes.byref(params), acc.data_ptr(),
+                                       stream_handle(st))
         if rc != OK:
             raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
 

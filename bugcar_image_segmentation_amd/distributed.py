@@ -49,6 +49,21 @@ def gather_grids(local: torch.Tensor, total: int, group=None) -> torch.Tensor:
     return torch.cat([p[:c] for p, c in zip(parts, counts)], 0)
 
 
+def reduce_confusion(acc: torch.Tensor, group=None) -> torch.Tensor:
+    """Sum the ranks' int64 confusion accumulators (evaluate.Evaluator.acc, C * C + 1 words) in place on every
+    rank: ONE all_reduce(SUM). Integer sums, so every rank holds the same bits whatever the order. A CPU
+    tensor is reduced as it is (gloo); a device tensor under gloo goes through a host copy."""
+    if acc.dtype != torch.int64:
+        raise ValueError("a confusion accumulator is an int64 tensor")
+    if acc.is_cuda and dist.get_backend(group) != "nccl":
+        host = acc.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        acc.copy_(host)
+        return acc
+    dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=group)
+    return acc
+
+
 def run_sharded(frames: torch.Tensor, step: Callable[[torch.Tensor], torch.Tensor], group=None) -> torch.Tensor:
     """frames: the FULL batch (every rank holds it, or a view of it); each rank runs `step` on its
     shard and the grids are all-gathered. Returns (B, h, w) on every rank."""

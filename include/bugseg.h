@@ -314,6 +314,28 @@ int bugseg_canny(bugseg_ctx *ctx, const uint8_t *img_dev, int B, const bugseg_ca
 int bugseg_debug_canny_stage(bugseg_ctx *ctx, const uint8_t *in_dev, int B, const bugseg_canny_params *p, int stage,
                              uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* Evaluation of class maps: the confusion matrix of predictions against labels, both u8 maps
+ * in device memory. A label pixel (y, x) of a gt_rows x gt_cols label map is compared with the prediction at
+ * sy = min(y * pred_rows / gt_rows, pred_rows - 1), sx = min(x * pred_cols / gt_cols, pred_cols - 1), exact
+ * integer arithmetic (the identity for equal shapes). g = gt_lut[label byte], p = pred_lut[prediction byte];
+ * a pixel with g >= num_classes or p >= num_classes is skipped. num_classes is 1..64. */
+typedef struct {
+    int pred_rows, pred_cols, gt_rows, gt_cols, num_classes;
+    uint8_t pred_lut[256], gt_lut[256];
+} bugseg_confusion_params;
+
+/* pred_dev (B, pred_rows, pred_cols) u8, gt_dev (B, gt_rows, gt_cols) u8 -> acc_dev, int64[C * C + 1] with
+ * C = num_classes: acc[g * C + p] += 1 per evaluated label pixel, acc[C * C] += 1 per skipped one, so one call
+ * adds B * gt_rows * gt_cols in all. The accumulator is the caller's and is not zeroed; the adds are device-scope
+ * 64-bit integer atomics, so the result does not depend on their order and concurrent calls may share an
+ * accumulator. One launch; the call never synchronises, allocates nothing, needs no weights and may be captured
+ * into a graph on its first call. The maps may start at any byte address; whole 16-byte loads are used when
+ * the two start equally far from a 16-byte boundary. BUGSEG_EINVAL, and nothing is launched: a NULL argument,
+ * B < 1, an empty map, num_classes outside 1..64, B * rows * cols of either map (or, for unequal shapes,
+ * gt_rows * pred_rows or gt_cols * pred_cols) too large for an int32 index, acc_dev not 8-byte aligned. */
+int bugseg_confusion(bugseg_ctx *ctx, const uint8_t *pred_dev, const uint8_t *gt_dev, int B,
+                     const bugseg_confusion_params *p, int64_t *acc_dev, void *stream);
+
 /* Plan introspection for the bench / roofline, for the engine-input entry (bgr_input = 0) or
  * bugseg_enet_forward_bgr (bgr_input = 1), context precision:
  *   n_launches  kernel launches of one forward;
