@@ -342,39 +342,44 @@ class Context:
         check(self.lib.bugseg_debug_read_block_output(self.h, op, out.data_ptr(), out.numel() * out.element_size(),
                                                       ctypes.c_void_p(stream_handle(stream))), self.h)
 
+    def _stream_ws(self, x, stream, workspace=None, size_fn=None, params=None, B=0):
+        """-> (stream handle, (workspace pointer, bytes), the workspace tensor: keep it until the call is enqueued)
+        for an operator on `x`'s device. The stream is `stream` or the current one; the workspace is `workspace`
+        or, given size_fn, size_fn(params, B) bytes from torch's caching allocator on that stream (reuse is
+        stream-ordered; under graph capture it is the graph's pool)."""
+        st = stream if stream is not None else torch.cuda.current_stream(x.device)
+        ws = workspace
+        nws = int(size_fn(ctypes.byref(params), B)) if ws is None and size_fn is not None else 0
+        if nws:
+            with torch.cuda.stream(st):
+                ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+        return stream_handle(st), ((0, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())), ws
+
+    def _raise_any(self, rc: int) -> None:
+        """BugsegError for any non-zero code (check() turns EINVAL into ValueError)."""
+        if rc != OK:
+            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
+
     def bev(self, seg, B, params: BevParams, out, stream=None):
         """bugseg_bev_occgrid_ws: the laserscan scratch comes from torch's caching allocator on the
         stream the work runs on (reuse is stream-ordered; under graph capture it is the graph's pool),
         so the library never allocates or synchronises for it."""
-        st = stream if stream is not None else torch.cuda.current_stream(seg.device)
-        nws = int(self.lib.bugseg_bev_workspace_bytes(ctypes.byref(params), B))
-        ws = None
-        if nws:
-            with torch.cuda.stream(st):
-                ws = torch.empty(nws, dtype=torch.uint8, device=seg.device)
-        check(self.lib.bugseg_bev_occgrid_ws(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(),
-                                             0 if ws is None else ws.data_ptr(), nws, stream_handle(st)), self.h)
+        sh, w, _keep = self._stream_ws(seg, stream, None, self.lib.bugseg_bev_workspace_bytes, params, B)
+        check(self.lib.bugseg_bev_occgrid_ws(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(), *w, sh),
+              self.h)
 
     def road_filter(self, seg, B, params: RoadFilterParams, out, stream=None, ops=None, workspace=None):
         """bugseg_road_filter: the workspace comes from torch's caching allocator on the stream the work
         runs on, as in bev (`workspace`: a uint8 device tensor to use instead). ops = (first, last) enqueues
         only those launches (bugseg_debug_road_filter_ops, the benchmark's per-kernel times). Any refusal,
         a bad argument included, raises BugsegError and launches nothing."""
-        st = stream if stream is not None else torch.cuda.current_stream(seg.device)
-        nws = int(self.lib.bugseg_road_filter_workspace_bytes(ctypes.byref(params), B))
-        ws = workspace
-        if ws is None and nws:
-            with torch.cuda.stream(st):
-                ws = torch.empty(nws, dtype=torch.uint8, device=seg.device)
-        wp, wn = (0, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
+        sh, w, _keep = self._stream_ws(seg, stream, workspace, self.lib.bugseg_road_filter_workspace_bytes, params, B)
         if ops is None:
-            rc = self.lib.bugseg_road_filter(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(), wp, wn,
-                                             stream_handle(st))
+            rc = self.lib.bugseg_road_filter(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(), *w, sh)
         else:
             rc = self.lib.bugseg_debug_road_filter_ops(self.h, seg.data_ptr(), B, ctypes.byref(params), out.data_ptr(),
-                                                       wp, wn, int(ops[0]), int(ops[1]), stream_handle(st))
-        if rc != OK:
-            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
+                                                       *w, int(ops[0]), int(ops[1]), sh)
+        self._raise_any(rc)
 
     def clahe(self, frames, B, params: ClaheParams, out, stream=None, stage=None, workspace=None):
         """bugseg_clahe_bgr: (B, rows, cols, 3) u8 BGR frames -> `out`, the same shape. The workspace (the tile
@@ -382,21 +387,15 @@ class Context:
         (`workspace`: a uint8 device tensor to use instead). stage = 0..4 enqueues that stage alone
         (bugseg_debug_clahe_stage: the tests' and the benchmark's view of the parts; `out` may be None for
         stage 3). Any refusal, a bad argument included, raises BugsegError and launches nothing."""
-        st = stream if stream is not None else torch.cuda.current_stream(frames.device)
-        nws = int(self.lib.bugseg_clahe_workspace_bytes(ctypes.byref(params), B))
-        ws = workspace
-        if ws is None and nws and stage not in (0, 1, 2):
-            with torch.cuda.stream(st):
-                ws = torch.empty(nws, dtype=torch.uint8, device=frames.device)
-        wp, wn = (0, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
+        size_fn = None if stage in (0, 1, 2) else self.lib.bugseg_clahe_workspace_bytes    # (stages 0-2 use none)
+        sh, w, _keep = self._stream_ws(frames, stream, workspace, size_fn, params, B)
         op = 0 if out is None else out.data_ptr()
         if stage is None:
-            rc = self.lib.bugseg_clahe_bgr(self.h, frames.data_ptr(), B, ctypes.byref(params), op, wp, wn, stream_handle(st))
+            rc = self.lib.bugseg_clahe_bgr(self.h, frames.data_ptr(), B, ctypes.byref(params), op, *w, sh)
         else:
             rc = self.lib.bugseg_debug_clahe_stage(self.h, frames.data_ptr(), B, ctypes.byref(params), int(stage), op,
-                                                   wp, wn, stream_handle(st))
-        if rc != OK:
-            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
+                                                   *w, sh)
+        self._raise_any(rc)
 
     def canny(self, images, B, params: CannyParams, out, stream=None, stage=None, workspace=None):
         """bugseg_canny: (B, rows, cols) u8 images -> `out`, the same shape, in {0, 255}. The workspace comes
@@ -404,32 +403,22 @@ class Context:
         device tensor to use instead). stage = 0 or 1 enqueues that half alone (bugseg_debug_canny_stage: 0
         writes the non-maximum-suppression map to `out`, 1 reads `images` as such a map). Any refusal, a bad
         argument included, raises BugsegError and launches nothing."""
-        st = stream if stream is not None else torch.cuda.current_stream(images.device)
-        nws = int(self.lib.bugseg_canny_workspace_bytes(ctypes.byref(params), B))
-        ws = workspace
-        if ws is None and nws:
-            with torch.cuda.stream(st):
-                ws = torch.empty(nws, dtype=torch.uint8, device=images.device)
-        wp, wn = (0, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
+        sh, w, _keep = self._stream_ws(images, stream, workspace, self.lib.bugseg_canny_workspace_bytes, params, B)
         if stage is None:
-            rc = self.lib.bugseg_canny(self.h, images.data_ptr(), B, ctypes.byref(params), out.data_ptr(), wp, wn,
-                                       stream_handle(st))
+            rc = self.lib.bugseg_canny(self.h, images.data_ptr(), B, ctypes.byref(params), out.data_ptr(), *w, sh)
         else:
             rc = self.lib.bugseg_debug_canny_stage(self.h, images.data_ptr(), B, ctypes.byref(params), int(stage),
-                                                   out.data_ptr(), wp, wn, stream_handle(st))
-        if rc != OK:
-            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
+                                                   out.data_ptr(), *w, sh)
+        self._raise_any(rc)
 
     def confusion(self, pred, gt, B, params: ConfusionParams, acc, stream=None):
         """bugseg_confusion: (B, pred_rows, pred_cols) u8 predictions against (B, gt_rows, gt_cols) u8 labels,
         added into `acc`, an int64 device tensor of num_classes^2 + 1 words (the matrix row by row, rows =
         labels, then the skipped pixels). One launch, no workspace. Any refusal, a bad argument included,
         raises BugsegError and launches nothing."""
-        st = stream if stream is not None else torch.cuda.current_stream(gt.device)
-        rc = self.lib.bugseg_confusion(self.h, pred.data_ptr(), gt.data_ptr(), B, ctypes.byref(params), acc.data_ptr(),
-                                       stream_handle(st))
-        if rc != OK:
-            raise BugsegError(rc, self.lib.bugseg_last_error(self.h).decode(errors="replace"))
+        sh, _, _ = self._stream_ws(gt, stream)
+        self._raise_any(self.lib.bugseg_confusion(self.h, pred.data_ptr(), gt.data_ptr(), B, ctypes.byref(params),
+                                                  acc.data_ptr(), sh))
 
     def plan_info(self, B, H, W, out_kind, bgr_input=False):
         """-> (launches, per-layer algorithmic bytes, plan compulsory bytes, flops) of one forward."""

@@ -334,5 +334,30 @@ int ctx_device(const bugseg_ctx *ctx);
 // uploads `host` (`bytes` long) on the context's private setup stream and waits for it there, so it works
 // while `stream` is being captured (as the resize tables). Freed with the context. BUGSEG_OK or an error.
 int ctx_clahe_tables(bugseg_ctx *ctx, const void *host, size_t bytes, void *stream, const void **dev);
+// launch_fail: the error the last kernel launch left, recorded as "<op> launch: <HIP's text>" (BUGSEG_EHIP);
+// BUGSEG_OK (0) when it left none.
+int launch_fail(bugseg_ctx *ctx, const char *op);
+
+// Makes `dev` the calling thread's HIP device for a scope and puts the previous one back (both runtimes too).
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// whether the byte ranges [a, a + na) and [b, b + nb) share a byte
+inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+// workspace carving: sizes and pointers rounded up to 256 bytes
+__host__ __device__ inline size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
+inline unsigned char *align256(void *p) { return (unsigned char *)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 
 }  // namespace bugseg

@@ -344,18 +344,6 @@ void retire(bugseg_ctx *c, void *p, bool capturing) {
     (void)hipFree(p);
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 // ---------------------------------------------------------------- blob parsing
 struct Reader {
     const unsigned char *p, *end;
@@ -1583,6 +1571,11 @@ void linear_coeffs(int dsize, int ssize, double scale, int *ofs, short *a01) {
 namespace bugseg {
 int ctx_fail(bugseg_ctx *ctx, int code, const char *msg) { return fail(ctx, code, msg); }
 int ctx_device(const bugseg_ctx *ctx) { return ctx->device; }
+int launch_fail(bugseg_ctx *ctx, const char *op) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return BUGSEG_OK;
+    return fail(ctx, BUGSEG_EHIP, std::string(op) + " launch: " + hipGetErrorString(e));
+}
 int ctx_clahe_tables(bugseg_ctx *ctx, const void *host, size_t bytes, void *stream, const void **dev) {
     (void)stream;       // never touched: the upload runs and is waited for on the private setup stream
     if (!ctx->clahe_tabs) {

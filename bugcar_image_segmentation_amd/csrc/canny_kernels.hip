@@ -11,39 +11,35 @@
 //   0 nms     u8 image -> map byte per pixel: 2 strong, 0 weak, 1 none. The tile and a 2-pixel halo are staged
 //             in LDS with the image border replicated; dx, dy and |dx| + |dy| of the tile and a 1-pixel ring are
 //             formed there (0 outside the image) and never reach memory
-//   1 tile    union-find over the candidate (strong or weak) pixels of a 16 x 64 tile in LDS, 8-connected;
-//             label = the frame index of the component's raster-first pixel inside the tile. Only candidate
-//             pixels have a label: the other words of the label image are never read
-//   2 merge   unions across tile borders with atomicMin on the label image
-//   3 mark    every strong pixel walks to its root r and stores ~r there: a negative label is a root whose
+//   1 tile    ccl_common.h's labelling of the candidate (strong or weak) pixels of a 16 x 64 tile in LDS,
+//             8-connected. Only candidate pixels have a label: the other words of the label image are never read
+//   2 merge   ccl_common.h's unions across tile borders, one thread per border pixel of a tile
+//   3 mark   every strong pixel walks to its root r and stores ~r there: a negative label is a root whose
 //             component holds a strong pixel
 //   4 out     out[p] = 255 if p is a candidate and the label of its root is negative, else 0
 // There is no flatten launch: launch 4 walks the same chain a flatten would, once, and writes no label.
 //
 // Workspace: 5 bytes per pixel (the map, one int32 label) plus alignment.
 //
-// Visibility across workgroups (as in road_kernels.hip; MI355X: the L2 of one XCD is not coherent with another's,
-// a CU's L1 is never refreshed by another CU's stores): inside the merge and mark launches every label word is
-// read and written with agent-scope atomics only; everything else a launch reads was written by an earlier
-// launch (a kernel boundary makes it visible). In the mark launch a walker that meets a negative label has
-// found its root already marked.
+// Visibility across workgroups: the rule in ccl_common.h, which the merge and mark launches follow for every
+// label word. In the mark launch a walker that meets a negative label has found its root already marked.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
-#include <string>
 
 #include "bugseg_internal.h"
+#include "ccl_common.h"
 #include "../../include/bugseg.h"
 
 namespace {
+
+using namespace bugseg;
 
 constexpr int THREADS = 256;
 constexpr int NM_TH = 32, NM_TW = 64;     // nms: output tile
 constexpr int NM_PH = NM_TH + 4, NM_PW = NM_TW + 4;     // pixels with the 2-pixel halo
 constexpr int NM_GH = NM_TH + 2, NM_GW = NM_TW + 2;     // gradients with the 1-pixel ring
-constexpr int LT_TH = 16, LT_TW = 64;     // labelling: tile (LT_TH * LT_TW labels in LDS)
-constexpr int LT_N = LT_TH * LT_TW;
 constexpr int LT_BORDER = LT_TW + 2 * (LT_TH - 1);     // merge: the pixels of a tile with a neighbour in another
 constexpr int TG22 = 13573;               // int(tan(22.5 deg) * 2^15 + 0.5)
 constexpr uint8_t STRONG = 2, WEAK = 0, NONE = 1;
@@ -60,7 +56,6 @@ struct CannyArgs {
     int tiles_x;          // of the launch's tiling
 };
 
-__host__ __device__ inline size_t canny_npad(size_t n) { return (n + 255) & ~(size_t)255; }
 __device__ inline bool cand(uint8_t m) { return m == STRONG || m == WEAK; }
 
 // ---------------------------------------------------------------- 0: gradient and non-maximum suppression
@@ -120,113 +115,35 @@ __global__ __launch_bounds__(THREADS) void canny_nms_kernel(CannyArgs a) {
     }
 }
 
-// ---------------------------------------------------------------- union-find (as road_kernels.hip)
-// Labels only decrease and label[x] <= x always, so the forest stays acyclic under any interleaving; the
-// root of a set is its smallest index, i.e. its raster-first pixel.
-__device__ inline int ld_wg(int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline int ld_agent(int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// ---------------------------------------------------------------- 1, 2: labelling (ccl_common.h)
+// The pixels of one frame: a candidate joins its W, NW, N and NE candidate neighbours, any other pixel nothing.
+struct CannyPixels {
+    static constexpr bool HAS_BG = false, HAS_NONE = true;
+    const uint8_t *map;
+    int *label;
+    int W, H;
+    __device__ CannyPixels(const CannyArgs &a, size_t f)
+        : map(a.map + f * a.map_stride), label(a.label + f * a.n), W(a.cols), H(a.rows) {}
+    __device__ uint8_t kind(int p) const { return cand(map[p]) ? 1 : 2; }
+    __device__ void store(int p, int root) const { label[p] = root; }
+};
 
-template <bool LDS>
-__device__ inline int uf_find(int *lab, int x) {
-    for (;;) {
-        int p = LDS ? ld_wg(lab + x) : ld_agent(lab + x);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-template <bool LDS>
-__device__ inline void uf_union(int *lab, int a, int b) {
-    for (;;) {
-        a = uf_find<LDS>(lab, a);
-        b = uf_find<LDS>(lab, b);
-        if (a == b) return;
-        if (a > b) { int t = a; a = b; b = t; }
-        int old = atomicMin(lab + b, a);   // vector atomic (LDS: ds_min, global: device scope)
-        if (old == b) return;
-        b = old;
-    }
-}
-
-// ---------------------------------------------------------------- 1: per-tile labelling in LDS
-// A candidate pixel joins its W, NW, N and NE candidate neighbours.
 __global__ __launch_bounds__(THREADS) void canny_tile_kernel(CannyArgs a) {
-    __shared__ int lab[LT_N];
-    __shared__ uint8_t kind[LT_N];
-    const int W = a.cols, H = a.rows;
     const int tyi = blockIdx.x / a.tiles_x, txi = blockIdx.x - tyi * a.tiles_x;
-    const int x0 = txi * LT_TW, y0 = tyi * LT_TH;
-    const size_t f = blockIdx.y;
-    const uint8_t *map = a.map + f * a.map_stride;
-    const int tid = threadIdx.x;
-    // a tile row is one wave (LT_TW = 64 lanes): every candidate starts at the first pixel of its horizontal
-    // run, found from the ballot, so no union is needed along rows
-    static_assert(LT_TW == 64 && THREADS % 64 == 0, "one wave per tile row");
-    for (int i = tid; i < LT_N; i += THREADS) {
-        int ly = i / LT_TW, lx = i - ly * LT_TW;
-        int gy = y0 + ly, gx = x0 + lx;
-        uint8_t kd = (gy < H && gx < W && cand(map[(size_t)gy * W + gx])) ? 1 : 0;
-        unsigned long long same = __ballot(kd == 1);
-        unsigned long long brk = ~same & ((1ull << lx) - 1ull);       // lanes below that are no candidates
-        int start = brk ? 64 - __clzll((long long)brk) : 0;
-        kind[i] = kd;
-        lab[i] = kd ? ly * LT_TW + start : i;
-    }
-    __syncthreads();
-    // rows are joined where an overlap of two runs starts (the pixels after it hang together through both
-    // rows); a diagonal only where no straight neighbour makes the same link
-    for (int i = tid; i < LT_N; i += THREADS) {
-        int ly = i / LT_TW, lx = i - ly * LT_TW;
-        if (!kind[i] || ly == 0) continue;
-        bool up = kind[i - LT_TW];
-        bool w = lx > 0 && kind[i - 1];
-        bool nw = lx > 0 && kind[i - LT_TW - 1];
-        if (up && !(w && nw)) uf_union<true>(lab, i, i - LT_TW);
-        if (!up) {
-            if (nw && !w) uf_union<true>(lab, i, i - LT_TW - 1);
-            if (lx + 1 < LT_TW && kind[i - LT_TW + 1]) uf_union<true>(lab, i, i - LT_TW + 1);
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < LT_N; i += THREADS) {
-        if (!kind[i]) continue;                 // (a candidate lies inside the image)
-        int ly = i / LT_TW, lx = i - ly * LT_TW;
-        int r = uf_find<true>(lab, i);
-        int ry = r / LT_TW, rx = r - ry * LT_TW;
-        a.label[f * a.n + (size_t)(y0 + ly) * W + x0 + lx] = (y0 + ry) * W + x0 + rx;
-    }
+    label_tile<THREADS>(CannyPixels(a, blockIdx.y), txi * LT_TW, tyi * LT_TH);
 }
 
-// ---------------------------------------------------------------- 2: merge across tile borders
-// Every candidate whose W, NW, N or NE neighbour lies in another tile joins it if it is a candidate. One
-// thread per pixel of a tile's top row, left column and right column (LT_BORDER of them), tiles along grid x.
+// One thread per pixel of a tile's top row, left column and right column (LT_BORDER of them), tiles along grid x.
 __global__ __launch_bounds__(THREADS) void canny_merge_kernel(CannyArgs a) {
-    const int W = a.cols, H = a.rows;
     const long long idx = (long long)blockIdx.x * THREADS + threadIdx.x;
     const int tile = (int)(idx / LT_BORDER), k = (int)(idx - (long long)tile * LT_BORDER);
     const int tyi = tile / a.tiles_x, txi = tile - tyi * a.tiles_x;
     const int ty = k < LT_TW ? 0 : (k - LT_TW) % (LT_TH - 1) + 1;
     const int tx = k < LT_TW ? k : k < LT_TW + LT_TH - 1 ? 0 : LT_TW - 1;
     const int y = tyi * LT_TH + ty, x = txi * LT_TW + tx;
-    if (y >= H || x >= W) return;               // (also every thread past the last tile: its y is past H)
-    const int p = y * W + x;
-    const size_t f = blockIdx.y;
-    const uint8_t *map = a.map + f * a.map_stride;
-    int *lab = a.label + f * a.n;
-    if (!cand(map[p])) return;
-    // As inside a tile, a straight link is made only where an overlap of two runs starts along the border
-    // (after it, the pixels on either side hang together along the border, through links made in their tiles
-    // or by this launch), and a diagonal only where no straight neighbour makes the same link.
-    const bool wk = x > 0 && cand(map[p - 1]), nk = y > 0 && cand(map[p - W]);
-    const bool nwk = x > 0 && y > 0 && cand(map[p - W - 1]);
-    // (the pixel in a tile's corner makes both links whatever its neighbours: each rule would lean on the other)
-    const bool corner = tx == 0 && ty == 0;
-    if (tx == 0 && wk && (corner || !(nk && nwk))) uf_union<false>(lab, p, p - 1);
-    if (ty == 0 && nk && (corner || !(wk && nwk))) uf_union<false>(lab, p, p - W);
-    if (y > 0 && !nk) {
-        if ((ty == 0 || tx == 0) && nwk && !wk) uf_union<false>(lab, p, p - W - 1);
-        if ((ty == 0 || tx == LT_TW - 1) && x + 1 < W && cand(map[p - W + 1])) uf_union<false>(lab, p, p - W + 1);
-    }
+    if (y >= a.rows || x >= a.cols) return;     // (also every thread past the last tile: its y is past the frame)
+    const CannyPixels px(a, blockIdx.y);
+    link_border(px, px.label, x, y, tx, ty);
 }
 
 // ---------------------------------------------------------------- 3: mark the roots of strong pixels
@@ -266,7 +183,7 @@ __global__ __launch_bounds__(THREADS) void canny_out_kernel(CannyArgs a) {
 }
 
 // n is checked: B * n fits an int with one more block of THREADS indices
-size_t canny_ws_bytes(size_t n, int B) { return (size_t)B * (canny_npad(n) + 4 * n) + 256; }
+size_t canny_ws_bytes(size_t n, int B) { return (size_t)B * (pad256(n) + 4 * n) + 256; }
 
 bool canny_shape_ok(const bugseg_canny_params *p, int B) {
     if (B < 1 || B > 65535 || p->rows < 1 || p->cols < 1) return false;
@@ -281,24 +198,9 @@ bool canny_shape_ok(const bugseg_canny_params *p, int B) {
     return std::max(nms_tiles, lab_tiles) * THREADS <= (long long)UINT_MAX;
 }
 
-struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~Guard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-bool overlap(const uint8_t *x, const uint8_t *y, size_t bytes) { return x < y + bytes && y < x + bytes; }
-
 // stage -1: the whole call; 0: launch 0 alone, the map into `out`; 1: launches 1-4 alone, `in` read as a map
 int canny(bugseg_ctx *ctx, const uint8_t *in, int B, const bugseg_canny_params *p, uint8_t *out, void *ws, size_t ws_bytes,
           int stage, void *stream) {
-    using bugseg::ctx_fail;
     if (!ctx || !in || !p || !out) return ctx_fail(ctx, BUGSEG_EINVAL, "canny: NULL argument");
     if (B < 1) return ctx_fail(ctx, BUGSEG_EINVAL, "canny: B must be at least 1");
     if (B > 65535) return ctx_fail(ctx, BUGSEG_EINVAL, "canny: B above 65535");
@@ -307,14 +209,14 @@ int canny(bugseg_ctx *ctx, const uint8_t *in, int B, const bugseg_canny_params *
     const size_t n = (size_t)p->rows * p->cols;
     if (!ws || ws_bytes < canny_ws_bytes(n, B))
         return ctx_fail(ctx, BUGSEG_EINVAL, "canny: workspace missing or smaller than bugseg_canny_workspace_bytes()");
-    if (overlap(out, in, n * B)) return ctx_fail(ctx, BUGSEG_EINVAL, "canny: out_dev overlaps the input");
-    Guard g(bugseg::ctx_device(ctx));
+    if (ranges_overlap(out, n * B, in, n * B)) return ctx_fail(ctx, BUGSEG_EINVAL, "canny: out_dev overlaps the input");
+    DeviceGuard g(ctx_device(ctx));
     CannyArgs a;
     a.img = in; a.out = out;
     a.B = B; a.rows = p->rows; a.cols = p->cols; a.low = p->low; a.high = p->high;
     a.n = (int)n;
-    unsigned char *w = (unsigned char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    a.mapw = w; a.map = w; a.map_stride = canny_npad(n);
+    unsigned char *w = align256(ws);
+    a.mapw = w; a.map = w; a.map_stride = pad256(n);
     a.label = (int *)(w + (size_t)B * a.map_stride);
     if (stage == 0) { a.mapw = out; a.map_stride = n; }
     if (stage == 1) { a.map = in; a.map_stride = n; }
@@ -336,11 +238,7 @@ int canny(bugseg_ctx *ctx, const uint8_t *in, int B, const bugseg_canny_params *
         case 3: hipLaunchKernelGGL(canny_mark_kernel, px, blk, 0, s, a); break;
         default: hipLaunchKernelGGL(canny_out_kernel, px, blk, 0, s, a); break;
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            std::string m = std::string("canny launch: ") + hipGetErrorString(e);
-            return ctx_fail(ctx, BUGSEG_EHIP, m.c_str());
-        }
+        if (int rc = launch_fail(ctx, "canny")) return rc;
     }
     return BUGSEG_OK;
 }

@@ -21,7 +21,6 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <string>
 
 #include "bugseg_internal.h"
 #include "../../include/bugseg.h"
@@ -324,18 +323,6 @@ const ClaheTables &host_tables() {
 }
 
 // ---------------------------------------------------------------- host: the call
-struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~Guard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 // The shape checks every entry shares; nullptr when the parameters are usable.
 const char *bad_shape(const bugseg_clahe_params *p, int B) {
     if (B < 1) return "clahe: B must be at least 1";
@@ -352,16 +339,12 @@ const char *bad_shape(const bugseg_clahe_params *p, int B) {
 
 size_t lut_bytes(const bugseg_clahe_params *p, int B) { return (size_t)B * p->tiles_x * p->tiles_y * 256; }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 enum { STAGE_LAB = 0, STAGE_LUTS = 1, STAGE_BGR = 2, STAGE_LAUNCH1 = 3, STAGE_LAUNCH2 = 4, STAGE_ALL = 5 };
 
 int clahe_run(bugseg_ctx *ctx, const uint8_t *in, int B, const bugseg_clahe_params *p, int stage, uint8_t *out, void *ws,
               size_t ws_bytes, void *stream) {
     using bugseg::ctx_fail;
+    using bugseg::ranges_overlap;
     if (!ctx || !p) return ctx_fail(ctx, BUGSEG_EINVAL, "clahe: NULL argument");
     if (stage < 0 || stage > STAGE_ALL) return ctx_fail(ctx, BUGSEG_EINVAL, "clahe: stage must be in [0, 4]");
     const bool writes_out = stage != STAGE_LAUNCH1;
@@ -371,13 +354,13 @@ int clahe_run(bugseg_ctx *ctx, const uint8_t *in, int B, const bugseg_clahe_para
     const size_t frames = (size_t)B * p->rows * p->cols * 3, nlut = lut_bytes(p, B);
     if (uses_ws && (!ws || ws_bytes < nlut))
         return ctx_fail(ctx, BUGSEG_EINVAL, "clahe: workspace missing or smaller than bugseg_clahe_workspace_bytes()");
-    if (writes_out && overlap(in, frames, out, stage == STAGE_LUTS ? nlut : frames))
+    if (writes_out && ranges_overlap(in, frames, out, stage == STAGE_LUTS ? nlut : frames))
         return ctx_fail(ctx, BUGSEG_EINVAL, "clahe: out_dev overlaps the input");
-    if (uses_ws && (overlap(ws, nlut, in, frames) || (writes_out && overlap(ws, nlut, out, frames))))
+    if (uses_ws && (ranges_overlap(ws, nlut, in, frames) || (writes_out && ranges_overlap(ws, nlut, out, frames))))
         return ctx_fail(ctx, BUGSEG_EINVAL, "clahe: the workspace overlaps a frame buffer");
     const void *tabs = nullptr;
     if (int rc = bugseg::ctx_clahe_tables(ctx, &host_tables(), sizeof(ClaheTables), stream, &tabs)) return rc;
-    Guard g(bugseg::ctx_device(ctx));
+    bugseg::DeviceGuard g(bugseg::ctx_device(ctx));
     ClaheArgs a;
     a.in = in; a.out = out; a.t = (const ClaheTables *)tabs;
     a.luts = stage == STAGE_LUTS ? out : (uint8_t *)ws;
@@ -409,11 +392,7 @@ int clahe_run(bugseg_ctx *ctx, const uint8_t *in, int B, const bugseg_clahe_para
         if (launch == 0 && l1) hipLaunchKernelGGL(clahe_luts_kernel, tiles, blk, 0, s, a);
         else if (launch == 1 && l2) hipLaunchKernelGGL(clahe_pixels_kernel, px, blk, 0, s, a);
         else continue;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            std::string m = std::string("clahe launch: ") + hipGetErrorString(e);
-            return ctx_fail(ctx, BUGSEG_EHIP, m.c_str());
-        }
+        if (int rc = bugseg::launch_fail(ctx, "clahe")) return rc;
     }
     return BUGSEG_OK;
 }

@@ -67,18 +67,6 @@ int dl_fail(bugseg_dl *c, int code, const std::string &m) {
     return code;
 }
 
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 void *bufp(bugseg_dl *c, int id) { return static_cast<char *>(c->arena) + c->buf_off[id]; }
 
 bool in_w(const bugseg_dl *c, long off, long bytes) { return off >= 0 && bytes >= 0 && off + bytes <= (long)c->w_bytes; }
@@ -345,7 +333,7 @@ int bugseg_dl_create(int device, int precision, bugseg_dl **out) {
     c->device = device;
     c->prec = precision == BUGSEG_BF16 ? PREC_BF16 : PREC_F32;
     {   // the class LUT lives as long as the context: identity until one is set
-        DevGuard g(device);
+        DeviceGuard g(device);
         uint8_t id[256];
         for (int k = 0; k < 256; ++k) id[k] = (uint8_t)k;
         void *p = nullptr;
@@ -363,7 +351,7 @@ int bugseg_dl_create(int device, int precision, bugseg_dl **out) {
 
 int bugseg_dl_destroy(bugseg_dl *c) {
     if (!c) return BUGSEG_OK;
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     if (c->dev_w) (void)hipFree(c->dev_w);
     if (c->arena) (void)hipFree(c->arena);
     if (c->dev_lut) (void)hipFree(c->dev_lut);
@@ -373,7 +361,7 @@ int bugseg_dl_destroy(bugseg_dl *c) {
 
 int bugseg_dl_load_weights(bugseg_dl *c, const void *blob, size_t bytes) {
     if (!c || !blob || bytes == 0 || bytes >= (size_t)1 << 31) return dl_fail(c, BUGSEG_EINVAL, "bad weight blob");
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     if (c->dev_w) { (void)hipDeviceSynchronize(); (void)hipFree(c->dev_w); c->dev_w = nullptr; }
     // the blob, then 256 zero bytes at a 256-B boundary (the implicit-GEMM conv's padding taps read them)
     const size_t zoff = (bytes + 255) / 256 * 256;
@@ -440,7 +428,7 @@ int bugseg_dl_set_plan(bugseg_dl *c, const int32_t *ops, int nops, const uint64_
     // validate against the new plan before touching the old one
     const int rc = validate_plan(c, c->prec, c->w_bytes, ops, nops, buf_bytes, nbufs, B, Hc, Wc, v, bb, off, total);
     if (rc != BUGSEG_OK) return rc;
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     if (c->arena) {
         (void)hipDeviceSynchronize();   // a forward of the old plan may still be running on any stream
         (void)hipFree(c->arena);
@@ -520,7 +508,7 @@ int bugseg_dl_forward(bugseg_dl *c, const uint8_t *rgb_dev, int B, int H, int W,
     if (!c || !rgb_dev || !out_dev) return dl_fail(c, BUGSEG_EINVAL, "null argument");
     if (c->ops.empty()) return dl_fail(c, BUGSEG_ESTATE, "forward before set_plan");
     if (const int rc = check_frame(c, B, H, W)) return rc;
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     DlIo io;
     io.img = rgb_dev; io.H = H; io.W = W; io.out = out_dev;
     return run_plan(c, io, static_cast<hipStream_t>(stream));
@@ -539,7 +527,7 @@ int bugseg_dl_set_class_lut(bugseg_dl *c, const uint8_t *lut, int n) {
     }
     uint8_t host[256];
     for (int k = 0; k < 256; ++k) host[k] = lut && k < n ? lut[k] : (uint8_t)k;
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     // a synchronous copy from pageable memory: it orders after every earlier forward's reads of the
     // old table, and leaves nothing for a later captured step to copy
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(c->dev_lut, host, 256, hipMemcpyHostToDevice) != hipSuccess)
@@ -555,7 +543,7 @@ int bugseg_dl_forward_classes(bugseg_dl *c, const uint8_t *img_dev, int bgr, int
     if (c->ops.empty()) return dl_fail(c, BUGSEG_ESTATE, "forward before set_plan");
     if (const int rc = check_frame(c, B, H, W)) return rc;
     if (const int rc = check_classes(c, H, row0, row1)) return rc;
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     DlIo io;
     io.img = img_dev; io.bgr = bgr; io.H = H; io.W = W; io.seg = seg_dev; io.row0 = row0; io.row1 = row1;
     return run_plan(c, io, static_cast<hipStream_t>(stream));
@@ -569,7 +557,7 @@ int bugseg_dl_classes_from_logits(bugseg_dl *c, int B, int H, int W, uint8_t *se
         return dl_fail(c, BUGSEG_EINVAL, "the last forward ran " + std::to_string(c->last.H) + "x" + std::to_string(c->last.W) +
                                              " frames, not " + std::to_string(H) + "x" + std::to_string(W));
     if (const int rc = check_classes(c, H, row0, row1)) return rc;
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     DlIo io = c->last;
     io.seg = seg_dev; io.row0 = row0; io.row1 = row1;
     const hipError_t e = run_op(c, *argmax_op(c), io, static_cast<hipStream_t>(stream));
@@ -578,7 +566,7 @@ int bugseg_dl_classes_from_logits(bugseg_dl *c, int B, int H, int W, uint8_t *se
 
 int bugseg_dl_launch_op(bugseg_dl *c, int op, void *stream) {
     if (!c || op < 0 || op >= (int)c->ops.size() || !c->last.img) return dl_fail(c, BUGSEG_EINVAL, "no such op / no forward yet");
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     const hipError_t e = run_op(c, c->ops[op], c->last, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? BUGSEG_OK : dl_fail(c, BUGSEG_EHIP, hipGetErrorString(e));
 }
@@ -586,7 +574,7 @@ int bugseg_dl_launch_op(bugseg_dl *c, int op, void *stream) {
 int bugseg_dl_read_buffer(bugseg_dl *c, int buf, void *dst_dev, size_t bytes, void *stream) {
     if (!c || !dst_dev || !c->arena || buf < 0 || buf >= (int)c->buf_bytes.size() || bytes > c->buf_bytes[buf])
         return dl_fail(c, BUGSEG_EINVAL, "no such buffer / too many bytes");
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     const hipError_t e = hipMemcpyAsync(dst_dev, bufp(c, buf), bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? BUGSEG_OK : dl_fail(c, BUGSEG_EHIP, hipGetErrorString(e));
 }

@@ -32,7 +32,6 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <string>
 
 #include "bugseg_internal.h"
 #include "../../include/bugseg.h"
@@ -171,18 +170,6 @@ __global__ __launch_bounds__(THREADS) void eval_confusion_kernel(EvalArgs a) {
     }
 }
 
-struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~Guard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -205,7 +192,7 @@ int bugseg_confusion(bugseg_ctx *ctx, const uint8_t *pred_dev, const uint8_t *gt
     if (!same && ((long long)p->gt_rows * p->pred_rows > lim || (long long)p->gt_cols * p->pred_cols > lim))
         return ctx_fail(ctx, BUGSEG_EINVAL, "confusion: label rows * prediction rows (or cols * cols) too large for an int32 index");
     if ((uintptr_t)acc_dev & 7) return ctx_fail(ctx, BUGSEG_EINVAL, "confusion: acc_dev is not 8-byte aligned");
-    Guard g(bugseg::ctx_device(ctx));
+    bugseg::DeviceGuard g(bugseg::ctx_device(ctx));
     EvalArgs a;
     a.pred = pred_dev; a.gt = gt_dev; a.acc = (unsigned long long *)acc_dev;
     a.n_total = (unsigned)(gn * B);
@@ -233,12 +220,7 @@ int bugseg_confusion(bugseg_ctx *ctx, const uint8_t *pred_dev, const uint8_t *gt
     groups = groups < 1 ? 1 : groups > (unsigned)MAX_GROUPS ? (unsigned)MAX_GROUPS : groups;
     const size_t lds = (size_t)(LDS_TABLE_WORDS + a.copies * a.bins) * 4;
     hipLaunchKernelGGL(eval_confusion_kernel, dim3(groups), dim3(THREADS), lds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        std::string m = std::string("confusion launch: ") + hipGetErrorString(e);
-        return ctx_fail(ctx, BUGSEG_EHIP, m.c_str());
-    }
-    return BUGSEG_OK;
+    return bugseg::launch_fail(ctx, "confusion");
 }
 
 }

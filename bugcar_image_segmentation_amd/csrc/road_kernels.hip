@@ -9,34 +9,31 @@
 //
 // Launch sequence of one call (fixed: nothing is read back by the host), B frames each:
 //   0 close     u8 map -> closed mask, separable OR then AND from LDS tiles with a halo
-//   1 tile      union-find per 16 x 64 tile in LDS; label = the frame index of the region's raster-first
-//               pixel inside the tile; clears the per-root counters of the tile's pixels
-//   2 merge     unions across tile borders with atomicMin on the label image
+//   1 tile      ccl_common.h's labelling of a 16 x 64 tile in LDS; clears the per-root counters of its pixels
+//   2 merge     ccl_common.h's unions across tile borders, one thread per pixel of the frame
 //   3 flatten   label[p] = root(p)
 //   4 count     band and ring counts per root, outside marks
 //   5 sub       every root adds its band count to itself and its ancestors
 //   6 keep      per root: the nearest qualifying node, from the root upwards
 //   7 out       out[p] = keep[label[p]]
 //
-// Visibility across workgroups (MI355X: the L2 of one XCD is not coherent with another's, a CU's L1 is
-// never refreshed by another CU's stores): inside the merge and sub launches every word another workgroup
-// may change is read and written with agent-scope atomics only; everything else a launch reads was written
-// by an earlier launch (a kernel boundary makes it visible). The flatten launch reads labels that other
-// workgroups overwrite with their roots: a stale read is an older, still valid, ancestor.
+// Visibility across workgroups: the rule in ccl_common.h, which the merge and sub launches follow. The flatten
+// launch reads labels that other workgroups overwrite with their roots: a stale read is an older, still valid,
+// ancestor.
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <string>
 
 #include "bugseg_internal.h"
+#include "ccl_common.h"
 #include "../../include/bugseg.h"
 
 namespace {
 
+using namespace bugseg;
+
 constexpr int THREADS = 256;
 constexpr int CL_TH = 32, CL_TW = 64;     // closing: output tile
-constexpr int LT_TH = 16, LT_TW = 64;     // labelling: tile (LT_TH * LT_TW labels in LDS)
-constexpr int LT_N = LT_TH * LT_TW;
 constexpr int OUTSIDE = INT_MIN;          // sub[] of a background root that touches the image border
 constexpr int N_OPS = 8;
 
@@ -49,8 +46,6 @@ struct RoadArgs {
     int n;                // rows * cols
     size_t npad;          // n rounded up to 256
 };
-
-__host__ __device__ inline size_t road_npad(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------- 0: closing
 // One workgroup = one CL_TH x CL_TW output tile of one frame. a = k / 2 is the anchor of both passes: d(y, x)
@@ -116,92 +111,30 @@ __global__ __launch_bounds__(THREADS) void road_close_kernel(RoadArgs a) {
     }
 }
 
-// ---------------------------------------------------------------- union-find
-// Labels only decrease and label[x] <= x always, so the forest stays acyclic under any interleaving; the
-// root of a set is its smallest index, i.e. its raster-first pixel.
-__device__ inline int ld_wg(int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline int ld_agent(int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-template <bool LDS>
-__device__ inline int uf_find(int *lab, int x) {
-    for (;;) {
-        int p = LDS ? ld_wg(lab + x) : ld_agent(lab + x);
-        if (p == x) return x;
-        x = p;
+// ---------------------------------------------------------------- 1, 2: labelling (ccl_common.h)
+// The pixels of one frame: the closed mask's foreground is 8-connected, its background 4-connected.
+struct RoadPixels {
+    static constexpr bool HAS_BG = true, HAS_NONE = false;
+    const uint8_t *closed;
+    int *label, *band, *ring, *sub;
+    int W, H;
+    __device__ RoadPixels(const RoadArgs &a, size_t f)
+        : closed(a.closed + f * a.npad), label(a.label + f * a.n), band(a.band + f * a.n), ring(a.ring + f * a.n),
+          sub(a.sub + f * a.n), W(a.cols), H(a.rows) {}
+    __device__ uint8_t kind(int p) const { return closed[p]; }
+    __device__ void store(int p, int root) const {
+        label[p] = root;
+        band[p] = 0;
+        ring[p] = 0;
+        sub[p] = 0;
     }
-}
+};
 
-template <bool LDS>
-__device__ inline void uf_union(int *lab, int a, int b) {
-    for (;;) {
-        a = uf_find<LDS>(lab, a);
-        b = uf_find<LDS>(lab, b);
-        if (a == b) return;
-        if (a > b) { int t = a; a = b; b = t; }
-        int old = atomicMin(lab + b, a);   // vector atomic (LDS: ds_min, global: device scope)
-        if (old == b) return;
-        b = old;
-    }
-}
-
-// ---------------------------------------------------------------- 1: per-tile labelling in LDS
-// A pixel joins its W and N neighbours of the same kind, a foreground pixel its NW and NE ones too.
 __global__ __launch_bounds__(THREADS) void road_tile_kernel(RoadArgs a) {
-    __shared__ int lab[LT_N];
-    __shared__ uint8_t kind[LT_N];
-    const int W = a.cols, H = a.rows;
-    const int x0 = blockIdx.x * LT_TW, y0 = blockIdx.y * LT_TH;
-    const size_t f = blockIdx.z;
-    const uint8_t *closed = a.closed + f * a.npad;
-    const int tid = threadIdx.x;
-    // a tile row is one wave (LT_TW = 64 lanes): every pixel starts at the first pixel of its horizontal run,
-    // found from the ballot of its kind, so no union is needed along rows
-    static_assert(LT_TW == 64 && THREADS % 64 == 0, "one wave per tile row");
-    for (int i = tid; i < LT_N; i += THREADS) {
-        int ly = i / LT_TW, lx = i - ly * LT_TW;
-        int gy = y0 + ly, gx = x0 + lx;
-        // 2: outside the image, joins nothing
-        uint8_t kd = (gy < H && gx < W) ? closed[(size_t)gy * W + gx] : 2;
-        unsigned long long m1 = __ballot(kd == 1), m0 = __ballot(kd == 0);
-        unsigned long long same = kd == 1 ? m1 : kd == 0 ? m0 : 0ull;
-        unsigned long long brk = ~same & ((1ull << lx) - 1ull);       // lanes below of another kind
-        int start = brk ? 64 - __clzll((long long)brk) : 0;
-        kind[i] = kd;
-        lab[i] = kd == 2 ? i : ly * LT_TW + start;
-    }
-    __syncthreads();
-    // rows are joined where an overlap of two runs starts (the pixels after it hang together through both
-    // rows); a diagonal only where no straight neighbour makes the same link
-    for (int i = tid; i < LT_N; i += THREADS) {
-        int ly = i / LT_TW, lx = i - ly * LT_TW;
-        uint8_t kd = kind[i];
-        if (kd == 2 || ly == 0) continue;
-        uint8_t up = kind[i - LT_TW];
-        bool wsame = lx > 0 && kind[i - 1] == kd;
-        uint8_t nw = lx > 0 ? kind[i - LT_TW - 1] : 2;
-        if (up == kd && !(wsame && nw == kd)) uf_union<true>(lab, i, i - LT_TW);
-        if (kd == 1 && up != 1) {
-            if (nw == 1 && !wsame) uf_union<true>(lab, i, i - LT_TW - 1);
-            if (lx + 1 < LT_TW && kind[i - LT_TW + 1] == 1) uf_union<true>(lab, i, i - LT_TW + 1);
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < LT_N; i += THREADS) {
-        int ly = i / LT_TW, lx = i - ly * LT_TW;
-        int gy = y0 + ly, gx = x0 + lx;
-        if (gy >= H || gx >= W) continue;
-        int r = uf_find<true>(lab, i);
-        int ry = r / LT_TW, rx = r - ry * LT_TW;
-        size_t g = f * a.n + (size_t)gy * W + gx;
-        a.label[g] = (y0 + ry) * W + x0 + rx;
-        a.band[g] = 0;
-        a.ring[g] = 0;
-        a.sub[g] = 0;
-    }
+    label_tile<THREADS>(RoadPixels(a, blockIdx.z), blockIdx.x * LT_TW, blockIdx.y * LT_TH);
 }
 
-// ---------------------------------------------------------------- 2: merge across tile borders
-// Every pixel whose W, NW, N or NE neighbour lies in another tile joins it under its kind's connectivity.
+// One thread per pixel of the frame: those with no neighbour in another tile leave at once.
 __global__ __launch_bounds__(THREADS) void road_merge_kernel(RoadArgs a) {
     const int W = a.cols;
     const int p = blockIdx.x * THREADS + threadIdx.x;
@@ -209,24 +142,8 @@ __global__ __launch_bounds__(THREADS) void road_merge_kernel(RoadArgs a) {
     const int y = p / W, x = p - y * W;
     const int ty = y % LT_TH, tx = x % LT_TW;
     if (ty != 0 && tx != 0 && tx != LT_TW - 1) return;
-    const size_t f = blockIdx.y;
-    const uint8_t *closed = a.closed + f * a.npad;
-    int *lab = a.label + f * a.n;
-    // As inside a tile, a straight link is made only where an overlap of two runs starts along the border
-    // (after it, the pixels on either side hang together along the border, through links made in their tiles
-    // or by this launch), and a diagonal only where no straight neighbour makes the same link: a uniform
-    // region crossing many tiles costs one atomic per border, not one per border pixel.
-    const uint8_t kd = closed[p];
-    const uint8_t wk = x > 0 ? closed[p - 1] : 2, nk = y > 0 ? closed[p - W] : 2;
-    const uint8_t nwk = (x > 0 && y > 0) ? closed[p - W - 1] : 2;
-    // (the pixel in a tile's corner makes both links whatever its neighbours: each rule would lean on the other)
-    const bool corner = tx == 0 && ty == 0;
-    if (tx == 0 && wk == kd && (corner || !(nk == kd && nwk == kd))) uf_union<false>(lab, p, p - 1);
-    if (ty == 0 && nk == kd && (corner || !(wk == kd && nwk == kd))) uf_union<false>(lab, p, p - W);
-    if (kd == 1 && y > 0 && nk != 1) {
-        if ((ty == 0 || tx == 0) && nwk == 1 && wk != 1) uf_union<false>(lab, p, p - W - 1);
-        if ((ty == 0 || tx == LT_TW - 1) && x + 1 < W && closed[p - W + 1] == 1) uf_union<false>(lab, p, p - W + 1);
-    }
+    const RoadPixels px(a, blockIdx.y);
+    link_border(px, px.label, x, y, tx, ty);
 }
 
 // ---------------------------------------------------------------- 3: flatten
@@ -350,23 +267,10 @@ __global__ __launch_bounds__(THREADS) void road_out_kernel(RoadArgs a) {
     a.out[f * a.n + p] = (uint8_t)a.band[f * a.n + a.label[f * a.n + p]];
 }
 
-size_t road_ws_bytes(size_t n, int B) { return (size_t)B * (road_npad(n) + 4 * 4 * n) + 256; }
-
-struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~Guard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
+size_t road_ws_bytes(size_t n, int B) { return (size_t)B * (pad256(n) + 4 * 4 * n) + 256; }
 
 int road_filter(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_road_filter_params *p, uint8_t *out, void *ws,
                 size_t ws_bytes, int first, int last, void *stream) {
-    using bugseg::ctx_fail;
     if (!ctx || !seg || !p || !out) return ctx_fail(ctx, BUGSEG_EINVAL, "road filter: NULL argument");
     if (B < 1) return ctx_fail(ctx, BUGSEG_EINVAL, "road filter: B must be at least 1");
     if (p->rows < 1 || p->cols < 1) return ctx_fail(ctx, BUGSEG_EINVAL, "road filter: bad shape");
@@ -382,14 +286,13 @@ int road_filter(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_road_fi
         return ctx_fail(ctx, BUGSEG_EINVAL, "road filter: workspace missing or smaller than bugseg_road_filter_workspace_bytes()");
     if (last < 0 || last > N_OPS) last = N_OPS;
     if (first < 0 || first > last) return ctx_fail(ctx, BUGSEG_EINVAL, "road filter: bad op range");
-    const uint8_t *ob = out, *sb = seg;
-    if (ob < sb + n * B && sb < ob + n * B) return ctx_fail(ctx, BUGSEG_EINVAL, "road filter: out_dev overlaps seg_dev");
-    Guard g(bugseg::ctx_device(ctx));
+    if (ranges_overlap(out, n * B, seg, n * B)) return ctx_fail(ctx, BUGSEG_EINVAL, "road filter: out_dev overlaps seg_dev");
+    DeviceGuard g(ctx_device(ctx));
     RoadArgs a;
     a.seg = seg; a.out = out;
     a.B = B; a.rows = p->rows; a.cols = p->cols; a.k = p->k; a.y_top = p->y_top; a.min_count = p->min_count;
-    a.n = (int)n; a.npad = road_npad(n);
-    unsigned char *w = (unsigned char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    a.n = (int)n; a.npad = pad256(n);
+    unsigned char *w = align256(ws);
     a.closed = w;
     a.label = (int *)(w + (size_t)B * a.npad);
     a.band = a.label + (size_t)B * n;
@@ -413,11 +316,7 @@ int road_filter(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_road_fi
         case 6: hipLaunchKernelGGL(road_keep_kernel, px, blk, 0, s, a); break;
         default: hipLaunchKernelGGL(road_out_kernel, px, blk, 0, s, a); break;
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            std::string m = std::string("road filter launch: ") + hipGetErrorString(e);
-            return ctx_fail(ctx, BUGSEG_EHIP, m.c_str());
-        }
+        if (int rc = launch_fail(ctx, "road filter")) return rc;
     }
     return BUGSEG_OK;
 }

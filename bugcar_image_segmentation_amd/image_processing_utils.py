@@ -29,6 +29,39 @@ import torch
 
 from . import _native as N
 
+def _device_batch(t, name: str, bgr: bool = False):
+    """What every *_device function does first: `t`, a uint8 device tensor of one frame or a batch of them
+    (frames are (h, w), or (h, w, 3) when `bgr`), as a contiguous batch -> (batch, (B, h, w))."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+        raise ValueError(f"{name} must be a uint8 device tensor")
+    nd = 4 if bgr else 3
+    b = t if t.dim() == nd else t.unsqueeze(0)
+    if b.dim() != nd or (bgr and b.shape[3] != 3):
+        raise ValueError(f"{name} must have shape " + ("(B, h, w, 3) or (h, w, 3)" if bgr else "(B, h, w) or (h, w)"))
+    b = b.contiguous()
+    return b, tuple(b.shape[:3])
+
+
+def _out_like(batch: torch.Tensor, name: str, out):
+    """After the parameter checks: refuse an empty batch, then check `out` against the batch or allocate it."""
+    if batch.shape[0] < 1:
+        raise ValueError(f"{name} holds no frame")
+    if out is None:
+        return torch.empty_like(batch)
+    if tuple(out.shape) != tuple(batch.shape) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != batch.device:
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(batch.shape)} on {batch.device}")
+    return out
+
+
+def _host_call(t: torch.Tensor, device_fn, *args):
+    """The host wrappers' tail, after their checks: one frame to the current device, through `device_fn`, back
+    as an owned NumPy array (no torch storage behind it)."""
+    N.require_gpu()
+    if not t.is_cuda:
+        t = t.to(torch.device("cuda", torch.cuda.current_device()))
+    return device_fn(t, *args)[0].cpu().numpy().copy()
+
+
 LENGTH_RATIO = 0.1        # image_processing_utils.py:19
 MASK_AREA_THRESH = 0.4    # image_processing_utils.py:31
 MIN_SIDE = 50
@@ -63,20 +96,9 @@ def road_filter_params(h: int, w: int) -> N.RoadFilterParams:
 def contour_noise_removal_device(segmaps: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """Batched contour_noise_removal on device tensors: (B, h, w) or (h, w) uint8 maps (any non-zero
     value is road) -> (B, h, w) uint8 in {0, 1}, on the current stream. `out` must not overlap the input."""
-    if not isinstance(segmaps, torch.Tensor) or not segmaps.is_cuda or segmaps.dtype != torch.uint8:
-        raise ValueError("segmaps must be a uint8 device tensor")
-    seg = segmaps if segmaps.dim() == 3 else segmaps.unsqueeze(0)
-    if seg.dim() != 3:
-        raise ValueError("segmaps must have shape (B, h, w) or (h, w)")
-    seg = seg.contiguous()
-    B, h, w = seg.shape
+    seg, (B, h, w) = _device_batch(segmaps, "segmaps")
     p = road_filter_params(h, w)
-    if B < 1:
-        raise ValueError("segmaps holds no frame")
-    if out is None:
-        out = torch.empty((B, h, w), dtype=torch.uint8, device=seg.device)
-    elif tuple(out.shape) != (B, h, w) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != seg.device:
-        raise ValueError(f"out must be a contiguous uint8 tensor of shape {(B, h, w)} on {seg.device}")
+    out = _out_like(seg, "segmaps", out)
     with torch.cuda.device(seg.device):
         N.shared_context(seg.device.index).road_filter(seg, B, p, out, torch.cuda.current_stream(seg.device))
     return out
@@ -92,12 +114,9 @@ def contour_noise_removal(segmap):
     if t.dim() != 2:
         raise ValueError("segmap must have shape (h, w)")       # image_processing_utils.py:6 unpacks two
     road_filter_params(*t.shape)                                # the size check, before any device work
-    N.require_gpu()
     if t.dtype != torch.uint8:
         t = (t != 0).to(torch.uint8)
-    if not t.is_cuda:
-        t = t.to(torch.device("cuda", torch.cuda.current_device()))
-    return contour_noise_removal_device(t)[0].cpu().numpy().copy()      # owned: no torch storage behind it
+    return _host_call(t, contour_noise_removal_device)
 
 
 CLAHE_CLIP_LIMIT = 3.0          # image_processing_utils.py:53
@@ -131,20 +150,9 @@ def clahe_device(frames: torch.Tensor, out: torch.Tensor | None = None, clip_lim
                  tile_grid=CLAHE_TILE_GRID) -> torch.Tensor:
     """Batched clahe on device tensors: (B, h, w, 3) or (h, w, 3) uint8 BGR frames -> (B, h, w, 3) uint8 BGR,
     on the current stream. `out` must not overlap the input."""
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
-        raise ValueError("frames must be a uint8 device tensor")
-    f = frames if frames.dim() == 4 else frames.unsqueeze(0)
-    if f.dim() != 4 or f.shape[3] != 3:
-        raise ValueError("frames must have shape (B, h, w, 3) or (h, w, 3)")
-    f = f.contiguous()
-    B, h, w = f.shape[:3]
+    f, (B, h, w) = _device_batch(frames, "frames", bgr=True)
     p = clahe_params(h, w, clip_limit, tile_grid)
-    if B < 1:
-        raise ValueError("frames holds no frame")
-    if out is None:
-        out = torch.empty_like(f)
-    elif tuple(out.shape) != tuple(f.shape) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != f.device:
-        raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(f.shape)} on {f.device}")
+    out = _out_like(f, "frames", out)
     with torch.cuda.device(f.device):
         N.shared_context(f.device.index).clahe(f, B, p, out, torch.cuda.current_stream(f.device))
     return out
@@ -157,10 +165,7 @@ def clahe(img):
     if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
         raise ValueError("img must be an (h, w, 3) uint8 BGR frame")     # cv2.COLOR_BGR2LAB of 8-bit input
     clahe_params(t.shape[0], t.shape[1])                        # the size check, before any device work
-    N.require_gpu()
-    if not t.is_cuda:
-        t = t.to(torch.device("cuda", torch.cuda.current_device()))
-    return clahe_device(t)[0].cpu().numpy().copy()              # owned: no torch storage behind it
+    return _host_call(t, clahe_device)
 
 
 CANNY_LOW, CANNY_HIGH = 50, 150         # image_processing_utils.py:104
@@ -195,20 +200,9 @@ def canny_params(h: int, w: int, threshold1, threshold2, apertureSize: int = 3, 
 def canny_device(images: torch.Tensor, threshold1, threshold2, out: torch.Tensor | None = None) -> torch.Tensor:
     """Batched cv2.Canny(image, threshold1, threshold2) on device tensors: (B, h, w) or (h, w) uint8 images
     -> (B, h, w) uint8 in {0, 255}, on the current stream. `out` must not overlap the input."""
-    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype != torch.uint8:
-        raise ValueError("images must be a uint8 device tensor")
-    im = images if images.dim() == 3 else images.unsqueeze(0)
-    if im.dim() != 3:
-        raise ValueError("images must have shape (B, h, w) or (h, w)")
-    im = im.contiguous()
-    B, h, w = im.shape
+    im, (B, h, w) = _device_batch(images, "images")
     p = canny_params(h, w, threshold1, threshold2)
-    if B < 1:
-        raise ValueError("images holds no frame")
-    if out is None:
-        out = torch.empty((B, h, w), dtype=torch.uint8, device=im.device)
-    elif tuple(out.shape) != (B, h, w) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != im.device:
-        raise ValueError(f"out must be a contiguous uint8 tensor of shape {(B, h, w)} on {im.device}")
+    out = _out_like(im, "images", out)
     with torch.cuda.device(im.device):
         N.shared_context(im.device.index).canny(im, B, p, out, torch.cuda.current_stream(im.device))
     return out
@@ -221,10 +215,7 @@ def canny(img, threshold1, threshold2, apertureSize: int = 3, L2gradient: bool =
     if t.dim() != 2 or t.dtype != torch.uint8:
         raise ValueError("img must be an (h, w) uint8 image")            # cv2.Canny's 8-bit single-channel input
     canny_params(t.shape[0], t.shape[1], threshold1, threshold2, apertureSize, L2gradient)   # before any device work
-    N.require_gpu()
-    if not t.is_cuda:
-        t = t.to(torch.device("cuda", torch.cuda.current_device()))
-    return canny_device(t, threshold1, threshold2)[0].cpu().numpy().copy()      # owned: no torch storage behind it
+    return _host_call(t, canny_device, threshold1, threshold2)
 
 
 def find_intersection_line(line1, line2):
@@ -265,4 +256,4 @@ def create_skeleton(perspective_transformer, input_shape, occupancy_grid_width_i
     occ_grid = perspective_transformer.create_occupancy_grid_device(free_img, occupancy_grid_width_in_m,
                                                                     occupancy_grid_height_in_m, cell_size_in_m)
     edges = canny_device(occ_grid.contiguous().view(torch.uint8), CANNY_LOW, CANNY_HIGH)
-    return edges[0].cpu().numpy().copy()
+    return edges[0].cpu().numpy().copy()      # owned: no torch storage behind it

@@ -5,6 +5,7 @@ separately rounded IEEE op written in the source, which is what the restated Ope
 """
 from __future__ import annotations
 
+import os
 import subprocess
 from pathlib import Path
 
@@ -17,10 +18,15 @@ def build_oracle(force: bool = False) -> Path:
     OUT.mkdir(exist_ok=True)
     src = HERE / "ocv_ref.c"
     if force or not LIB.exists() or src.stat().st_mtime > LIB.stat().st_mtime:
-        cmd = ["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", str(LIB), str(src), "-lm"]
+        # several processes may come here at once (the ranks of tests/test_distributed_gloo.py): each links into a
+        # file of its own and renames it, so that no other ever loads a half-written library
+        tmp = OUT / f"libocvref.{os.getpid()}.so.tmp"
+        cmd = ["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", str(tmp), str(src), "-lm"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
+            tmp.unlink(missing_ok=True)
             raise RuntimeError(f"oracle build failed: {' '.join(cmd)}\n{r.stderr}")
+        os.replace(tmp, LIB)
     return LIB
 
 

@@ -17,7 +17,7 @@ from scipy import ndimage
 S8 = np.ones((3, 3), bool)
 S4 = np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]], bool)
 
-SHAPES = [(50, 64), (53, 50), (50, 67), (100, 120), (150, 200), (256, 512), (480, 640)]
+SHAPES = [(50, 64), (53, 50), (50, 67), (99, 130), (100, 120), (150, 200), (256, 512), (480, 640)]
 
 
 def host_params(h, w):
@@ -373,6 +373,43 @@ def joined_blobs(h, w, gap):
     return m
 
 
+CORNERS = [(16, 64), (32, 64), (48, 64)]       # (y, x) of the first pixel of a labelling tile (16 x 64 tiles)
+CORNER_SHAPES = ((50, 67), (99, 130))          # k = 1: the closing is the identity, one-pixel lines survive it
+
+
+def corner_diagonal_parts(ne):
+    """Per corner of CORNERS: (the staircase's pixel at the corner, the 2 x 2 blob above the staircase as slices).
+    ne False: the staircase runs down to the right, its only link across the corner is (y - 1, x - 1) -> (y, x);
+    ne True: down to the left, the link is (y - 1, x) -> (y, x - 1)."""
+    parts = []
+    for cy, cx in CORNERS:
+        at = (cy, cx - 1) if ne else (cy, cx)
+        xe = cx + 2 if ne else cx - 3          # the column of the staircase's top end, three rows up
+        parts.append((at, (slice(cy - 5, cy - 3), slice(xe - 1, xe + 1))))
+    return parts
+
+
+def corner_diagonals(h, w, ne):
+    """One-pixel diagonal staircases of five pixels across the tile corners CORNERS, each from a blob above it
+    down to a trunk column that a connector row joins to a band block large enough to be kept: a blob is in the
+    output only through the diagonal link across its corner."""
+    k, y_top, mc = host_params(h, w)
+    assert k == 1 and h >= 50 and w >= 67
+    m = np.zeros((h, w), np.uint8)
+    bw = -(-mc // (h - y_top)) + 2
+    assert 20 < bw < 56
+    m[y_top:, :bw] = 1                         # the band block
+    m[40:y_top, 20] = 1                        # up from it ...
+    trunk = 61 if ne else 66
+    m[40, 20:trunk + 1] = 1                    # ... along the connector row, between the second and third staircase ...
+    m[17:50, trunk] = 1                        # ... to the trunk, which the low end of every staircase touches
+    for (cy, cx), (_, blob) in zip(CORNERS, corner_diagonal_parts(ne)):
+        for t in range(-3, 2):
+            m[cy + t, cx - 1 - t if ne else cx + t] = 1
+        m[blob] = 1
+    return m
+
+
 NOISE = [(50, 64, 0.3, 1), (50, 64, 0.5, 2), (50, 64, 0.6, 3), (50, 64, 0.7, 4),
          (60, 50, 0.3, 5), (60, 50, 0.5, 6), (60, 50, 0.6, 7), (60, 50, 0.7, 8), (100, 120, 0.6, 9)]
 
@@ -385,6 +422,9 @@ def cases_with_ref(h, w):
         k = host_params(h, w)[0]
         cs["blobs_joined"] = joined_blobs(h, w, k - 1)
         cs["blobs_apart"] = joined_blobs(h, w, k)
+    if (h, w) in CORNER_SHAPES:
+        cs["corner_diagonals_nw"] = corner_diagonals(h, w, False)
+        cs["corner_diagonals_ne"] = corner_diagonals(h, w, True)
     for nh, nw, d, seed in NOISE:
         if (nh, nw) == (h, w):
             cs[f"noise_{d}"] = noise(h, w, d, seed)

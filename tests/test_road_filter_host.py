@@ -86,6 +86,28 @@ def test_cases_are_what_they_say(h, w):
     assert case["values_0_255"][0].max() > 1
 
 
+@pytest.mark.parametrize("ne", [False, True], ids=["nw", "ne"])
+@pytest.mark.parametrize("h,w", R.CORNER_SHAPES, ids=lambda v: str(v))
+def test_corner_diagonals_hang_on_the_link_across_the_corner(h, w, ne):
+    names, maps, ref = R.cases_with_ref(h, w)
+    name = "corner_diagonals_ne" if ne else "corner_diagonals_nw"
+    m, out = maps[names.index(name)], ref[names.index(name)]
+    assert R.host_params(h, w)[0] == 1 and np.array_equal(out, m)          # one component, kept whole
+    for (y, x), blob in R.corner_diagonal_parts(ne):
+        assert (y, x + ne) in R.CORNERS
+        # the staircase's pixel at the corner and the one before it lie in diagonally opposite tiles, and no
+        # straight neighbour stands in for the diagonal
+        py, px = y - 1, x + 1 if ne else x - 1
+        assert y % 16 == 0 and {x % 64, px % 64} == {0, 63}
+        assert m[y, x] and m[py, px] and not m[y, px] and not m[py, x]
+        assert out[blob].all()
+        cut = m.copy()
+        cut[y, x] = 0
+        got = R.brute(cut)
+        assert not got[blob].any(), f"the blob above corner {(y, x + ne)} does not depend on the link across it"
+        assert got[h - 1, 0] == 1                                           # (the band block stays)
+
+
 def out_equals(out, mask):
     return np.array_equal(out.astype(bool), mask.astype(bool))
 
