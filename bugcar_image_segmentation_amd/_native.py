@@ -31,6 +31,8 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_road_filter_workspace_bytes", "bugseg_road_filter", "bugseg_debug_road_filter_ops",
             "bugseg_clahe_workspace_bytes", "bugseg_clahe_bgr", "bugseg_debug_clahe_stage", "bugseg_debug_clahe_table",
             "bugseg_canny_workspace_bytes", "bugseg_canny", "bugseg_debug_canny_stage", "bugseg_confusion",
+            "bugseg_bev_warp_image", "bugseg_hough_trig", "bugseg_hough_workspace_bytes", "bugseg_hough_lines",
+            "bugseg_debug_hough_stage",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
@@ -62,6 +64,13 @@ class ClaheParams(ctypes.Structure):
 class CannyParams(ctypes.Structure):
     """bugseg_canny_params: image_processing_utils.canny_params builds and checks them."""
     _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("low", ctypes.c_int), ("high", ctypes.c_int)]
+
+
+class HoughParams(ctypes.Structure):
+    """bugseg_hough_params: image_processing_utils.hough_params builds and checks them."""
+    _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("numangle", ctypes.c_int), ("numrho", ctypes.c_int),
+                ("threshold", ctypes.c_int), ("max_lines", ctypes.c_int), ("rho", ctypes.c_float),
+                ("theta", ctypes.c_float), ("min_theta", ctypes.c_float)]
 
 
 class ConfusionParams(ctypes.Structure):
@@ -132,6 +141,11 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_canny": (i, [vp, vp, i, ctypes.POINTER(CannyParams), vp, vp, sz, vp]),
             "bugseg_debug_canny_stage": (i, [vp, vp, i, ctypes.POINTER(CannyParams), i, vp, vp, sz, vp]),
             "bugseg_confusion": (i, [vp, vp, vp, i, ctypes.POINTER(ConfusionParams), vp, vp]),
+            "bugseg_bev_warp_image": (i, [vp, vp, i, i, ctypes.POINTER(BevParams), i, vp, vp]),
+            "bugseg_hough_trig": (i, [ctypes.POINTER(HoughParams), vp]),
+            "bugseg_hough_workspace_bytes": (sz, [ctypes.POINTER(HoughParams), i]),
+            "bugseg_hough_lines": (i, [vp, vp, i, ctypes.POINTER(HoughParams), vp, vp, vp, vp, vp, sz, vp]),
+            "bugseg_debug_hough_stage": (i, [vp, vp, i, ctypes.POINTER(HoughParams), vp, i, vp, vp, vp, vp, vp, sz, vp]),
             "bugseg_dl_create": (i, [i, i, ctypes.POINTER(vp)]),
             "bugseg_dl_destroy": (i, [vp]),
             "bugseg_dl_load_weights": (i, [vp, vp, sz]),
@@ -419,6 +433,33 @@ class Context:
         sh, _, _ = self._stream_ws(gt, stream)
         self._raise_any(self.lib.bugseg_confusion(self.h, pred.data_ptr(), gt.data_ptr(), B, ctypes.byref(params),
                                                   acc.data_ptr(), sh))
+
+    def warp_image(self, frames, B, channels, params: BevParams, gray, out, stream=None):
+        """bugseg_bev_warp_image: (B, in_rows, in_cols[, 3]) u8 frames -> `out`, (B, warp_h, warp_w[, 3]) u8 (one
+        byte per pixel with gray). One launch, no workspace. A bad argument raises ValueError (as bev) and
+        launches nothing."""
+        sh, _, _ = self._stream_ws(frames, stream)
+        check(self.lib.bugseg_bev_warp_image(self.h, frames.data_ptr(), B, int(channels), ctypes.byref(params),
+                                             int(gray), out.data_ptr(), sh), self.h)
+
+    def hough(self, images, B, params: HoughParams, trig, lines, counts, peaks, stream=None, stage=None, acc=None,
+              workspace=None):
+        """bugseg_hough_lines: (B, rows, cols) u8 images and the device copy of the trig table -> lines
+        (B, max_lines, 2) float32, counts and peaks (B,) int32. The workspace comes from torch's caching allocator
+        on the stream the work runs on, as in road_filter (`workspace`: a uint8 device tensor to use instead).
+        stage = 0 or 1 enqueues that half alone (bugseg_debug_hough_stage: 0 writes the accumulators to `acc`,
+        1 reads them from it; the arguments a stage does not use may be None). Any refusal, a bad argument
+        included, raises BugsegError and launches nothing."""
+        ref = next(t for t in (images, acc, lines) if t is not None)
+        sh, w, _keep = self._stream_ws(ref, stream, workspace, self.lib.bugseg_hough_workspace_bytes, params, B)
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        if stage is None:
+            rc = self.lib.bugseg_hough_lines(self.h, ptr(images), B, ctypes.byref(params), ptr(trig), ptr(lines),
+                                             ptr(counts), ptr(peaks), *w, sh)
+        else:
+            rc = self.lib.bugseg_debug_hough_stage(self.h, ptr(images), B, ctypes.byref(params), ptr(trig), int(stage),
+                                                   ptr(acc), ptr(lines), ptr(counts), ptr(peaks), *w, sh)
+        self._raise_any(rc)
 
     def plan_info(self, B, H, W, out_kind, bgr_input=False):
         """-> (launches, per-layer algorithmic bytes, plan compulsory bytes, flops) of one forward."""

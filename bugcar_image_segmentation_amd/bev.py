@@ -13,7 +13,9 @@ on the engine too: the rasteriser, a per-ray nearest-obstacle kernel and a re-pr
 polar tables the library builds once per geometry (csrc/bev_kernels.hip).
 
 Additions: `create_occupancy_grid_device` (batched, device tensors in and out, optional ROS data
-layout) and `occupancy_params`.
+layout), `occupancy_params`, and `warp_image_device` / `warp_image`: the camera frame itself in the
+bird's-eye view (cv2.warpPerspective with the rasteriser's own arithmetic), which the reference's absent
+test_straight_line.py looked at.
 """
 from __future__ import annotations
 
@@ -160,6 +162,73 @@ class bev_transform_tools:
         assert tuple(shape) == (self.input_width, self.input_height), \
             "current segmap size: {},the segmap's original size must be the same as the required input shape, which is {}" \
             .format(tuple(shape), (self.input_width, self.input_height))
+
+    # -- the camera frame in the bird's-eye view -----------------------------------------------
+    def warp_params(self) -> N.BevParams:
+        """The fields bugseg_bev_warp_image reads: the matrix and the two image sizes."""
+        p = N.BevParams()
+        M = np.asarray(self._bev_matrix, dtype=np.float64).reshape(9)
+        for i in range(9):
+            p.M[i] = float(M[i])
+        p.in_rows, p.in_cols = int(self.input_width), int(self.input_height)
+        p.warp_w, p.warp_h = int(self.after_warp_width), int(self.after_warp_height)
+        return p
+
+    def _frame_batch(self, frames):
+        """frames as a contiguous batch -> (batch, channels): (B, r, c, 3) and (r, c, 3) have 3 channels, (B, r, c)
+        and (r, c) one; (r, c) must be (input_width, input_height), the convention of _check_shape."""
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
+            raise ValueError("frames must be a uint8 device tensor")
+        rc = (int(self.input_width), int(self.input_height))
+        s = tuple(frames.shape)
+        if frames.dim() == 4 and s[3] == 3:
+            f, ch = frames, 3
+        elif frames.dim() == 3 and s[1:] == rc:
+            f, ch = frames, 1
+        elif frames.dim() == 3 and s[2] == 3:
+            f, ch = frames.unsqueeze(0), 3
+        elif frames.dim() == 2:
+            f, ch = frames.unsqueeze(0), 1
+        else:
+            raise ValueError(f"frames must have shape (B, r, c, 3), (r, c, 3), (B, r, c) or (r, c) with (r, c) = {rc}, got {s}")
+        self._check_shape(f.shape[1:3])
+        if f.shape[0] < 1:
+            raise ValueError("frames holds no frame")
+        return f.contiguous(), ch
+
+    def warp_image_device(self, frames: torch.Tensor, gray: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """cv2.warpPerspective(frame, _bev_matrix, (after_warp_width, after_warp_height)) (INTER_LINEAR, constant 0
+        border) of a batch of camera frames on the device: uint8 (B, r, c, 3), (r, c, 3), (B, r, c) or (r, c) ->
+        (B, after_warp_height, after_warp_width[, 3]) uint8 on the current stream. gray=True (3-channel frames
+        only) stores cv2.cvtColor(warped, COLOR_BGR2GRAY) instead, one byte per pixel. `out` must not overlap
+        the input."""
+        f, ch = self._frame_batch(frames)
+        if gray and ch != 3:
+            raise ValueError("gray=True needs 3-channel (BGR) frames")
+        p = self.warp_params()
+        if p.warp_w < 1 or p.warp_h < 1:
+            raise ValueError("the warped image is empty")
+        B = f.shape[0]
+        shape = (B, p.warp_h, p.warp_w) if ch == 1 or gray else (B, p.warp_h, p.warp_w, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=f.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != f.device:
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on {f.device}")
+        with torch.cuda.device(f.device):
+            N.shared_context(f.device.index).warp_image(f, B, ch, p, gray, out, torch.cuda.current_stream(f.device))
+        return out
+
+    def warp_image(self, frame, gray: bool = False):
+        """One frame, (r, c, 3) or (r, c) uint8 (NumPy array or torch tensor), in the bird's-eye view -> an owned
+        NumPy uint8 (after_warp_height, after_warp_width[, 3]) image; (after_warp_height, after_warp_width) with gray."""
+        from .image_processing_utils import _host_call
+        t = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
+        if t.dtype != torch.uint8 or not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)):
+            raise ValueError("frame must be an (r, c, 3) or (r, c) uint8 image")
+        self._check_shape(t.shape[:2])
+        if gray and t.dim() != 3:
+            raise ValueError("gray=True needs a 3-channel (BGR) frame")
+        return _host_call(t, self.warp_image_device, gray)
 
     # -- the hot path --------------------------------------------------------------------------
     def create_occupancy_grid_device(self, segmaps: torch.Tensor, occupancy_grid_width_in_m,

@@ -1034,6 +1034,52 @@ __global__ void __launch_bounds__(256) laserscan_kernel(const BevArgs a) {
     }
 }
 
+// cv2.warpPerspective(frame, M, (warp_w, warp_h)), INTER_LINEAR, constant 0 border, of whole frames of C
+// interleaved channels (bugseg_bev_warp_image): one thread per warped pixel. The taps and weights do not depend
+// on the frame, so a thread evaluates warp_tap once and serves BEV_WARP_FRAMES frames with it. The blend is
+// remapBilinear's: Q15 weights (32 - ax)(32 - ay) * 32 ..., (sum + 2^14) >> 15, which is (sum / 32 + 512) >> 10.
+// GRAY (C = 3): one byte per pixel, cv2.cvtColor(., COLOR_BGR2GRAY) of the warped pixel in 8 bits.
+template <int C, bool GRAY>
+__global__ void __launch_bounds__(256) bev_warp_image_kernel(const BevArgs a, const uint8_t *__restrict__ img,
+                                                            uint8_t *__restrict__ out) {
+    const int npx = a.warp_w * a.warp_h;
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= npx) return;
+    const int y = i / a.warp_w, x = i - y * a.warp_w;
+    const WarpTap t = warp_tap(a, x, y);
+    const int w00 = (32 - t.ax) * (32 - t.ay), w01 = t.ax * (32 - t.ay), w10 = (32 - t.ax) * t.ay, w11 = t.ax * t.ay;
+    const bool v00 = t.y0 && t.x0, v01 = t.y0 && t.x1, v10 = t.y1 && t.x0, v11 = t.y1 && t.x1;
+    // the top-left tap's byte in a frame; a tap is read only where it lies inside the frame
+    const long o00 = ((long)t.sy * a.in_cols + t.sx) * C, o10 = o00 + (long)a.in_cols * C;
+    const size_t in_frame = (size_t)a.in_rows * a.in_cols * C, out_frame = (size_t)npx * (GRAY ? 1 : C);
+    const int b0 = (int)blockIdx.y * BEV_WARP_FRAMES, b1 = min(a.B, b0 + BEV_WARP_FRAMES);
+    for (int b = b0; b < b1; ++b) {
+        const uint8_t *src = img + (size_t)b * in_frame;
+        int v[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int s = (v00 ? src[o00 + c] * w00 : 0) + (v01 ? src[o00 + C + c] * w01 : 0) +
+                          (v10 ? src[o10 + c] * w10 : 0) + (v11 ? src[o10 + C + c] * w11 : 0);
+            v[c] = (s + 512) >> 10;
+        }
+        uint8_t *dst = out + (size_t)b * out_frame;
+        if (GRAY) {
+            dst[i] = (uint8_t)((1868 * v[0] + 9617 * v[1 % C] + 4899 * v[2 % C] + 8192) >> 14);
+        } else {
+#pragma unroll
+            for (int c = 0; c < C; ++c) dst[(size_t)i * C + c] = (uint8_t)v[c];
+        }
+    }
+}
+
+hipError_t launch_bev_warp_image(const BevArgs &a, const uint8_t *img, int channels, int gray, uint8_t *out, hipStream_t s) {
+    const dim3 grid((unsigned)(((long)a.warp_w * a.warp_h + 255) / 256), (unsigned)((a.B + BEV_WARP_FRAMES - 1) / BEV_WARP_FRAMES));
+    if (channels == 1) hipLaunchKernelGGL((bev_warp_image_kernel<1, false>), grid, dim3(256), 0, s, a, img, out);
+    else if (gray) hipLaunchKernelGGL((bev_warp_image_kernel<3, true>), grid, dim3(256), 0, s, a, img, out);
+    else hipLaunchKernelGGL((bev_warp_image_kernel<3, false>), grid, dim3(256), 0, s, a, img, out);
+    return hipGetLastError();
+}
+
 size_t bev_table_bytes(int occ_w, int occ_h) {
     return bev_items_offset(occ_w, occ_h) + (size_t)bev_bands(occ_h) * BEV_BAND * sizeof(int2);
 }

@@ -307,6 +307,10 @@ struct BevArgs {
 hipError_t launch_bev(const Knobs &k, const BevArgs &a, hipStream_t s);   // the form: Knobs::bev_*
 hipError_t launch_bev_table(const BevArgs &a, hipStream_t s);
 size_t bev_table_bytes(int occ_w, int occ_h);   // tap table + per-band class-map boxes
+// cv2.warpPerspective of whole frames with the rasteriser's warp_tap (bugseg_bev_warp_image): a thread serves one
+// warped pixel of BEV_WARP_FRAMES frames. Of `a` the fields warp_geometry() sets and B are read.
+constexpr int BEV_WARP_FRAMES = 8;
+hipError_t launch_bev_warp_image(const BevArgs &a, const uint8_t *img, int channels, int gray, uint8_t *out, hipStream_t s);
 
 // the band-staged forms cut the grid into bands of BEV_BAND rows (one class-map box each)
 constexpr int BEV_BAND = 4;

@@ -2106,13 +2106,9 @@ int internal_scratch(bugseg_ctx *ctx, void *stream, size_t need, bool cap, void 
     return BUGSEG_OK;
 }
 
-// the geometry fields of the rasteriser's arguments from the caller's parameters (checked)
-int bev_geometry(bugseg_ctx *ctx, const bugseg_bev_params *p, BevArgs &a) {
-    if (p->in_rows <= 0 || p->in_cols <= 0 || p->warp_w <= 0 || p->warp_h <= 0 || p->occ_w <= 0 ||
-        p->occ_h <= 0 || p->occ_w_px <= 0 || p->occ_h_px <= 0)
-        return fail(ctx, BUGSEG_EINVAL, "bad BEV geometry");
-    if (p->variant != 0 && p->variant != 1) return fail(ctx, BUGSEG_EINVAL, "variant must be 0 or 1");
-    if (p->laserscan != 0 && p->laserscan != 1) return fail(ctx, BUGSEG_EINVAL, "laserscan must be 0 or 1");
+// what warp_tap (bev_kernels.hip) reads: the sizes of the source and of the warped image, the inverse matrix and
+// the x-block width; every other field of `a` is zeroed. The sizes are positive (the callers check).
+void warp_geometry(const bugseg_bev_params *p, BevArgs &a) {
     std::memset(&a, 0, sizeof(a));
     a.in_rows = p->in_rows; a.in_cols = p->in_cols;
     {
@@ -2136,6 +2132,16 @@ int bev_geometry(bugseg_ctx *ctx, const bugseg_bev_params *p, BevArgs &a) {
     const int bh0 = std::min(16, p->warp_h);
     a.bw0 = std::min(1024 / bh0, p->warp_w);
     a.warp_w = p->warp_w; a.warp_h = p->warp_h;
+}
+
+// the geometry fields of the rasteriser's arguments from the caller's parameters (checked)
+int bev_geometry(bugseg_ctx *ctx, const bugseg_bev_params *p, BevArgs &a) {
+    if (p->in_rows <= 0 || p->in_cols <= 0 || p->warp_w <= 0 || p->warp_h <= 0 || p->occ_w <= 0 ||
+        p->occ_h <= 0 || p->occ_w_px <= 0 || p->occ_h_px <= 0)
+        return fail(ctx, BUGSEG_EINVAL, "bad BEV geometry");
+    if (p->variant != 0 && p->variant != 1) return fail(ctx, BUGSEG_EINVAL, "variant must be 0 or 1");
+    if (p->laserscan != 0 && p->laserscan != 1) return fail(ctx, BUGSEG_EINVAL, "laserscan must be 0 or 1");
+    warp_geometry(p, a);
     a.occ_w_px = p->occ_w_px; a.occ_h_px = p->occ_h_px; a.occ_w = p->occ_w; a.occ_h = p->occ_h;
     a.left_x = p->left_x; a.top_y = p->top_y;
     a.ifx = 1.0 / ((double)p->occ_w / p->occ_w_px);
@@ -2299,6 +2305,26 @@ size_t bugseg_bev_workspace_bytes(const bugseg_bev_params *p, int B) {
 int bugseg_bev_occgrid_ws(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_params *p, int8_t *out,
                           void *workspace, size_t workspace_bytes, void *stream) {
     return bev_occgrid(ctx, seg, B, p, out, false, workspace, workspace_bytes, stream);
+}
+
+int bugseg_bev_warp_image(bugseg_ctx *ctx, const uint8_t *img, int B, int channels, const bugseg_bev_params *p, int gray,
+                          uint8_t *out, void *stream) {
+    if (!ctx || !img || !p || !out) return fail(ctx, BUGSEG_EINVAL, "warp image: NULL argument");
+    if (channels != 1 && channels != 3) return fail(ctx, BUGSEG_EINVAL, "warp image: channels must be 1 or 3");
+    if ((gray != 0 && gray != 1) || (gray && channels != 3)) return fail(ctx, BUGSEG_EINVAL, "warp image: gray is 0 or 1, and 1 only with 3 channels");
+    if (B < 1 || B > 65535 * BEV_WARP_FRAMES) return fail(ctx, BUGSEG_EINVAL, "warp image: B must be at least 1 (and fit the launch grid)");
+    if (p->in_rows <= 0 || p->in_cols <= 0 || p->warp_w <= 0 || p->warp_h <= 0) return fail(ctx, BUGSEG_EINVAL, "warp image: an empty source or result");
+    const size_t in_frame = (size_t)p->in_rows * p->in_cols * channels, out_frame = (size_t)p->warp_w * p->warp_h * (gray ? 1 : channels);
+    if (in_frame > (size_t)INT_MAX || (size_t)p->warp_w * p->warp_h * 3 > (size_t)INT_MAX)
+        return fail(ctx, BUGSEG_EINVAL, "warp image: a frame or a result of 2^31 bytes or more");
+    if (ranges_overlap(out, out_frame * B, img, in_frame * B)) return fail(ctx, BUGSEG_EINVAL, "warp image: out_dev overlaps the input");
+    BevArgs a;
+    warp_geometry(p, a);
+    a.B = B;
+    DeviceGuard g(ctx->device);
+    hipError_t e = launch_bev_warp_image(a, img, channels, gray, out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("warp image launch: ") + hipGetErrorString(e));
+    return BUGSEG_OK;
 }
 
 // ---- test hooks (host only: no device, no HIP call) — tests/asan drives them under ASan + UBSan

@@ -21,8 +21,14 @@ False, the only form the reference uses). Here it is five launches over a batch 
 bit-exact against the restatements in tests/canny_ref.py. create_skeleton is the outline of the camera's field
 of view in the occupancy grid: the edges of the grid of an all-free map. find_intersection_line is host
 arithmetic. There is no CPU fallback for the device functions.
+
+What hough_lines computes is stated in DESIGN.md §6.21: cv2.HoughLines' standard transform, the step between
+canny and find_intersection_line. Here it is three launches over a batch (csrc/hough_kernels.hip), bit-exact
+against the restatements in tests/hough_ref.py; the sines and cosines come from one host function of the library.
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -216,6 +222,119 @@ def canny(img, threshold1, threshold2, apertureSize: int = 3, L2gradient: bool =
         raise ValueError("img must be an (h, w) uint8 image")            # cv2.Canny's 8-bit single-channel input
     canny_params(t.shape[0], t.shape[1], threshold1, threshold2, apertureSize, L2gradient)   # before any device work
     return _host_call(t, canny_device, threshold1, threshold2)
+
+
+HOUGH_MAX_LINES = 4096          # the most lines one call stores per frame (the select's LDS sort)
+HOUGH_MAX_SIDE, HOUGH_MAX_NUMRHO, HOUGH_MAX_NUMANGLE = 65535, 13651, 65536      # include/bugseg.h
+
+
+def hough_params(h: int, w: int, rho, theta, threshold, max_lines, min_theta=0.0, max_theta=np.pi) -> N.HoughParams:
+    """bugseg_hough_params for (h, w) images, with every check before any device work.
+    rho and theta are rounded to float32 first; numangle = floor((max_theta - min_theta) / theta) + 1 in double,
+    less one if numangle > 1 and |pi - (numangle - 1) theta| < theta / 2; numrho = cvRound((2 (w + h) + 1) / rho)
+    in double. ValueError for: an empty image or a side above 65535; rho or theta that is not positive and finite
+    as float32; min_theta or max_theta not finite, max_theta < min_theta; a threshold that is no finite number
+    (it is floored and clamped to int32); max_lines outside 1..4096; numrho below 1 or above 13651, numangle above
+    65536, (numangle + 2) (numrho + 2) of 2^31 or more."""
+    h, w = int(h), int(w)
+    if not (1 <= h <= HOUGH_MAX_SIDE and 1 <= w <= HOUGH_MAX_SIDE):
+        raise ValueError(f"hough needs an image of 1 x 1 to {HOUGH_MAX_SIDE} x {HOUGH_MAX_SIDE}, got {h} x {w}")
+    with np.errstate(over="ignore"):
+        r32, t32, m32 = np.float32(float(rho)), np.float32(float(theta)), np.float32(float(min_theta))
+    if not (np.isfinite(r32) and r32 > 0 and np.isfinite(t32) and t32 > 0):
+        raise ValueError(f"rho and theta must be positive and finite as float32, got {rho!r}, {theta!r}")
+    lo, hi = float(min_theta), float(max_theta)
+    if not (np.isfinite(lo) and np.isfinite(hi) and np.isfinite(m32)) or hi < lo:
+        raise ValueError(f"min_theta and max_theta must be finite with max_theta >= min_theta, got {min_theta!r}, {max_theta!r}")
+    thr = float(threshold)
+    if not np.isfinite(thr):
+        raise ValueError(f"threshold must be finite, got {threshold!r}")
+    if isinstance(max_lines, bool) or int(max_lines) != max_lines or not 1 <= int(max_lines) <= HOUGH_MAX_LINES:
+        raise ValueError(f"max_lines must be an integer in [1, {HOUGH_MAX_LINES}], got {max_lines!r}")
+    t, r = float(t32), float(r32)
+    angles = np.floor((hi - lo) / t) + 1.0
+    rhos = np.rint((2.0 * (w + h) + 1.0) / r)
+    if angles > HOUGH_MAX_NUMANGLE + 1:
+        raise ValueError(f"theta {theta!r} gives more than {HOUGH_MAX_NUMANGLE} angles")
+    numangle = int(angles)
+    if numangle > 1 and abs(np.pi - (numangle - 1) * t) < t / 2:
+        numangle -= 1
+    if numangle > HOUGH_MAX_NUMANGLE:
+        raise ValueError(f"theta {theta!r} gives more than {HOUGH_MAX_NUMANGLE} angles")
+    if not 1 <= rhos <= HOUGH_MAX_NUMRHO:
+        raise ValueError(f"rho {rho!r} gives {rhos:.0f} accumulator columns for {h} x {w}; 1 to {HOUGH_MAX_NUMRHO} are supported")
+    numrho = int(rhos)
+    if (numangle + 2) * (numrho + 2) >= 2 ** 31:
+        raise ValueError("the accumulator has 2^31 cells or more")
+    p = N.HoughParams()
+    p.rows, p.cols, p.numangle, p.numrho = h, w, numangle, numrho
+    p.threshold = int(min(max(np.floor(thr), -2.0 ** 31), 2.0 ** 31 - 1))
+    p.max_lines = int(max_lines)
+    p.rho, p.theta, p.min_theta = float(r32), float(t32), float(m32)
+    return p
+
+
+_hough_trig_tables: dict = {}       # (device, numangle, rho, theta, min_theta) -> the device copy of the trig table
+
+
+def hough_trig_host(p: N.HoughParams) -> np.ndarray:
+    """bugseg_hough_trig: the (2, numangle) float32 table of p, cosines / rho then sines / rho. Host only."""
+    tab = np.empty((2, p.numangle), np.float32)
+    N.check(N.load_library().bugseg_hough_trig(ctypes.byref(p), tab.ctypes.data))
+    return tab
+
+
+def hough_trig_device(device: torch.device, p: N.HoughParams) -> torch.Tensor:
+    """The device copy of p's trig table, made on first use per (device, parameters) and kept for the process's
+    life (a captured graph may hold its address; a table is 8 bytes per angle). Making it copies from the host,
+    so the first call with new parameters must come before a capture: inside one it raises RuntimeError."""
+    key = (device.index, p.numangle, float(p.rho), float(p.theta), float(p.min_theta))
+    t = _hough_trig_tables.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("hough: call once with these parameters before capturing (the trig table is uploaded on first use)")
+        t = torch.from_numpy(hough_trig_host(p).reshape(-1)).to(device)
+        t = _hough_trig_tables.setdefault(key, t)
+    return t
+
+
+def hough_lines_device(images: torch.Tensor, rho, theta, threshold, max_lines: int = 256, min_theta=0.0, max_theta=np.pi):
+    """Batched cv2.HoughLines(image, rho, theta, threshold, min_theta=, max_theta=) on device tensors: (B, h, w) or
+    (h, w) uint8 images, any non-zero byte is an edge -> (lines, counts, peaks) on the current stream: lines
+    (B, max_lines, 2) float32 (rho, theta), strongest first, zero from row counts[b] on; counts (B,) int32 =
+    min(peaks, max_lines); peaks (B,) int32, the peaks found. Nothing is read back: the call does not synchronise."""
+    im, (B, h, w) = _device_batch(images, "images")
+    p = hough_params(h, w, rho, theta, threshold, max_lines, min_theta, max_theta)
+    if B < 1:
+        raise ValueError("images holds no frame")
+    trig = hough_trig_device(im.device, p)
+    with torch.cuda.device(im.device):
+        lines = torch.empty((B, p.max_lines, 2), dtype=torch.float32, device=im.device)
+        counts = torch.empty((B,), dtype=torch.int32, device=im.device)
+        peaks = torch.empty((B,), dtype=torch.int32, device=im.device)
+        N.shared_context(im.device.index).hough(im, B, p, trig, lines, counts, peaks, torch.cuda.current_stream(im.device))
+    return lines, counts, peaks
+
+
+def hough_lines(img, rho, theta, threshold, min_theta=0.0, max_theta=np.pi):
+    """cv2.HoughLines(img, rho, theta, threshold, min_theta=0, max_theta=pi), the standard transform: an (h, w)
+    uint8 image (NumPy array or torch tensor) -> an owned NumPy float32 (N, 1, 2) array of (rho, theta), strongest
+    first, or None when no line passes. cv2 returns every peak; one call here stores at most 4096, so a frame with
+    more raises ValueError naming the count: nothing is cut off silently."""
+    t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+    if t.dim() != 2 or t.dtype != torch.uint8:
+        raise ValueError("img must be an (h, w) uint8 image")
+    hough_params(t.shape[0], t.shape[1], rho, theta, threshold, HOUGH_MAX_LINES, min_theta, max_theta)    # before any device work
+    N.require_gpu()
+    if not t.is_cuda:
+        t = t.to(torch.device("cuda", torch.cuda.current_device()))
+    lines, counts, peaks = hough_lines_device(t, rho, theta, threshold, HOUGH_MAX_LINES, min_theta, max_theta)
+    found, n = int(peaks[0]), int(counts[0])
+    if found > HOUGH_MAX_LINES:
+        raise ValueError(f"the image has {found} lines above the threshold; at most {HOUGH_MAX_LINES} can be returned: raise the threshold")
+    if n == 0:
+        return None
+    return lines[0, :n].cpu().numpy().reshape(n, 1, 2).copy()
 
 
 def find_intersection_line(line1, line2):

@@ -208,6 +208,19 @@ size_t bugseg_bev_workspace_bytes(const bugseg_bev_params *p, int B);
 int bugseg_bev_occgrid_ws(bugseg_ctx *ctx, const uint8_t *seg_dev, int B, const bugseg_bev_params *p,
                           int8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* cv2.warpPerspective(frame, M, (warp_w, warp_h)) with INTER_LINEAR and a constant 0 border, over a batch of
+ * frames: img_dev (B, in_rows, in_cols[, 3]) u8 (channels 1 or 3, interleaved) -> out_dev (B, warp_h, warp_w[, 3])
+ * u8. The arithmetic is the rasteriser's own warp (double inverse map with OpenCV's per-block split, cvRound to
+ * 1/32 pixel, Q15 weights, (sum + 2^14) >> 15), per channel. gray = 1, for 3 channels only, stores one byte per
+ * pixel instead: (1868 b + 9617 g + 4899 r + 8192) >> 14 of the warped pixel (cv2.cvtColor(., COLOR_BGR2GRAY) of
+ * an 8-bit image). Of p only M, in_rows, in_cols, warp_w and warp_h are read. A singular M warps like OpenCV: the
+ * inverse is taken as all zeros and every pixel samples the source's corner. One launch, no workspace, no tables;
+ * the call never synchronises and may be captured on its first call. BUGSEG_EINVAL, and nothing is launched: a
+ * NULL argument, channels other than 1 or 3, gray other than 0 or 1 or with 1 channel, B < 1, an empty source
+ * or result, a frame or a result of 2^31 bytes or more, overlapping buffers. */
+int bugseg_bev_warp_image(bugseg_ctx *ctx, const uint8_t *img_dev, int B, int channels,
+                          const bugseg_bev_params *p, int gray, uint8_t *out_dev, void *stream);
+
 /* contour_noise_removal (image_processing_utils.py:4-44), the clean-up of a binary road map between
  * ENET.predict_binary and create_occupancy_grid_binary: close small gaps with a k x k square, keep the
  * road regions that reach the bottom band of the image, fill their small holes, drop everything else.
@@ -313,6 +326,55 @@ int bugseg_canny(bugseg_ctx *ctx, const uint8_t *img_dev, int B, const bugseg_ca
  *   1  hysteresis only: in_dev is read as such a map (any byte other than 2 and 0 is none), out_dev the edges */
 int bugseg_debug_canny_stage(bugseg_ctx *ctx, const uint8_t *in_dev, int B, const bugseg_canny_params *p, int stage,
                              uint8_t *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* The standard Hough transform, cv2.HoughLines(image, rho, theta, threshold, min_theta, max_theta), batched.
+ * The exact semantics are stated in DESIGN.md 6.21. image_processing_utils.hough_params computes the fields:
+ *   numangle   floor((max_theta - min_theta) / theta) + 1, less one if the last angle would be pi again
+ *   numrho     cvRound((2 (cols + rows) + 1) / rho), in double with rho as stored here
+ *   threshold  a cell needs more votes than this
+ *   max_lines  the strongest lines stored per frame, 1..4096
+ *   rho, theta, min_theta  as float32, the values every step uses
+ * Limits: rows and cols 1..65535 (a pixel is packed as x | y << 16), B * rows * cols below 2^31 - 256; numrho
+ * exactly the value above (the votes are indexed with it) and at most 13651 (three accumulator rows of
+ * numrho + 2 int32 must fit the 160 KiB of LDS; 1080 x 1920 at rho 1 has 6001); numangle 1..65536 with
+ * (numangle + 2) * (numrho + 2) below 2^31; B 1..65535. */
+typedef struct {
+    int rows, cols, numangle, numrho, threshold, max_lines;
+    float rho, theta, min_theta;
+} bugseg_hough_params;
+
+/* Host only, no GPU: the trig table of p, 2 * numangle float32 into dst_host: (float)(cos((double)ang) * irho)
+ * for every angle, then the sines likewise, with irho = 1 / rho in float32 and ang starting at min_theta and
+ * growing by theta in float32. The one place these values are computed; the device reads them as they are. */
+int bugseg_hough_trig(const bugseg_hough_params *p, float *dst_host);
+
+/* Bytes of the device workspace bugseg_hough_lines needs for B frames: per frame 4 bytes per pixel (the list of
+ * non-zero pixels), 8 bytes per possible peak (ceil(numangle * numrho / 2) keys) and two counters, plus alignment;
+ * 0 for parameters the call would refuse. */
+size_t bugseg_hough_workspace_bytes(const bugseg_hough_params *p, int B);
+
+/* img_dev (B, rows, cols) u8, any non-zero byte is set; trig_dev the table of bugseg_hough_trig in device memory
+ * -> lines_dev (B, max_lines, 2) float32 (rho, theta), strongest first (on equal votes the smaller accumulator
+ * index first), zero from row counts[b] on; counts_dev (B,) int32 = min(peaks, max_lines); peaks_dev (B,) int32,
+ * the peaks found. The workspace is caller-owned and used only by the work this call enqueues on `stream`; its
+ * prior contents do not matter. One memset of the counters and three launches (list the non-zero pixels; vote and
+ * test for peaks in LDS, the accumulator never reaches memory; select and sort). The call never synchronises,
+ * allocates nothing and may be captured into a graph on its first call. BUGSEG_EINVAL, and nothing is launched: a
+ * NULL argument, parameters outside the limits above, rho or theta not positive and finite, min_theta not finite,
+ * max_lines outside 1..4096, a NULL or short workspace, a written buffer that overlaps another buffer. */
+int bugseg_hough_lines(bugseg_ctx *ctx, const uint8_t *img_dev, int B, const bugseg_hough_params *p,
+                       const float *trig_dev, float *lines_dev, int32_t *counts_dev, int32_t *peaks_dev,
+                       void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Tests and bench_hough.py: one half of bugseg_hough_lines, run by the device functions the product runs; the
+ * refusals are bugseg_hough_lines'.
+ *   0  list and vote: acc_dev receives the accumulators, (B, numangle + 2, numrho + 2) int32 with a zero border
+ *      (row n + 1, column r + 1 is cell (n, r)); lines_dev, counts_dev and peaks_dev are not used
+ *   1  peaks, select and sort on the accumulators given in acc_dev (that shape, non-negative values; the border
+ *      is read as given); img_dev and trig_dev are not used */
+int bugseg_debug_hough_stage(bugseg_ctx *ctx, const uint8_t *img_dev, int B, const bugseg_hough_params *p,
+                             const float *trig_dev, int stage, int32_t *acc_dev, float *lines_dev, int32_t *counts_dev,
+                             int32_t *peaks_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* Evaluation of class maps: the confusion matrix of predictions against labels, both u8 maps
  * in device memory. A label pixel (y, x) of a gt_rows x gt_cols label map is compared with the prediction at
