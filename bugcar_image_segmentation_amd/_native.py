@@ -33,6 +33,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_canny_workspace_bytes", "bugseg_canny", "bugseg_debug_canny_stage", "bugseg_confusion",
             "bugseg_bev_warp_image", "bugseg_hough_trig", "bugseg_hough_workspace_bytes", "bugseg_hough_lines",
             "bugseg_debug_hough_stage",
+            "bugseg_quad_workspace_bytes", "bugseg_find_quad", "bugseg_quad_moments", "bugseg_debug_quad_stage",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
@@ -71,6 +72,12 @@ class HoughParams(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("numangle", ctypes.c_int), ("numrho", ctypes.c_int),
                 ("threshold", ctypes.c_int), ("max_lines", ctypes.c_int), ("rho", ctypes.c_float),
                 ("theta", ctypes.c_float), ("min_theta", ctypes.c_float)]
+
+
+class QuadParams(ctypes.Structure):
+    """bugseg_quad_params: calibration.quad_params builds and checks them."""
+    _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("channels", ctypes.c_int), ("bright", ctypes.c_int),
+                ("threshold", ctypes.c_int), ("min_area", ctypes.c_int), ("band", ctypes.c_int * 2)]
 
 
 class ConfusionParams(ctypes.Structure):
@@ -146,6 +153,10 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_hough_workspace_bytes": (sz, [ctypes.POINTER(HoughParams), i]),
             "bugseg_hough_lines": (i, [vp, vp, i, ctypes.POINTER(HoughParams), vp, vp, vp, vp, vp, sz, vp]),
             "bugseg_debug_hough_stage": (i, [vp, vp, i, ctypes.POINTER(HoughParams), vp, i, vp, vp, vp, vp, vp, sz, vp]),
+            "bugseg_quad_workspace_bytes": (sz, [ctypes.POINTER(QuadParams), i]),
+            "bugseg_find_quad": (i, [vp, vp, i, ctypes.POINTER(QuadParams), vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+            "bugseg_quad_moments": (i, [vp, vp, i, ctypes.POINTER(QuadParams), i, vp, vp, vp, sz, vp]),
+            "bugseg_debug_quad_stage": (i, [vp, vp, i, ctypes.POINTER(QuadParams), i, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
             "bugseg_dl_create": (i, [i, i, ctypes.POINTER(vp)]),
             "bugseg_dl_destroy": (i, [vp]),
             "bugseg_dl_load_weights": (i, [vp, vp, sz]),
@@ -460,6 +471,31 @@ class Context:
             rc = self.lib.bugseg_debug_hough_stage(self.h, ptr(images), B, ctypes.byref(params), ptr(trig), int(stage),
                                                    ptr(acc), ptr(lines), ptr(counts), ptr(peaks), *w, sh)
         self._raise_any(rc)
+
+    def find_quad(self, frames, B, params: QuadParams, status, threshold, area, root, corners, moments, stream=None,
+                  stage=None, workspace=None):
+        """bugseg_find_quad: (B, rows, cols[, 3]) u8 frames -> status, threshold, area, root (B,) int32, corners
+        (B, 4, 2) int32, moments (B, 4, 6) int64. The workspace comes from torch's caching allocator on the stream
+        the work runs on, as in road_filter (`workspace`: a uint8 device tensor to use instead). stage = 0..11
+        enqueues that launch alone (bugseg_debug_quad_stage: the benchmark's per-launch times). Any refusal, a bad
+        argument included, raises BugsegError and launches nothing."""
+        ref = next(t for t in (frames, moments, corners, status) if t is not None)
+        sh, w, _keep = self._stream_ws(ref, stream, workspace, self.lib.bugseg_quad_workspace_bytes, params, B)
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        outs = [ptr(t) for t in (status, threshold, area, root, corners, moments)]
+        if stage is None:
+            rc = self.lib.bugseg_find_quad(self.h, ptr(frames), B, ctypes.byref(params), *outs, *w, sh)
+        else:
+            rc = self.lib.bugseg_debug_quad_stage(self.h, ptr(frames), B, ctypes.byref(params), int(stage), *outs, *w, sh)
+        self._raise_any(rc)
+
+    def quad_moments(self, frames, B, params: QuadParams, band, corners2, moments, stream=None, workspace=None):
+        """bugseg_quad_moments: the side moments of the frames' tile regions for the doubled corners `corners2`
+        (B, 4, 2) int32 -> moments (B, 4, 6) int64. Workspace and refusals as find_quad."""
+        sh, w, _keep = self._stream_ws(frames, stream, workspace, self.lib.bugseg_quad_workspace_bytes, params, B)
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        self._raise_any(self.lib.bugseg_quad_moments(self.h, ptr(frames), B, ctypes.byref(params), int(band), ptr(corners2),
+                                                     ptr(moments), *w, sh))
 
     def plan_info(self, B, H, W, out_kind, bgr_input=False):
         """-> (launches, per-layer algorithmic bytes, plan compulsory bytes, flops) of one forward."""

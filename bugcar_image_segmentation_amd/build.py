@@ -18,7 +18,7 @@ CSRC = PKG / "csrc"
 OBJ = PKG / "_build"
 LIB = PKG / "libbugseg.so"
 SOURCES = ["conv_kernels.hip", "cls_kernels.hip", "init_kernels.hip", "bneck_kernels.hip", "bneck2_kernels.hip", "up_kernels.hip", "prep_kernels.hip",
-           "bev_kernels.hip", "deeplab_kernels.hip", "road_kernels.hip", "clahe_kernels.hip", "canny_kernels.hip", "eval_kernels.hip", "hough_kernels.hip", "bugseg_runtime.cpp", "deeplab_runtime.cpp"]
+           "bev_kernels.hip", "deeplab_kernels.hip", "road_kernels.hip", "clahe_kernels.hip", "canny_kernels.hip", "eval_kernels.hip", "hough_kernels.hip", "quad_kernels.hip", "bugseg_runtime.cpp", "deeplab_runtime.cpp"]
 HEADERS = [CSRC / "bugseg_internal.h", CSRC / "deeplab_internal.h", CSRC / "knobs.h", CSRC / "mfma_common.h", CSRC / "cls_common.h", CSRC / "ccl_common.h", ROOT / "include" / "bugseg.h"]
 ARCH = os.environ.get("BUGSEG_OFFLOAD_ARCH", "gfx950")
 # per-source code-generation options. The class layer: MFMA results in ordinary VGPRs instead of AGPRs
@@ -27,8 +27,9 @@ ARCH = os.environ.get("BUGSEG_OFFLOAD_ARCH", "gfx950")
 # clahe: no a * b + c contracted into a fused multiply-add, on the host (the tables) or the device (the
 # float32 blend, whose semantics round every operation: DESIGN.md §6.18)
 # hough: the same, for the float32 products and sums of the votes and of the lines
+# quad: the same, for the float64 quotients and products of Otsu's threshold
 SOURCE_FLAGS = {"cls_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "clahe_kernels.hip": ["-ffp-contract=off"],
-                "hough_kernels.hip": ["-ffp-contract=off"]}
+                "hough_kernels.hip": ["-ffp-contract=off"], "quad_kernels.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -376,6 +376,56 @@ int bugseg_debug_hough_stage(bugseg_ctx *ctx, const uint8_t *img_dev, int B, con
                              const float *trig_dev, int stage, int32_t *acc_dev, float *lines_dev, int32_t *counts_dev,
                              int32_t *peaks_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* The calibration tile in a camera frame, batched: the largest bright (or dark) region that does
+ * not touch the frame's border, its four corners, and per side the moments of the region's boundary cracks.
+ * calibration.quad_params computes the fields:
+ *   channels   3: frames are (rows, cols, 3) BGR bytes, turned into 8-bit grey; 1: (rows, cols) grey bytes
+ *   bright     non-zero: foreground is grey > t; zero: grey <= t
+ *   threshold  0..254: t; any other value: Otsu's threshold of the frame, computed on the device
+ *   min_area   a region needs at least this many pixels
+ *   band       the half-width in pixels of the strip along a side whose crack points the side takes:
+ *              band[0] in bugseg_find_quad; band[1] is what calibration.find_tile passes to its second pass
+ * Limits: rows and cols 3..4096, channels 1 or 3, B 1..65535, min_area at least 1, band 0..64. */
+typedef struct { int rows, cols, channels, bright, threshold, min_area, band[2]; } bugseg_quad_params;
+
+/* status of a frame */
+#define BUGSEG_QUAD_OK 0
+#define BUGSEG_QUAD_NO_TILE 1       /* one grey level, or no region off the border with min_area pixels */
+#define BUGSEG_QUAD_DEGENERATE 2    /* the region has no four distinct corners that span a quadrilateral */
+
+/* Bytes of the device workspace the calls below need for B frames: per frame 9 bytes per pixel (grey value,
+ * label, counter), the histogram and the state, plus alignment; 0 for parameters the calls would refuse. */
+size_t bugseg_quad_workspace_bytes(const bugseg_quad_params *p, int B);
+
+/* frames_dev (B, rows, cols[, 3]) u8 -> per frame status, threshold (-1 for a frame of one grey level), area and
+ * root (the region's pixel count and its raster-first pixel's index; 0 and -1 without a region), corners_dev
+ * (B, 4, 2) int32 (x, y) in cyclic order and moments_dev (B, 4, 6) int64 (n, sum X, sum Y, sum XX, sum XY, sum YY
+ * of side i, from corner i to corner i + 1, in doubled coordinates); corners and moments are zero unless the
+ * status is BUGSEG_QUAD_OK. The workspace is caller-owned and used only by the work this call enqueues on
+ * `stream`; its prior contents do not matter. Two memsets and twelve launches; the call never synchronises,
+ * allocates nothing and may be captured into a graph on its first call. BUGSEG_EINVAL, and nothing is launched:
+ * a NULL argument, parameters outside the limits above, a NULL or short workspace, moments_dev not 8-byte
+ * aligned, a written buffer that overlaps another buffer. */
+int bugseg_find_quad(bugseg_ctx *ctx, const uint8_t *frames_dev, int B, const bugseg_quad_params *p, int32_t *status_dev,
+                     int32_t *threshold_dev, int32_t *area_dev, int32_t *root_dev, int32_t *corners_dev,
+                     int64_t *moments_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* The side moments alone, for corners the caller gives: corners2_dev (B, 4, 2) int32 in doubled coordinates
+ * (2 x, 2 y), cyclic. The region is found again from the frames (launches 0..5 of bugseg_find_quad), then its
+ * crack points are summed with `band`. A frame without a region, and a side of zero length or with a coordinate
+ * outside -16384..16384, gets zero sums. The refusals are those of bugseg_find_quad, and band outside 0..64. */
+int bugseg_quad_moments(bugseg_ctx *ctx, const uint8_t *frames_dev, int B, const bugseg_quad_params *p, int band,
+                        const int32_t *corners2_dev, int64_t *moments_dev, void *workspace_dev, size_t workspace_bytes,
+                        void *stream);
+
+/* Tests and bench_calibration.py: launch `stage` (0..11, the list in csrc/quad_kernels.hip) of bugseg_find_quad
+ * alone, with the memset that belongs to it, on a workspace an earlier whole call has filled; the refusals are
+ * those of bugseg_find_quad. */
+int bugseg_debug_quad_stage(bugseg_ctx *ctx, const uint8_t *frames_dev, int B, const bugseg_quad_params *p, int stage,
+                            int32_t *status_dev, int32_t *threshold_dev, int32_t *area_dev, int32_t *root_dev,
+                            int32_t *corners_dev, int64_t *moments_dev, void *workspace_dev, size_t workspace_bytes,
+                            void *stream);
+
 /* Evaluation of class maps: the confusion matrix of predictions against labels, both u8 maps
  * in device memory. A label pixel (y, x) of a gt_rows x gt_cols label map is compared with the prediction at
  * sy = min(y * pred_rows / gt_rows, pred_rows - 1), sx = min(x * pred_cols / gt_cols, pred_cols - 1), exact
