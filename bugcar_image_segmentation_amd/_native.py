@@ -26,6 +26,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_enet_forward_bgr", "bugseg_enet_forward_bgr_ops", "bugseg_enet_forward_bgr_rows",
             "bugseg_bev_source_rows", "bugseg_debug_row_windows", "bugseg_debug_poison_arena",
             "bugseg_debug_stage3_windows", "bugseg_debug_plan_windows", "bugseg_debug_read_block_output",
+            "bugseg_debug_pair_walk", "bugseg_debug_pair_plan",
             "bugseg_bev_occgrid", "bugseg_bev_workspace_bytes", "bugseg_bev_occgrid_ws", "bugseg_plan_info", "bugseg_plan_op", "bugseg_plan_launch_op",
             "bugseg_last_error",
             "bugseg_road_filter_workspace_bytes", "bugseg_road_filter", "bugseg_debug_road_filter_ops",
@@ -128,6 +129,8 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_debug_stage3_windows": (i, [i, i, i, i, vp, vp]),
             "bugseg_debug_plan_windows": (i, [vp, i, i, vp]),
             "bugseg_debug_read_block_output": (i, [vp, i, vp, sz, vp]),
+            "bugseg_debug_pair_walk": (i, [i, vp, i, i, vp]),
+            "bugseg_debug_pair_plan": (i, [vp, vp, i]),
             "bugseg_bev_occgrid": (i, [vp, vp, i, ctypes.POINTER(BevParams), vp, vp]),
             "bugseg_bev_workspace_bytes": (sz, [ctypes.POINTER(BevParams), i]),
             "bugseg_bev_occgrid_ws": (i, [vp, vp, i, ctypes.POINTER(BevParams), vp, vp, sz, vp]),
@@ -265,6 +268,21 @@ def stage3_windows(h: int, y0: int, y1: int, blocks) -> list[tuple[int, int]]:
     return [(win[2 * k], win[2 * k + 1]) for k in range(m)]
 
 
+def pair_walk(cands, first_op: int = 0, last_op: int = -1):
+    """Test hook (bugseg_debug_pair_walk, host only): the pair overlay's walk over a plan described per op by
+    (candidate, grid rows, grid columns, buffer read, buffer written), for a forward over ops [first_op, last_op).
+    -> (number of pairs, [(action, flip) per op]); the actions are listed in include/bugseg.h."""
+    lib = load_library()
+    n = len(cands)
+    flat = [int(v) for c in cands for v in c]
+    cand = (ctypes.c_int32 * max(1, len(flat)))(*flat)
+    out = (ctypes.c_int32 * max(1, 2 * n))()
+    m = lib.bugseg_debug_pair_walk(n, cand, first_op, n if last_op < 0 else last_op, out)
+    if m < 0:
+        check(m)
+    return m, [(out[2 * k], out[2 * k + 1]) for k in range(n)]
+
+
 def require_gpu() -> None:
     if not torch.cuda.is_available():
         raise RuntimeError("bugseg needs a HIP GPU (MI355X / gfx950); none is visible — there is no CPU fallback")
@@ -361,6 +379,15 @@ class Context:
         if m < 0:
             check(m, self.h)
         return [tuple(win[5 * k:5 * k + 5]) for k in range(m)]
+
+    def pair_plan(self) -> list[tuple[int, ...]]:
+        """Test hook (bugseg_debug_pair_plan): the current plan's paired launches, one row each: (first op, tile rows,
+        tile columns, tiles_y, tiles_x, threads, LDS bytes, flip of the first op)."""
+        rows = (ctypes.c_int32 * (8 * 16))()
+        m = self.lib.bugseg_debug_pair_plan(self.h, rows, 16)
+        if m < 0:
+            check(m, self.h)
+        return [tuple(rows[8 * k:8 * k + 8]) for k in range(min(m, 16))]
 
     def read_block_output(self, op: int, out, stream=None) -> None:
         """Test hook (bugseg_debug_read_block_output): the output of fused bottleneck launch `op` into `out`."""

@@ -1762,6 +1762,24 @@ __global__ void __launch_bounds__((BShape<C, V>::NW * 64), BNECK_F32_OCC128) bne
     if (!bneck_body<T, C, ASYM, V, false, 0, false, -1, true>(a, rl)) bneck_body<T, C, ASYM, V, false, 0, true, -1, true>(a, rl);
 }
 
+// The fp32 C = 64 regular forms as the fallback of a paired launch (bneck_pair_kernels.hip; BneckGuardArgs): the
+// pair ran both blocks with every range exponent taken as 0. With the measured max |x| and max |y| in their
+// words, every workgroup evaluates both blocks' exponents and returns when all are 0; otherwise the launch is
+// bneck_kernel's. Their own kernels, outside the form table: the unguarded ones keep their symbols and code.
+template <int V>
+__global__ void __launch_bounds__((BShape<64, V>::NW * 64), (V == 2 ? BNECK_F32_OCC64_V2 : BNECK_F32_OCC64)) bneck_guard64_kernel(const BneckArgs a, const BneckGuardArgs g) {
+    span_enter(a.span);                               // (a launch that only checks is stamped too: armed spans cover every op)
+    const float mx = rng_reduce(rng_lane(g.ra)), my = rng_reduce(rng_lane(g.rb));
+    if (!bneck_range<false>(g.ra, mx).any && !bneck_range<false>(g.rb, my).any) {
+        span_exit(a.span);
+        return;
+    }
+    static_assert(BShape<64, V>::NW * 64 == RNG_SLOTS, "one range word per thread");
+    if (g.clear && blockIdx.x == 0) g.clear[threadIdx.x] = 0.f;
+    const float rl = rng_lane(a.rg);
+    if (!bneck_body<float, 64, false, V, false, 0, false>(a, rl)) bneck_body<float, 64, false, V, false, 0, true>(a, rl);
+}
+
 // C = 16 with the class layer fused (FC = the class map's LUT kind); launch bounds as the C = 16 form
 template <typename T, int FC>
 __global__ void __launch_bounds__(256, (sizeof(T) == 2 ? BShape<16, 0>::OCC : BNECK_F32_OCC16)) bneck_cls_kernel(const BneckArgs a) {
@@ -1900,6 +1918,21 @@ hipError_t launch_bneck(const Knobs &k, int prec, int C, bool asym, int v, const
     return hipLaunchKernel(f->fun, dim3(g), dim3(f->threads), args, (size_t)f->lds, s);
 }
 
+hipError_t launch_bneck_guarded(const Knobs &k, int v, const BneckArgs &a, const BneckGuardArgs &g, hipStream_t s) {
+    const void *fun = v == 0 ? (const void *)bneck_guard64_kernel<0> : v == 1 ? (const void *)bneck_guard64_kernel<1>
+                    : v == 2 ? (const void *)bneck_guard64_kernel<2> : nullptr;
+    const BneckEntry *f = bneck_form(PREC_F32, 64, false, v, false, 0, false);   // the form it guards: threads, LDS
+    if (!fun || !f || a.tr) return hipErrorInvalidValue;
+    // the grid of launch_bneck, from this kernel's own occupancy
+    const int spc = occupancy_per_cu(fun, f->threads, (size_t)f->lds), n_cu = device_cus();
+    int cap = k.bneck_grid;
+    if (cap <= 0) cap = spc > 0 && n_cu > 0 ? (k.bneck_grid < 0 ? std::max(1, spc / -k.bneck_grid) : spc) * n_cu : 2048;
+    int grid = a.ntiles < cap ? a.ntiles : cap;
+    grid = (grid + 7) & ~7;
+    void *args[] = {const_cast<BneckArgs *>(&a), const_cast<BneckGuardArgs *>(&g)};
+    return hipLaunchKernel(fun, dim3(grid), dim3(f->threads), args, (size_t)f->lds, s);
+}
+
 hipError_t launch_bneck_cls(const Knobs &k, int prec, const BneckArgs &a, hipStream_t s) {
     const int lk = a.lut && (a.lut_kind == 1 || a.lut_kind == 2) ? a.lut_kind : 0;
     const BneckEntry *f = bneck_form(prec, 16, false, 0, false, 0, false, lk);
@@ -1928,3 +1961,7 @@ int bneck_form_rows(int32_t *rows, int cap) {
 }
 
 }  // namespace bugseg
+
+// The paired C = 64 form (its own file) is part of this translation unit: its guarded fallbacks are
+// the kernels above, and the library's object list stays what its other builders name
+#include "bneck_pair_kernels.hip"

@@ -225,6 +225,29 @@ size_t bneck2_lds_bytes();
 int bneck2_slots_per_cu();
 hipError_t launch_bneck2(const Knobs &k, const BneckArgs &a, hipStream_t s);
 
+// ---- two consecutive fp32 C = 64 regular bottlenecks in one launch (bneck_pair_kernels.hip) ----------
+// a: the first block's launch arguments — x, its weights, rg (amax_in: x's range words, amax_out: the words of
+// the tensor between the blocks) and the pair's tile grid (tiles of th x tw, bneck_pair_shape; oy_base as the
+// regular C = 64 forms); b: the second block's — out, its weights, rg.amax_out. The launch assumes that every
+// range exponent of both blocks is 0 and leaves x's successor untouched when block A's are not; the guarded
+// launches that follow it settle the rest.
+struct BneckPairArgs {
+    BneckArgs a, b;
+};
+void bneck_pair_shape(int &th, int &tw, int &threads, size_t &lds);
+hipError_t launch_bneck_pair(const Knobs &k, const BneckPairArgs &a, hipStream_t s);
+// The unpaired launch of one block of a pair as its fallback (bneck_kernels.hip): every workgroup evaluates
+// block A's exponents from the measured max |x| (ra.amax_in) and block B's from the measured max |y|
+// (rb.amax_in), both committed by then, and returns at once when all are 0 — the pair's result stands.
+// Otherwise the launch runs as launch_bneck would with tile variant v (0 .. 2). clear: range words the launch
+// zeroes before it runs (the first block's fallback clears the words of the pair's output, which the pair
+// filled from a speculation that failed), or null.
+struct BneckGuardArgs {
+    RangeArgs ra, rb;
+    float *clear;
+};
+hipError_t launch_bneck_guarded(const Knobs &k, int v, const BneckArgs &a, const BneckGuardArgs &g, hipStream_t s);
+
 // ---- fused upsampling bottleneck (up_kernels.hip) ----------------------------------------------
 struct UpArgs {
     const void *x;            // block input (B, h, w, Cin) NHWC

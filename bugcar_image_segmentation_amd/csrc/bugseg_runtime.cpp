@@ -221,9 +221,71 @@ struct WinPlan {
     }
 };
 
+// ---- the pair overlay (bneck_pair_kernels.hip). The plan keeps one op per block; a forward runs ops
+// i and i + 1 as one paired launch where the overlay has a pair (i, i + 1) and both lie in the forward's op range.
+// BNECK_PAIR64 = 0 builds a library without it (A/B builds).
+#ifndef BNECK_PAIR64
+#define BNECK_PAIR64 1
+#endif
+// What the walk needs of an op: ok — a fused fp32 C = 64 regular d = 1 bottleneck on an h x w grid in an untransposed
+// form, before the row-windowed decoder ops; in, out — which of the arena's two activation buffers it reads and
+// writes (0, 1; -1: another buffer).
+struct PairCand { bool ok = false; int h = 0, w = 0, in = -1, out = -1; };
+// The pairs' first ops: left to right, op i with op i + 1 when both are candidates on one grid, i + 1 reads what i
+// writes and writes the buffer i reads (the arena's ping-pong).
+std::vector<int> pair_firsts(const std::vector<PairCand> &c) {
+    std::vector<int> f;
+    for (size_t i = 0; i + 1 < c.size(); ++i) {
+        const PairCand &p = c[i], &q = c[i + 1];
+        if (p.ok && q.ok && p.h == q.h && p.w == q.w && p.in >= 0 && p.out >= 0 && p.in != p.out && q.in == p.out && q.out == p.in) {
+            f.push_back((int)i);
+            ++i;
+        }
+    }
+    return f;
+}
+// What each op of an n-op plan does in a forward over ops [first_op, last_op), and where. A paired launch reads
+// x where op i would and writes where op i would (the buffer of the tensor it skips), so everything after a pair
+// lives in the other buffer than the plan says: flip[k] = 1. A pair cut by the op range runs as its two plain
+// launches through a spare buffer — the first writes it, the second reads it and writes where the pair would — so
+// where every tensor lives does not depend on how a forward was cut into calls.
+enum { PA_PLAIN = 0, PA_PAIR = 1, PA_SKIP = 2, PA_LONE_FIRST = 3, PA_LONE_SECOND = 4 };
+void pair_actions(int n, const std::vector<int> &firsts, int first_op, int last_op, int *act, int *flip) {
+    for (int k = 0; k < n; ++k) { act[k] = PA_PLAIN; flip[k] = 0; }
+    for (const int i : firsts) {
+        if (i < 0 || i + 1 >= n) continue;
+        const bool both = first_op <= i && i + 1 < last_op;
+        act[i] = both ? PA_PAIR : PA_LONE_FIRST;
+        act[i + 1] = both ? PA_SKIP : PA_LONE_SECOND;
+        for (int k = i + 2; k < n; ++k) flip[k] ^= 1;
+    }
+}
+// One pair of the overlay: the paired launch and the two guarded fallbacks behind it, buffers bound
+struct PairOp {
+    int first = 0, var_a = 0, var_b = 0;
+    BneckPairArgs args{};
+    BneckArgs fa{}, fb{};
+    BneckGuardArgs ga{}, gb{};
+};
+
 struct Plan {
     int B = 0, H = 0, W = 0;
     std::vector<Op> ops;
+    // the pair overlay: the pairs, each op's flip (pair_actions), and the buffers it moves tensors between
+    std::vector<PairOp> pairs;
+    std::vector<int> flip;
+    unsigned char *X[2] = {nullptr, nullptr}, *spare = nullptr;
+    const PairOp *pair_at(int i) const {
+        for (const PairOp &p : pairs)
+            if (p.first == i) return &p;
+        return nullptr;
+    }
+    // 1: op i is a pair's first op, 2: its second, 0: neither
+    int pair_role(int i) const {
+        for (const PairOp &p : pairs)
+            if (p.first == i || p.first + 1 == i) return i - p.first + 1;
+        return 0;
+    }
     std::vector<WinPlan> wins;   // windowed forms of this plan, by window (window_plan); dropped with the plan
     size_t act_bytes = 0;        // the arena's activation and pool-index part (before the range words)
     float *words = nullptr;  // fp32 mode: RNG_SLOTS range words per measured tensor (block 0: the engine input)
@@ -1304,6 +1366,51 @@ Launch cls_fused_launch(const BneckLaunch &q, const ConvArgs &l) {
     return f;
 }
 
+// The pair overlay of the plan just built (Plan::pairs, Plan::flip). Pairs exist in fp32, in the fused
+// plan, with no C = 64 tile variant forced, where the spare buffer holds a C = 64 tensor; the decoder's last
+// WIN_OPS ops keep their own (row-windowed) launches.
+void build_pairs(bugseg_ctx *ctx, size_t spare_bytes) {
+    Plan &pl = ctx->plan;
+    const int n = (int)pl.ops.size();
+    pl.pairs.clear();
+    pl.flip.assign((size_t)n, 0);
+    const Knobs &k = ctx->knobs;
+    if (!BNECK_PAIR64 || ctx->prec != PREC_F32 || k.no_fuse || k.bneck_variant >= 0 || k.bneck_variant_c64 >= 0) return;
+    auto buf = [&](const void *p) { return p == pl.X[0] ? 0 : p == pl.X[1] ? 1 : -1; };
+    std::vector<PairCand> c((size_t)n);
+    for (int i = 0; i < n - WIN_OPS; ++i) {
+        const BneckLaunch *b = pl.ops[(size_t)i].bneck();
+        if (!b || !pl.ops[(size_t)i].regular(64, b->a.H) || b->a.tr || b->cls || b->win || b->var < 0 || b->var > 2) continue;
+        if (b->a.x_bytes > spare_bytes) continue;
+        c[(size_t)i] = PairCand{true, b->a.H, b->a.W, buf(b->a.x), buf(b->a.out)};
+    }
+    const std::vector<int> firsts = pair_firsts(c);
+    std::vector<int> act((size_t)n);
+    pair_actions(n, firsts, 0, n, act.data(), pl.flip.data());
+    int th, tw, threads;
+    size_t lds;
+    bneck_pair_shape(th, tw, threads, lds);
+    for (const int i : firsts) {
+        const BneckLaunch &A = *pl.ops[(size_t)i].bneck(), &Bk = *pl.ops[(size_t)i + 1].bneck();
+        const bool f = pl.flip[(size_t)i] != 0;
+        auto at = [&](const void *p) { return (void *)pl.X[buf(p) ^ (f ? 1 : 0)]; };
+        PairOp p;
+        p.first = i; p.var_a = A.var; p.var_b = Bk.var;
+        p.args.a = A.a; p.args.b = Bk.a;
+        p.args.a.x = at(A.a.x);
+        p.args.b.out = at(A.a.out);           // where the skipped tensor would have gone
+        p.args.a.tiles_y = (A.a.H + th - 1) / th; p.args.a.tiles_x = (A.a.W + tw - 1) / tw;
+        p.args.a.ntiles = A.a.B * p.args.a.tiles_y * p.args.a.tiles_x;
+        p.args.a.oy_base = 0;
+        // the fallbacks: block A into the spare buffer, block B from it to the pair's output
+        p.fa = A.a; p.fa.x = p.args.a.x; p.fa.out = pl.spare;
+        p.fb = Bk.a; p.fb.x = pl.spare; p.fb.out = p.args.b.out;
+        p.ga.ra = A.a.rg; p.ga.rb = Bk.a.rg; p.ga.clear = Bk.a.rg.amax_out;
+        p.gb = p.ga; p.gb.clear = nullptr;
+        pl.pairs.push_back(p);
+    }
+}
+
 bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *stream = nullptr) {
     Plan &pl = ctx->plan;
     if (pl.arena && pl.B == B && pl.H == H && pl.W == W) return true;
@@ -1359,6 +1466,9 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
                     (double)B * l.Hout * l.Wout < 2147483648.0;
         if (pl.cls_ok) pl.cls_fused = cls_fused_launch(*q.bneck(), l);
     }
+    pl.X[0] = w.X[0]; pl.X[1] = w.X[1];
+    pl.spare = w.T[1];                  // (the fused plan's launches use T[0] alone: the down blocks' pooled scratch)
+    build_pairs(ctx, al(w.szT));
     pl.idx = w.idx;
     pl.idx_bytes = w.szIdx;
     pl.words = w.words;
@@ -1880,7 +1990,10 @@ static void bind(const bugseg_ctx *ctx, const Binding &b, bool first, bool last,
 // it. The walk direction (Knobs::tile_order) follows the number of launches the plan issues before the op
 // (Op::pos, counted at plan build from Op::launches), so a single op (bugseg_plan_launch_op) and an op range
 // walk as they do in the whole forward; the span slots are those bugseg_debug_set_spans armed.
-static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const WinPlan *wp = nullptr) {
+// overlay (a forward, not bugseg_plan_launch_op): the op runs where the pair overlay puts it (Plan::flip) — in the
+// other activation buffers after an odd number of pairs, a cut pair's halves through the spare buffer — and walks
+// as the launches really issued before it alternate: a pair is one launch where the plan counts two.
+static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const WinPlan *wp = nullptr, bool overlay = false) {
     const Plan &pl = ctx->plan;
     const int n = (int)pl.ops.size();
     if (pl.cls_on && i + 1 == n) return hipSuccess;   // (ran within op i - 1)
@@ -1889,10 +2002,48 @@ static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const W
     if (!pick) pick = fused ? &pl.cls_fused : &pl.ops[(size_t)i].l;
     Launch l = *pick;
     bind(ctx, pl.bound, i == 0, fused || i + 1 == n, l);
+    const int flip = overlay && !pl.pairs.empty() ? pl.flip[(size_t)i] : 0;
+    if (overlay && !pl.pairs.empty()) {
+        auto sw = [&](auto *&p) {
+            using P = std::remove_reference_t<decltype(p)>;
+            if (flip && (const void *)p == pl.X[0]) p = (P)pl.X[1];
+            else if (flip && (const void *)p == pl.X[1]) p = (P)pl.X[0];
+        };
+        if (ConvLaunch *c = std::get_if<ConvLaunch>(&l)) { sw(c->a.in); sw(c->a.out); sw(c->a.res); }
+        else if (UpLaunch *u = std::get_if<UpLaunch>(&l)) { sw(u->a.x); sw(u->a.out); }
+        else if (BneckLaunch *b = std::get_if<BneckLaunch>(&l)) {
+            sw(b->a.x); sw(b->a.out); sw(b->a.xin);
+            // a pair cut by the op range: its halves through the spare buffer (pair_actions)
+            const int role = pl.pair_role(i);
+            if (role == 1) b->a.out = pl.spare;
+            if (role == 2) { b->a.out = const_cast<void *>(b->a.x); b->a.x = pl.spare; }
+        }
+    }
     const int order = ctx->knobs.tile_order;   // 0 ascending, 1 alternating from ascending, 2 descending
-    const int rev = order == 2 ? 1 : order == 1 ? (pl.ops[(size_t)i].pos & 1) : 0;
+    const int rev = order == 2 ? 1 : order == 1 ? ((pl.ops[(size_t)i].pos & 1) ^ flip) : 0;
     unsigned long long *sp = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;   // (mfma_common.h: 64 slots x 64 B)
     return issue(ctx, l, rev, sp, s);
+}
+
+// The pair whose first op is i, in place of ops i and i + 1: the paired launch, then the two guarded fallbacks
+// (BneckGuardArgs), which return at once unless the pair's speculation on the range exponents failed.
+static hipError_t launch_pair(const bugseg_ctx *ctx, const PairOp &p, hipStream_t s) {
+    const Plan &pl = ctx->plan;
+    const int i = p.first, order = ctx->knobs.tile_order;
+    auto rev_of = [&](int k) { return order == 2 ? 1 : order == 1 ? ((pl.ops[(size_t)k].pos & 1) ^ pl.flip[(size_t)k]) : 0; };
+    BneckPairArgs a = p.args;
+    a.a.rev = rev_of(i);
+    a.a.span = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;
+    hipError_t e = launch_bneck_pair(ctx->knobs, a, s);
+    if (e != hipSuccess) return e;
+    BneckArgs fa = p.fa, fb = p.fb;
+    fa.rev = rev_of(i); fa.span = nullptr;
+    // armed spans (bugseg_debug_set_spans): op i's slots time the paired launch, op i + 1's its second fallback
+    fb.rev = rev_of(i) ^ (order == 1 ? 1 : 0);
+    fb.span = ctx->spans && i + 1 < ctx->spans_ops ? ctx->spans + 512 * (size_t)(i + 1) : nullptr;
+    e = launch_bneck_guarded(ctx->knobs, p.var_a, fa, p.ga, s);
+    if (e != hipSuccess) return e;
+    return launch_bneck_guarded(ctx->knobs, p.var_b, fb, p.gb, s);
 }
 
 static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H, int W, int out_kind, void *out,
@@ -1919,7 +2070,14 @@ static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H,
     // class rows [row0, row1) only (bugseg_enet_forward_bgr_rows); null: the full-frame launches
     const WinPlan *wp = window_plan(ctx, row0, row1);
     for (int i = first_op; i < last_op; ++i) {
-        hipError_t e = launch_op(ctx, i, (hipStream_t)stream, wp);
+        // a pair of the overlay with both ops in the range: one launch for ops i and i + 1
+        if (const PairOp *p = i + 1 < last_op ? pl.pair_at(i) : nullptr) {
+            hipError_t e = launch_pair(ctx, *p, (hipStream_t)stream);
+            if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, "pair launch " + std::to_string(i) + ": " + hipGetErrorString(e));
+            ++i;
+            continue;
+        }
+        hipError_t e = launch_op(ctx, i, (hipStream_t)stream, wp, true);
         if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, "conv launch " + std::to_string(i) + ": " + hipGetErrorString(e));
     }
     return BUGSEG_OK;
@@ -2455,9 +2613,47 @@ int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_
     const BneckLaunch *b = op >= 0 && op < (int)pl.ops.size() ? pl.ops[(size_t)op].bneck() : nullptr;
     if (!b || bytes != b->a.x_bytes) return fail(ctx, BUGSEG_EINVAL, "not a fused bottleneck launch, or not its output's size");
     DeviceGuard g(ctx->device);
-    hipError_t e = hipMemcpyAsync(dst_dev, b->a.out, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    // where a forward leaves it (launch_op's overlay): the other activation buffer after an odd number of pairs; a
+    // pair's first block in the spare buffer (written only when the pair was cut), its second where the pair writes
+    const void *src = b->a.out;
+    if (!pl.pairs.empty()) {
+        auto at = [&](const void *p) -> const void * {
+            if (!pl.flip[(size_t)op]) return p;
+            return p == pl.X[0] ? pl.X[1] : p == pl.X[1] ? pl.X[0] : p;
+        };
+        const int role = pl.pair_role(op);
+        src = role == 1 ? (const void *)pl.spare : role == 2 ? at(b->a.x) : at(b->a.out);
+    }
+    hipError_t e = hipMemcpyAsync(dst_dev, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("read block output: ") + hipGetErrorString(e));
     return BUGSEG_OK;
+}
+
+int bugseg_debug_pair_walk(int n, const int32_t *cand, int first_op, int last_op, int32_t *out) {
+    if (n < 0 || n > 4096 || (n && (!cand || !out)) || first_op < 0 || first_op > last_op || last_op > n)
+        return fail(nullptr, BUGSEG_EINVAL, "bad pair walk");
+    std::vector<PairCand> c((size_t)n);
+    for (int k = 0; k < n; ++k) c[(size_t)k] = PairCand{cand[5 * k] != 0, cand[5 * k + 1], cand[5 * k + 2], cand[5 * k + 3], cand[5 * k + 4]};
+    const std::vector<int> firsts = pair_firsts(c);
+    std::vector<int> act((size_t)n), flip((size_t)n);
+    pair_actions(n, firsts, first_op, last_op, act.data(), flip.data());
+    for (int k = 0; k < n; ++k) { out[2 * k] = act[(size_t)k]; out[2 * k + 1] = flip[(size_t)k]; }
+    return (int)firsts.size();
+}
+
+int bugseg_debug_pair_plan(bugseg_ctx *ctx, int32_t *rows, int cap) {
+    if (!ctx || cap < 0 || (cap && !rows)) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
+    const Plan &pl = ctx->plan;
+    if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
+    int th, tw, threads;
+    size_t lds;
+    bneck_pair_shape(th, tw, threads, lds);
+    for (int k = 0; k < (int)pl.pairs.size() && k < cap; ++k) {
+        const BneckArgs &a = pl.pairs[(size_t)k].args.a;
+        const int32_t v[8] = {pl.pairs[(size_t)k].first, th, tw, a.tiles_y, a.tiles_x, threads, (int32_t)lds, pl.flip[(size_t)pl.pairs[(size_t)k].first]};
+        std::memcpy(rows + 8 * k, v, sizeof(v));
+    }
+    return (int)pl.pairs.size();
 }
 
 int bugseg_debug_ctx_info(const bugseg_ctx *ctx, int what, int arg) {

@@ -506,6 +506,18 @@ int bugseg_debug_stage3_windows(int h, int y0, int y1, int n, const int32_t *blk
  * current plan, as the last forward left it, to dst_dev (`bytes` = its size, B * H * W * C elements). */
 int bugseg_debug_plan_windows(bugseg_ctx *ctx, int row0, int row1, int32_t *win);
 int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_t bytes, void *stream);
+/* Test hooks of the pair overlay (two consecutive fp32 C = 64 regular bottlenecks as one launch).
+ * bugseg_debug_pair_walk (host only, no device): the overlay's walk over an n-op plan described by cand[5k ..] =
+ * (candidate: a fused fp32 C = 64 regular d = 1 bottleneck outside the windowed decoder ops; grid rows; grid
+ * columns; the activation buffer it reads, 0 / 1 or -1; the one it writes) and a forward over ops [first_op,
+ * last_op). Returns the number of pairs and fills out[2k] = what op k does (0 its plain launch, 1 the paired
+ * launch of ops k and k + 1, 2 nothing: it ran within op k - 1, 3 / 4 the first / second half of a pair the op
+ * range cuts: plain launches through the spare buffer) and out[2k + 1] = 1 when the op's tensors live in the
+ * other activation buffer than the plan says. bugseg_debug_pair_plan: the pairs of the current plan, rows[8k ..] =
+ * (first op, tile rows, tile columns, tiles_y, tiles_x, threads, LDS bytes, flip of the first op) for k < cap;
+ * returns their number (0: none — another precision, BUGSEG_NO_FUSE, a forced C = 64 tile variant). */
+int bugseg_debug_pair_walk(int n, const int32_t *cand, int first_op, int last_op, int32_t *out);
+int bugseg_debug_pair_plan(bugseg_ctx *ctx, int32_t *rows, int cap);
 /* Test hook (tests/test_gpu_row_window.py): fill the activation arena and the pooling-index tensors of the
  * current plan with `byte`, on `stream`, so that a launch reading a row its producer did not write this
  * forward sees the fill and not a correct row left by an earlier one. */

@@ -41,6 +41,11 @@ def short(name):
     if m:   # the row-windowed stage-3 forms (bneck_kernels.hip WIN)
         asym = m.group(2) in ("1", "true")
         return f"bneck C{m.group(1)}{' asym' if asym else ''} {BNECK_SHAPES.get((int(m.group(1)), int(m.group(3))), '?')} windowed"
+    m = re.search(r"bneck_pair_kernel<(\d+), (\d+)>", name) or re.search(r"bneck_pair_kernelILi(\d+)ELi(\d+)E", name)
+    if m:   # two C64 blocks in one launch (bneck_pair_kernels.hip)
+        return f"bneck pair C64 {m.group(1)}x16"
+    if "bneck_guard64_kernel" in name:   # the pair's guarded fallbacks (return at once when the pair's result stands)
+        return "bneck C64 guard"
     if "bneck_cls_kernel" in name:
         return "bneck C16+classes 16x16"
     if "bneck2_f32_kernel" in name:
