@@ -1885,10 +1885,26 @@ int bneck_slots_per_cu(const Knobs &k, int prec, int C, bool asym, int v, bool t
         // per launch; bneck2_kernels.hip says why)
         return prec == PREC_F32 && !asym && !tr && cin == 0 && k.bneck2 ? bneck2_slots_per_cu() : 0;
     }
-    // (cached per device and form: launch_bneck asks on every launch; bugseg_runtime.cpp occupancy_per_cu)
+    // (cached per device and form: resident_grid asks the same on every launch; bugseg_runtime.cpp occupancy_per_cu)
     const BneckEntry *e = bneck_form(prec, C, asym, v, tr, cin, win);
     if (!e || allow_dynamic_lds(e->fun) != hipSuccess) return 0;
     return occupancy_per_cu(e->fun, e->threads, (size_t)e->lds);
+}
+
+// The grid of a fused-bottleneck launch of `fun` over ntiles tiles: one round of resident workgroups (each walks
+// ntiles / grid tiles, staging its weights once), from the kernel's own occupancy, or 2048 where that is unknown;
+// rounded up to the tile walk's 8 groups. BUGSEG_BNECK_GRID=cap sets the cap instead (A/B knob, 0 = resident slots; a
+// test forces multi-tile walks with it at any shape); -k: 1/k of the resident slots, at least one per CU — leaves
+// room for a concurrent shard's launch on another stream (A/B knob).
+// frac = false (launch_bneck_cls) reads -k as 0: historical — the opt-in class-fused form never took part in that A/B.
+int resident_grid(const Knobs &k, const void *fun, int threads, size_t lds, int ntiles, bool frac) {
+    int cap = k.bneck_grid;
+    if (cap <= 0) {
+        const int spc = occupancy_per_cu(fun, threads, lds), n_cu = device_cus();
+        const int per = frac && cap < 0 ? std::max(1, spc / -cap) : spc;
+        cap = spc > 0 && n_cu > 0 ? per * n_cu : 2048;
+    }
+    return ((ntiles < cap ? ntiles : cap) + 7) & ~7;
 }
 
 hipError_t launch_bneck(const Knobs &k, int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin, bool win) {
@@ -1900,20 +1916,7 @@ hipError_t launch_bneck(const Knobs &k, int prec, int C, bool asym, int v, const
         hipError_t e = allow_dynamic_lds(f->fun);
         if (e != hipSuccess) return e;
     }
-    // grid: one round of resident workgroups (each walks ntiles / grid tiles, staging its weights
-    // once), or the earlier fixed cap of 2048 (BUGSEG_BNECK_GRID=cap: A/B knob, 0 = resident slots; a test
-    // forces multi-tile walks with it at any shape)
-    const int n_cu = device_cus();
-    int cap = k.bneck_grid;
-    if (cap <= 0) {
-        // (BUGSEG_BNECK_GRID=-k: 1/k of the resident slots, at least one per CU — leaves room for a
-        // concurrent shard's launch on another stream; A/B knob)
-        const int spc = bneck_slots_per_cu(k, prec, C, asym, v, a.tr != 0, cin, win);
-        const int per = k.bneck_grid < 0 ? std::max(1, spc / -k.bneck_grid) : spc;
-        cap = spc > 0 && n_cu > 0 ? per * n_cu : 2048;
-    }
-    int g = a.ntiles < cap ? a.ntiles : cap;
-    g = (g + 7) & ~7;
+    const int g = resident_grid(k, f->fun, f->threads, (size_t)f->lds, a.ntiles);
     void *args[] = {const_cast<BneckArgs *>(&a)};
     return hipLaunchKernel(f->fun, dim3(g), dim3(f->threads), args, (size_t)f->lds, s);
 }
@@ -1923,12 +1926,7 @@ hipError_t launch_bneck_guarded(const Knobs &k, int v, const BneckArgs &a, const
                     : v == 2 ? (const void *)bneck_guard64_kernel<2> : nullptr;
     const BneckEntry *f = bneck_form(PREC_F32, 64, false, v, false, 0, false);   // the form it guards: threads, LDS
     if (!fun || !f || a.tr) return hipErrorInvalidValue;
-    // the grid of launch_bneck, from this kernel's own occupancy
-    const int spc = occupancy_per_cu(fun, f->threads, (size_t)f->lds), n_cu = device_cus();
-    int cap = k.bneck_grid;
-    if (cap <= 0) cap = spc > 0 && n_cu > 0 ? (k.bneck_grid < 0 ? std::max(1, spc / -k.bneck_grid) : spc) * n_cu : 2048;
-    int grid = a.ntiles < cap ? a.ntiles : cap;
-    grid = (grid + 7) & ~7;
+    const int grid = resident_grid(k, fun, f->threads, (size_t)f->lds, a.ntiles);
     void *args[] = {const_cast<BneckArgs *>(&a), const_cast<BneckGuardArgs *>(&g)};
     return hipLaunchKernel(fun, dim3(grid), dim3(f->threads), args, (size_t)f->lds, s);
 }
@@ -1941,11 +1939,7 @@ hipError_t launch_bneck_cls(const Knobs &k, int prec, const BneckArgs &a, hipStr
         hipError_t e = allow_dynamic_lds(f->fun);
         if (e != hipSuccess) return e;
     }
-    // one round of resident workgroups, as launch_bneck
-    const int spc = occupancy_per_cu(f->fun, f->threads, (size_t)f->lds), n_cu = device_cus();
-    const int cap = k.bneck_grid > 0 ? k.bneck_grid : spc > 0 && n_cu > 0 ? spc * n_cu : 2048;
-    int g = a.ntiles < cap ? a.ntiles : cap;
-    g = (g + 7) & ~7;
+    const int g = resident_grid(k, f->fun, f->threads, (size_t)f->lds, a.ntiles, false);
     void *args[] = {const_cast<BneckArgs *>(&a)};
     return hipLaunchKernel(f->fun, dim3(g), dim3(f->threads), args, (size_t)f->lds, s);
 }

@@ -334,16 +334,7 @@ void bneck_pair_shape(int &th, int &tw, int &threads, size_t &lds) {
 hipError_t launch_bneck_pair(const Knobs &k, const BneckPairArgs &a, hipStream_t s) {
     hipError_t e = allow_dynamic_lds(pair_fun());
     if (e != hipSuccess) return e;
-    // one round of resident workgroups, each walking its tiles with its weights staged once (launch_bneck)
-    const int n_cu = device_cus();
-    int cap = k.bneck_grid;
-    if (cap <= 0) {
-        const int spc = occupancy_per_cu(pair_fun(), PairBuilt::NT, PairBuilt::LDS_BYTES);
-        const int per = k.bneck_grid < 0 ? std::max(1, spc / -k.bneck_grid) : spc;
-        cap = spc > 0 && n_cu > 0 ? per * n_cu : 2048;
-    }
-    int g = a.a.ntiles < cap ? a.a.ntiles : cap;
-    g = (g + 7) & ~7;
+    const int g = resident_grid(k, pair_fun(), PairBuilt::NT, PairBuilt::LDS_BYTES, a.a.ntiles);   // (bneck_kernels.hip)
     void *args[] = {const_cast<BneckPairArgs *>(&a)};
     return hipLaunchKernel(pair_fun(), dim3(g), dim3(PairBuilt::NT), args, PairBuilt::LDS_BYTES, s);
 }

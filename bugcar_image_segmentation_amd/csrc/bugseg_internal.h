@@ -215,6 +215,8 @@ size_t bneck_lds_bytes(int prec, int C, bool asym, int v, int cin = 0, bool cls 
 // and row-dilated 4 x 80 tiles; the C = 64 / 16 regular forms take their window in the plain form
 int bneck_slots_per_cu(const Knobs &k, int prec, int C, bool asym, int v, bool tr, int cin = 0, bool win = false);
 hipError_t launch_bneck(const Knobs &k, int prec, int C, bool asym, int v, const BneckArgs &a, hipStream_t s, int cin = 0, bool win = false);
+// the grid of a fused-bottleneck launch (bneck_kernels.hip, where the knob's meaning is written down)
+int resident_grid(const Knobs &k, const void *fun, int threads, size_t lds, int ntiles, bool frac = true);
 // the C = 16 block with the class layer fused (variant 0, untransposed; tiles 15 apart: tiles_x =
 // ceil(W / 15), tiles_y = ceil(H / 15)); bneck_lds_bytes(..., cls = true) its LDS
 hipError_t launch_bneck_cls(const Knobs &k, int prec, const BneckArgs &a, hipStream_t s);

@@ -171,12 +171,15 @@ using Launch = std::variant<ConvLaunch, BneckLaunch, UpLaunch>;
 
 // A plan op: its full-frame launch and its accounting. Immutable between build_plan calls: a forward's input and
 // output (Binding) and a row window (WinPlan) go into a copy of the launch, never into the plan.
+// l is the plan's own launch, which bugseg_plan_info / _op / _launch_op describe and run; fwd is the launch as a
+// forward issues it outside a whole pair, on the buffers the pair overlay leaves it (build_pairs; without pairs: l).
 struct Op {
-    Launch l;
+    Launch l, fwd;
     double bytes = 0, flops = 0;
     double layer_bytes = -1;   // per-layer (unfused) algorithmic bytes of the work; -1: same as bytes
     int launches = 1;          // kernel launches the op issues (every form today: one)
     int pos = 0;               // launches the plan issues before this op (build_plan): its walk direction's parity
+    int fwd_odd = 0;           // that parity in a forward (build_pairs): a pair is one launch where the plan counts two
     double layer() const { return layer_bytes >= 0 ? layer_bytes : bytes; }
     const ConvLaunch *conv() const { return std::get_if<ConvLaunch>(&l); }
     const BneckLaunch *bneck() const { return std::get_if<BneckLaunch>(&l); }
@@ -223,7 +226,9 @@ struct WinPlan {
 
 // ---- the pair overlay (bneck_pair_kernels.hip). The plan keeps one op per block; a forward runs ops
 // i and i + 1 as one paired launch where the overlay has a pair (i, i + 1) and both lie in the forward's op range.
-// BNECK_PAIR64 = 0 builds a library without it (A/B builds).
+// pair_firsts and pair_actions are the whole rule: build_pairs turns them into finished launches when the plan is
+// built, enet_forward switches on the actions of its op range, and bugseg_debug_pair_walk shows the same two to the
+// tests. BNECK_PAIR64 = 0 builds a library without it (A/B builds).
 #ifndef BNECK_PAIR64
 #define BNECK_PAIR64 1
 #endif
@@ -260,32 +265,20 @@ void pair_actions(int n, const std::vector<int> &firsts, int first_op, int last_
         for (int k = i + 2; k < n; ++k) flip[k] ^= 1;
     }
 }
-// One pair of the overlay: the paired launch and the two guarded fallbacks behind it, buffers bound
+// One pair of the overlay: the paired launch, buffers bound, and the guards of the two fallbacks behind it, which run
+// the forward launches (Op::fwd) of ops first and first + 1. flip: of op first (pair_actions)
 struct PairOp {
-    int first = 0, var_a = 0, var_b = 0;
+    int first = 0, flip = 0;
     BneckPairArgs args{};
-    BneckArgs fa{}, fb{};
     BneckGuardArgs ga{}, gb{};
 };
 
 struct Plan {
     int B = 0, H = 0, W = 0;
     std::vector<Op> ops;
-    // the pair overlay: the pairs, each op's flip (pair_actions), and the buffers it moves tensors between
+    // the pair overlay (build_pairs): the pairs' first ops (pair_firsts), ascending, and pair k's launch
+    std::vector<int> firsts;
     std::vector<PairOp> pairs;
-    std::vector<int> flip;
-    unsigned char *X[2] = {nullptr, nullptr}, *spare = nullptr;
-    const PairOp *pair_at(int i) const {
-        for (const PairOp &p : pairs)
-            if (p.first == i) return &p;
-        return nullptr;
-    }
-    // 1: op i is a pair's first op, 2: its second, 0: neither
-    int pair_role(int i) const {
-        for (const PairOp &p : pairs)
-            if (p.first == i || p.first + 1 == i) return i - p.first + 1;
-        return 0;
-    }
     std::vector<WinPlan> wins;   // windowed forms of this plan, by window (window_plan); dropped with the plan
     size_t act_bytes = 0;        // the arena's activation and pool-index part (before the range words)
     float *words = nullptr;  // fp32 mode: RNG_SLOTS range words per measured tensor (block 0: the engine input)
@@ -297,11 +290,12 @@ struct Plan {
     std::vector<size_t> idx_bytes;
     // ENet's last bottleneck (C = 16) and the class layer as ONE launch (bneck_kernels.hip, class fusion;
     // opt-in, BUGSEG_CLS_FUSE=1: measured slower, see there): possible for this plan (cls_ok: the plan ends
-    // with that bottleneck feeding the class kernel; cls_fused is then that launch, its output unbound), and
+    // with that bottleneck feeding the class kernel; cls_fused is then that launch, its output unbound, and
+    // cls_fused_fwd the same of the two ops' forward launches, Op::fwd), and
     // taken by the last forward (cls_on: a class-map output, both ops in its range). The last op then launches
     // nothing; its plan_op tag is "fused".
     bool cls_ok = false, cls_on = false;
-    Launch cls_fused;
+    Launch cls_fused, cls_fused_fwd;
     Binding bound;           // the last forward's binding (in == nullptr: none since the plan was built)
 };
 
@@ -1366,48 +1360,70 @@ Launch cls_fused_launch(const BneckLaunch &q, const ConvArgs &l) {
     return f;
 }
 
-// The pair overlay of the plan just built (Plan::pairs, Plan::flip). Pairs exist in fp32, in the fused
-// plan, with no C = 64 tile variant forced, where the spare buffer holds a C = 64 tensor; the decoder's last
-// WIN_OPS ops keep their own (row-windowed) launches.
-void build_pairs(bugseg_ctx *ctx, size_t spare_bytes) {
+// The plan's launch l as a forward issues it where the pair overlay has flipped the activation buffers X: every
+// tensor the plan puts in one of them lies in the other. The one place that knows which pointers of a launch are
+// tensors in those buffers; used while the plan is built only (build_pairs).
+Launch flipped(const Launch &l, unsigned char *const X[2]) {
+    Launch f = l;
+    auto mv = [&](auto *&p) {
+        using P = std::remove_reference_t<decltype(p)>;
+        if ((const void *)p == X[0]) p = (P)X[1];
+        else if ((const void *)p == X[1]) p = (P)X[0];
+    };
+    if (ConvLaunch *c = std::get_if<ConvLaunch>(&f)) { mv(c->a.in); mv(c->a.out); mv(c->a.res); }
+    else if (UpLaunch *u = std::get_if<UpLaunch>(&f)) { mv(u->a.x); mv(u->a.out); }
+    else if (BneckLaunch *b = std::get_if<BneckLaunch>(&f)) { mv(b->a.x); mv(b->a.out); mv(b->a.xin); }
+    return f;
+}
+
+// The pair overlay of the plan just built: the pairs (Plan::firsts, Plan::pairs) and every op's forward
+// launch and walk parity (Op::fwd, Op::fwd_odd), final from here on. Pairs exist in fp32, in the fused plan, with no
+// C = 64 tile variant forced, where the spare buffer holds a C = 64 tensor; the decoder's last WIN_OPS ops keep their
+// own (row-windowed) launches. X: the arena's two activation buffers.
+void build_pairs(bugseg_ctx *ctx, unsigned char *const X[2], unsigned char *spare, size_t spare_bytes) {
     Plan &pl = ctx->plan;
     const int n = (int)pl.ops.size();
     pl.pairs.clear();
-    pl.flip.assign((size_t)n, 0);
+    pl.firsts.clear();
     const Knobs &k = ctx->knobs;
-    if (!BNECK_PAIR64 || ctx->prec != PREC_F32 || k.no_fuse || k.bneck_variant >= 0 || k.bneck_variant_c64 >= 0) return;
-    auto buf = [&](const void *p) { return p == pl.X[0] ? 0 : p == pl.X[1] ? 1 : -1; };
-    std::vector<PairCand> c((size_t)n);
-    for (int i = 0; i < n - WIN_OPS; ++i) {
-        const BneckLaunch *b = pl.ops[(size_t)i].bneck();
-        if (!b || !pl.ops[(size_t)i].regular(64, b->a.H) || b->a.tr || b->cls || b->win || b->var < 0 || b->var > 2) continue;
-        if (b->a.x_bytes > spare_bytes) continue;
-        c[(size_t)i] = PairCand{true, b->a.H, b->a.W, buf(b->a.x), buf(b->a.out)};
+    if (BNECK_PAIR64 && ctx->prec == PREC_F32 && !k.no_fuse && k.bneck_variant < 0 && k.bneck_variant_c64 < 0) {
+        auto buf = [&](const void *p) { return p == X[0] ? 0 : p == X[1] ? 1 : -1; };
+        std::vector<PairCand> c((size_t)n);
+        for (int i = 0; i < n - WIN_OPS; ++i) {
+            const BneckLaunch *b = pl.ops[(size_t)i].bneck();
+            if (!b || !pl.ops[(size_t)i].regular(64, b->a.H) || b->a.tr || b->cls || b->win || b->var < 0 || b->var > 2) continue;
+            if (b->a.x_bytes > spare_bytes) continue;
+            c[(size_t)i] = PairCand{true, b->a.H, b->a.W, buf(b->a.x), buf(b->a.out)};
+        }
+        pl.firsts = pair_firsts(c);
     }
-    const std::vector<int> firsts = pair_firsts(c);
-    std::vector<int> act((size_t)n);
-    pair_actions(n, firsts, 0, n, act.data(), pl.flip.data());
+    std::vector<int> act((size_t)n), flip((size_t)n);
+    pair_actions(n, pl.firsts, 0, n, act.data(), flip.data());
+    for (int i = 0; i < n; ++i) {
+        Op &op = pl.ops[(size_t)i];
+        op.fwd = flip[(size_t)i] ? flipped(op.l, X) : op.l;
+        op.fwd_odd = (op.pos & 1) ^ flip[(size_t)i];
+    }
     int th, tw, threads;
     size_t lds;
     bneck_pair_shape(th, tw, threads, lds);
-    for (const int i : firsts) {
-        const BneckLaunch &A = *pl.ops[(size_t)i].bneck(), &Bk = *pl.ops[(size_t)i + 1].bneck();
-        const bool f = pl.flip[(size_t)i] != 0;
-        auto at = [&](const void *p) { return (void *)pl.X[buf(p) ^ (f ? 1 : 0)]; };
+    for (int i = 0; i < n; ++i) {
+        if (act[(size_t)i] != PA_PAIR) continue;
+        BneckArgs &A = std::get<BneckLaunch>(pl.ops[(size_t)i].fwd).a, &Bk = std::get<BneckLaunch>(pl.ops[(size_t)i + 1].fwd).a;
         PairOp p;
-        p.first = i; p.var_a = A.var; p.var_b = Bk.var;
-        p.args.a = A.a; p.args.b = Bk.a;
-        p.args.a.x = at(A.a.x);
-        p.args.b.out = at(A.a.out);           // where the skipped tensor would have gone
-        p.args.a.tiles_y = (A.a.H + th - 1) / th; p.args.a.tiles_x = (A.a.W + tw - 1) / tw;
-        p.args.a.ntiles = A.a.B * p.args.a.tiles_y * p.args.a.tiles_x;
+        p.first = i; p.flip = flip[(size_t)i];
+        p.args.a = A; p.args.b = Bk;
+        p.args.b.out = A.out;                 // where the skipped tensor would have gone
+        p.args.a.tiles_y = (A.H + th - 1) / th; p.args.a.tiles_x = (A.W + tw - 1) / tw;
+        p.args.a.ntiles = A.B * p.args.a.tiles_y * p.args.a.tiles_x;
         p.args.a.oy_base = 0;
-        // the fallbacks: block A into the spare buffer, block B from it to the pair's output
-        p.fa = A.a; p.fa.x = p.args.a.x; p.fa.out = pl.spare;
-        p.fb = Bk.a; p.fb.x = pl.spare; p.fb.out = p.args.b.out;
-        p.ga.ra = A.a.rg; p.ga.rb = Bk.a.rg; p.ga.clear = Bk.a.rg.amax_out;
+        p.ga.ra = A.rg; p.ga.rb = Bk.rg; p.ga.clear = Bk.rg.amax_out;
         p.gb = p.ga; p.gb.clear = nullptr;
         pl.pairs.push_back(p);
+        // outside the whole pair (a forward's op range cuts it; the pair's guarded fallbacks): block A into the spare
+        // buffer, block B from it to the pair's output
+        A.out = spare;
+        Bk.x = spare; Bk.out = p.args.b.out;
     }
 }
 
@@ -1456,6 +1472,8 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
     pl.ops = std::move(w.ops);
     int issued = 0;
     for (Op &op : pl.ops) { op.pos = issued; issued += op.launches; }
+    // the spare buffer: T[1] (the fused plan's launches use T[0] alone: the down blocks' pooled scratch)
+    build_pairs(ctx, w.X, w.T[1], al(w.szT));
     pl.cls_ok = false;
     pl.cls_on = false;
     pl.bound = Binding();
@@ -1464,11 +1482,11 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
         const Op &q = pl.ops[pl.ops.size() - 2];
         pl.cls_ok = q.regular(16, l.Hin) && q.bneck()->a.out == l.in && l.B == q.bneck()->a.B && l.Win == q.bneck()->a.W &&
                     (double)B * l.Hout * l.Wout < 2147483648.0;
-        if (pl.cls_ok) pl.cls_fused = cls_fused_launch(*q.bneck(), l);
+        if (pl.cls_ok) {
+            pl.cls_fused = cls_fused_launch(*q.bneck(), l);
+            pl.cls_fused_fwd = cls_fused_launch(std::get<BneckLaunch>(q.fwd), std::get<ConvLaunch>(pl.ops.back().fwd).a);
+        }
     }
-    pl.X[0] = w.X[0]; pl.X[1] = w.X[1];
-    pl.spare = w.T[1];                  // (the fused plan's launches use T[0] alone: the down blocks' pooled scratch)
-    build_pairs(ctx, al(w.szT));
     pl.idx = w.idx;
     pl.idx_bytes = w.szIdx;
     pl.words = w.words;
@@ -1597,8 +1615,9 @@ const WinPlan *window_plan(bugseg_ctx *ctx, int row0, int row1) {
     if (!(o[0].up_on(H / 8) && o[1].regular(64, H / 4) && o[2].regular(64, H / 4) && o[3].up_on(H / 4) &&
           o[4].regular(16, H / 2) && o[5].class_kernel() && o[5].conv()->a.Hg == H / 2))
         return nullptr;
-    // the op k blocks before the 128 -> 64 block, as a fused bottleneck (null: none, or another launch form)
-    auto s3b = [&](int k) { return n - WIN_OPS - 1 - k >= 0 ? pl.ops[(size_t)(n - WIN_OPS - 1 - k)].bneck() : nullptr; };
+    // the op k blocks before the 128 -> 64 block, as a fused bottleneck (null: none, or another launch form). Only
+    // forwards take a window, so the windowed launches are narrowed from the forward launches (Op::fwd)
+    auto s3b = [&](int k) { return n - WIN_OPS - 1 - k >= 0 ? std::get_if<BneckLaunch>(&pl.ops[(size_t)(n - WIN_OPS - 1 - k)].fwd) : nullptr; };
     // The tile form of block q for the `rows` rows it must produce, into r: the picker's choice for the window,
     // else (a thin window: none efficient enough) the full frame's. s3: among the untransposed forms with a
     // windowed kernel. -> image rows per tile row (0: no form).
@@ -1623,7 +1642,7 @@ const WinPlan *window_plan(bugseg_ctx *ctx, int row0, int row1) {
         WinOp &r = w.op[k];
         r.y0 = win[k][0]; r.y1 = win[k][1];
         r.tiles_y = (r.y1 - r.y0 + r.te - 1) / r.te;
-        r.l = narrow(o[k].l, r, false, row0, row1);
+        r.l = narrow(o[k].fwd, r, false, row0, row1);
     }
     // on into stage 3: the ops before the 128 -> 64 block, while they are fused C = 128 bottlenecks on its input
     // grid whose form has a windowed kernel (fp32). BUGSEG_ROW_WINDOW_S3=0: the decoder's windows only (A/B)
@@ -1945,8 +1964,22 @@ static hipError_t dispatch(const bugseg_ctx *c, const BneckLaunch &l, hipStream_
     return l.cls ? launch_bneck_cls(c->knobs, c->prec, l.a, s)
                  : launch_bneck(c->knobs, c->prec, l.C, l.asym, l.var, l.a, s, l.cin, l.win);
 }
-// One launch record to its kernel, with its launch-span slots (or null) and its tile walk direction: the one
-// place that sets them.
+// The tile walk direction of op i's launch (Knobs::tile_order: 0 ascending, 1 alternating from ascending (DESIGN
+// 6.10), 2 descending). Alternating follows the parity of the launches issued before the op, so a single op and an
+// op range walk as they do in the whole run: of the plan's own launches (Op::pos), or (fwd) of a forward's, where a
+// pair is one launch (Op::fwd_odd).
+static int walk_rev(const bugseg_ctx *ctx, int i, bool fwd) {
+    const Op &o = ctx->plan.ops[(size_t)i];
+    const int order = ctx->knobs.tile_order;
+    return order == 2 ? 1 : order == 1 ? (fwd ? o.fwd_odd : o.pos & 1) : 0;
+}
+// Op i's launch-span slots, where bugseg_debug_set_spans armed them (mfma_common.h: 64 slots x 64 B), else null
+static unsigned long long *span_slots(const bugseg_ctx *ctx, int i) {
+    return ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;
+}
+
+// One launch record to its kernel, with its launch-span slots (or null) and its tile walk direction (span_slots,
+// walk_rev): the one place that sets them for a single launch; launch_pair sets its three launches' from the same two.
 static hipError_t issue(const bugseg_ctx *ctx, Launch &l, int rev, unsigned long long *span, hipStream_t s) {
     return std::visit([&](auto &r) {
         r.a.span = span;
@@ -1984,66 +2017,40 @@ static void bind(const bugseg_ctx *ctx, const Binding &b, bool first, bool last,
     }
 }
 
-// One plan op for the last forward's binding (Plan::bound). launch_op only picks the op's record — its windowed
-// launch when wp (a row-windowed forward, window_plan) has one, the class-fused launch when the forward took it
-// (the last op then issues nothing; nothing follows it), else the full-frame launch — binds a copy and issues
-// it. The walk direction (Knobs::tile_order) follows the number of launches the plan issues before the op
-// (Op::pos, counted at plan build from Op::launches), so a single op (bugseg_plan_launch_op) and an op range
-// walk as they do in the whole forward; the span slots are those bugseg_debug_set_spans armed.
-// overlay (a forward, not bugseg_plan_launch_op): the op runs where the pair overlay puts it (Plan::flip) — in the
-// other activation buffers after an odd number of pairs, a cut pair's halves through the spare buffer — and walks
-// as the launches really issued before it alternate: a pair is one launch where the plan counts two.
-static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const WinPlan *wp = nullptr, bool overlay = false) {
+// One plan op for the last forward's binding (Plan::bound). Every record is final once the plan is built; launch_op
+// only picks the op's — its windowed launch when wp (a row-windowed forward, window_plan) has one, the class-fused
+// launch when the forward took it (the last op then issues nothing; nothing follows it), else the full-frame launch
+// — binds a copy and issues it. fwd: the launch of a forward (Op::fwd: where the pair overlay puts the op, walking as
+// the launches really issued before it alternate), not the plan's own (bugseg_plan_launch_op).
+static hipError_t launch_op(const bugseg_ctx *ctx, int i, hipStream_t s, const WinPlan *wp = nullptr, bool fwd = false) {
     const Plan &pl = ctx->plan;
     const int n = (int)pl.ops.size();
     if (pl.cls_on && i + 1 == n) return hipSuccess;   // (ran within op i - 1)
     const bool fused = pl.cls_on && i + 2 == n;
     const Launch *pick = wp ? wp->launch_of(i, n) : nullptr;
-    if (!pick) pick = fused ? &pl.cls_fused : &pl.ops[(size_t)i].l;
+    if (!pick) pick = fused ? (fwd ? &pl.cls_fused_fwd : &pl.cls_fused) : fwd ? &pl.ops[(size_t)i].fwd : &pl.ops[(size_t)i].l;
     Launch l = *pick;
     bind(ctx, pl.bound, i == 0, fused || i + 1 == n, l);
-    const int flip = overlay && !pl.pairs.empty() ? pl.flip[(size_t)i] : 0;
-    if (overlay && !pl.pairs.empty()) {
-        auto sw = [&](auto *&p) {
-            using P = std::remove_reference_t<decltype(p)>;
-            if (flip && (const void *)p == pl.X[0]) p = (P)pl.X[1];
-            else if (flip && (const void *)p == pl.X[1]) p = (P)pl.X[0];
-        };
-        if (ConvLaunch *c = std::get_if<ConvLaunch>(&l)) { sw(c->a.in); sw(c->a.out); sw(c->a.res); }
-        else if (UpLaunch *u = std::get_if<UpLaunch>(&l)) { sw(u->a.x); sw(u->a.out); }
-        else if (BneckLaunch *b = std::get_if<BneckLaunch>(&l)) {
-            sw(b->a.x); sw(b->a.out); sw(b->a.xin);
-            // a pair cut by the op range: its halves through the spare buffer (pair_actions)
-            const int role = pl.pair_role(i);
-            if (role == 1) b->a.out = pl.spare;
-            if (role == 2) { b->a.out = const_cast<void *>(b->a.x); b->a.x = pl.spare; }
-        }
-    }
-    const int order = ctx->knobs.tile_order;   // 0 ascending, 1 alternating from ascending, 2 descending
-    const int rev = order == 2 ? 1 : order == 1 ? ((pl.ops[(size_t)i].pos & 1) ^ flip) : 0;
-    unsigned long long *sp = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;   // (mfma_common.h: 64 slots x 64 B)
-    return issue(ctx, l, rev, sp, s);
+    return issue(ctx, l, walk_rev(ctx, i, fwd), span_slots(ctx, i), s);
 }
 
-// The pair whose first op is i, in place of ops i and i + 1: the paired launch, then the two guarded fallbacks
-// (BneckGuardArgs), which return at once unless the pair's speculation on the range exponents failed.
+// Pair p in place of ops i = p.first and i + 1: the paired launch, then the two ops' forward launches as its guarded
+// fallbacks (BneckGuardArgs), which return at once unless the pair's speculation on the range exponents failed. The
+// pair and the first fallback walk as op i, the second as op i + 1. Armed spans: op i's slots time the paired launch,
+// op i + 1's its second fallback.
 static hipError_t launch_pair(const bugseg_ctx *ctx, const PairOp &p, hipStream_t s) {
-    const Plan &pl = ctx->plan;
-    const int i = p.first, order = ctx->knobs.tile_order;
-    auto rev_of = [&](int k) { return order == 2 ? 1 : order == 1 ? ((pl.ops[(size_t)k].pos & 1) ^ pl.flip[(size_t)k]) : 0; };
+    const int i = p.first;
+    const BneckLaunch &A = std::get<BneckLaunch>(ctx->plan.ops[(size_t)i].fwd), &Bk = std::get<BneckLaunch>(ctx->plan.ops[(size_t)i + 1].fwd);
     BneckPairArgs a = p.args;
-    a.a.rev = rev_of(i);
-    a.a.span = ctx->spans && i < ctx->spans_ops ? ctx->spans + 512 * (size_t)i : nullptr;
+    BneckArgs fa = A.a, fb = Bk.a;
+    a.a.rev = fa.rev = walk_rev(ctx, i, true);
+    a.a.span = span_slots(ctx, i); fa.span = nullptr;
+    fb.rev = walk_rev(ctx, i + 1, true);
+    fb.span = span_slots(ctx, i + 1);
     hipError_t e = launch_bneck_pair(ctx->knobs, a, s);
-    if (e != hipSuccess) return e;
-    BneckArgs fa = p.fa, fb = p.fb;
-    fa.rev = rev_of(i); fa.span = nullptr;
-    // armed spans (bugseg_debug_set_spans): op i's slots time the paired launch, op i + 1's its second fallback
-    fb.rev = rev_of(i) ^ (order == 1 ? 1 : 0);
-    fb.span = ctx->spans && i + 1 < ctx->spans_ops ? ctx->spans + 512 * (size_t)(i + 1) : nullptr;
-    e = launch_bneck_guarded(ctx->knobs, p.var_a, fa, p.ga, s);
-    if (e != hipSuccess) return e;
-    return launch_bneck_guarded(ctx->knobs, p.var_b, fb, p.gb, s);
+    if (e == hipSuccess) e = launch_bneck_guarded(ctx->knobs, A.var, fa, p.ga, s);
+    if (e == hipSuccess) e = launch_bneck_guarded(ctx->knobs, Bk.var, fb, p.gb, s);
+    return e;
 }
 
 static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H, int W, int out_kind, void *out,
@@ -2069,16 +2076,22 @@ static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H,
     pl.cls_on = pl.cls_ok && out_kind != BUGSEG_OUT_LOGITS_F32 && first_op <= nops - 2 && last_op == nops;
     // class rows [row0, row1) only (bugseg_enet_forward_bgr_rows); null: the full-frame launches
     const WinPlan *wp = window_plan(ctx, row0, row1);
+    // what each op does in this op range (pair_actions, the walk bugseg_debug_pair_walk shows): a pair with both ops
+    // in the range is one launch for ops i and i + 1, every other op its forward launch
+    std::vector<int> act(2 * (size_t)nops);           // (the flips behind the actions: in the records already)
+    pair_actions(nops, pl.firsts, first_op, last_op, act.data(), act.data() + nops);
     for (int i = first_op; i < last_op; ++i) {
-        // a pair of the overlay with both ops in the range: one launch for ops i and i + 1
-        if (const PairOp *p = i + 1 < last_op ? pl.pair_at(i) : nullptr) {
-            hipError_t e = launch_pair(ctx, *p, (hipStream_t)stream);
+        hipError_t e = hipSuccess;
+        switch (act[(size_t)i]) {
+        case PA_SKIP: break;                          // (ran within the pair)
+        case PA_PAIR:
+            e = launch_pair(ctx, pl.pairs[(size_t)(std::lower_bound(pl.firsts.begin(), pl.firsts.end(), i) - pl.firsts.begin())], (hipStream_t)stream);
             if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, "pair launch " + std::to_string(i) + ": " + hipGetErrorString(e));
-            ++i;
-            continue;
+            break;
+        default:                                      // PA_PLAIN, PA_LONE_FIRST, PA_LONE_SECOND
+            e = launch_op(ctx, i, (hipStream_t)stream, wp, true);
+            if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, "conv launch " + std::to_string(i) + ": " + hipGetErrorString(e));
         }
-        hipError_t e = launch_op(ctx, i, (hipStream_t)stream, wp, true);
-        if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, "conv launch " + std::to_string(i) + ": " + hipGetErrorString(e));
     }
     return BUGSEG_OK;
 }
@@ -2610,21 +2623,12 @@ int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_
     if (!ctx || !dst_dev) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     const Plan &pl = ctx->plan;
     if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
-    const BneckLaunch *b = op >= 0 && op < (int)pl.ops.size() ? pl.ops[(size_t)op].bneck() : nullptr;
+    // where a forward leaves it (Op::fwd): the other activation buffer after an odd number of pairs; a pair's first
+    // block in the spare buffer (written only when the pair was cut), its second where the pair writes
+    const BneckLaunch *b = op >= 0 && op < (int)pl.ops.size() ? std::get_if<BneckLaunch>(&pl.ops[(size_t)op].fwd) : nullptr;
     if (!b || bytes != b->a.x_bytes) return fail(ctx, BUGSEG_EINVAL, "not a fused bottleneck launch, or not its output's size");
     DeviceGuard g(ctx->device);
-    // where a forward leaves it (launch_op's overlay): the other activation buffer after an odd number of pairs; a
-    // pair's first block in the spare buffer (written only when the pair was cut), its second where the pair writes
-    const void *src = b->a.out;
-    if (!pl.pairs.empty()) {
-        auto at = [&](const void *p) -> const void * {
-            if (!pl.flip[(size_t)op]) return p;
-            return p == pl.X[0] ? pl.X[1] : p == pl.X[1] ? pl.X[0] : p;
-        };
-        const int role = pl.pair_role(op);
-        src = role == 1 ? (const void *)pl.spare : role == 2 ? at(b->a.x) : at(b->a.out);
-    }
-    hipError_t e = hipMemcpyAsync(dst_dev, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    hipError_t e = hipMemcpyAsync(dst_dev, b->a.out, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("read block output: ") + hipGetErrorString(e));
     return BUGSEG_OK;
 }
@@ -2649,8 +2653,8 @@ int bugseg_debug_pair_plan(bugseg_ctx *ctx, int32_t *rows, int cap) {
     size_t lds;
     bneck_pair_shape(th, tw, threads, lds);
     for (int k = 0; k < (int)pl.pairs.size() && k < cap; ++k) {
-        const BneckArgs &a = pl.pairs[(size_t)k].args.a;
-        const int32_t v[8] = {pl.pairs[(size_t)k].first, th, tw, a.tiles_y, a.tiles_x, threads, (int32_t)lds, pl.flip[(size_t)pl.pairs[(size_t)k].first]};
+        const PairOp &p = pl.pairs[(size_t)k];
+        const int32_t v[8] = {p.first, th, tw, p.args.a.tiles_y, p.args.a.tiles_x, threads, (int32_t)lds, p.flip};
         std::memcpy(rows + 8 * k, v, sizeof(v));
     }
     return (int)pl.pairs.size();

@@ -2,7 +2,8 @@
 // ASan + UBSan on the host code only (tests/asan/build.sh) and run by tests/test_asan_runtime.py on the
 // CPU. It feeds the BSG1 weight-blob parser + BN folding + packer (bugseg_debug_parse_pack = what
 // bugseg_load_weights does before the upload), the DeepLab plan validator (bugseg_dl_debug_check_plan
-// = bugseg_dl_set_plan before the allocation), the polar-table builder and the knob reader (the environment,
+// = bugseg_dl_set_plan before the allocation), the polar-table builder, the pair overlay's walk
+// (bugseg_debug_pair_walk) and the knob reader (the environment,
 // set in-process: bugseg_debug_knobs / bugseg_dl_debug_knobs with no context) with valid inputs, every
 // truncation of the blob's head and a sample of the rest, and seeded corruptions. Any out-of-bounds
 // access, use-after-free or undefined behaviour aborts the process (exit status != 0); a rejected input
@@ -165,6 +166,44 @@ int main(int argc, char **argv) {
             if (bugseg_debug_fused_forms(buf.data(), rows) != n) { std::fprintf(stderr, "fused forms: %d rows\n", rows); return 1; }
         }
         tally(BUGSEG_OK);
+    }
+
+    // ---- the pair overlay's walk (bugseg_debug_pair_walk: the two functions a forward runs): seeded plans of 0 .. 64
+    // ops — mostly ping-pong chains on one grid, so pairs form up to the last op, with candidates, grids and buffer
+    // indices (-1 too) knocked out at random — over the whole plan and, for every fourth plan, over every cut; the
+    // rows go into a heap buffer of exactly 2 n ints
+    for (int it = 0; it < 200; ++it) {
+        const int n = it < 65 ? it : (int)rng.below(65);
+        std::vector<int32_t> cand((size_t)5 * n);
+        for (int k = 0; k < n; ++k) {
+            const int32_t c[5] = {rng.below(8) != 0, 18 + (int32_t)(rng.below(16) == 0), 26, rng.below(8) ? k & 1 : (int32_t)rng.below(3) - 1,
+                                  rng.below(8) ? (k & 1) ^ 1 : (int32_t)rng.below(3) - 1};
+            std::memcpy(&cand[(size_t)5 * k], c, sizeof(c));
+        }
+        for (int f = 0; f <= n; ++f)
+            for (int l = f; l <= n; ++l) {
+                if (it % 4 && (f != 0 || l != n)) continue;
+                std::vector<int32_t> out((size_t)2 * n);
+                const int m = bugseg_debug_pair_walk(n, n ? cand.data() : nullptr, f, l, n ? out.data() : nullptr);
+                int firsts = 0;
+                bool ok = m >= 0;
+                for (int k = 0; ok && k < n; ++k) {
+                    const int a = out[(size_t)2 * k], nx = k + 1 < n ? out[(size_t)2 * k + 2] : -1;
+                    firsts += a == 1 || a == 3;
+                    ok = a >= 0 && a <= 4 && (out[(size_t)2 * k + 1] | 1) == 1 && (a != 1 || (nx == 2 && f <= k && k + 1 < l)) &&
+                         (a != 3 || (nx == 4 && !(f <= k && k + 1 < l)));
+                }
+                if (!ok || firsts != m) { std::fprintf(stderr, "pair walk: plan %d, ops [%d, %d): %d pairs\n", it, f, l, m); return 1; }
+                tally(BUGSEG_OK);
+            }
+    }
+    {
+        int32_t c[10] = {1, 18, 26, 0, 1, 1, 18, 26, 1, 0}, o[4];
+        const int bad[][3] = {{-1, 0, 0}, {4097, 0, 0}, {2, -1, 2}, {2, 2, 1}, {2, 0, 3}};
+        bool refused = bugseg_debug_pair_walk(2, nullptr, 0, 2, o) == BUGSEG_EINVAL && bugseg_debug_pair_walk(2, c, 0, 2, nullptr) == BUGSEG_EINVAL;
+        for (const auto &b : bad) refused = refused && bugseg_debug_pair_walk(b[0], c, b[1], b[2], o) == BUGSEG_EINVAL;
+        if (!refused || bugseg_debug_pair_walk(2, c, 0, 2, o) != 1) { std::fprintf(stderr, "pair walk: argument shapes\n"); return 1; }
+        rejected += 7;
     }
 
     std::printf("asan driver ok: %ld inputs accepted, %ld rejected\n", accepted, rejected);

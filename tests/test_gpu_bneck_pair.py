@@ -7,6 +7,7 @@ plans without it, bit for bit.
   tiles; both tile orders. With the arena poisoned the spare buffer stays poison: the pair ran, and neither its
   fallbacks nor a cut pair's plain launches did.
 * a forward cut into two calls anywhere in stage 1 — between the ops of a pair too — equals the whole forward.
+* the plan's own launches, one by one (launch_op: what the per-kernel tables time), compute the paired forward's logits.
 * where the pair's speculation on the range exponents fails (weights scaled out of the f16 window in one block of
   a pair, the undamped draw) the guarded fallbacks redo the pair: the logits equal those of the fused plan without
   pairs, and the undamped ones pass the range bar."""
@@ -102,6 +103,33 @@ def test_a_forward_cut_in_two_calls_equals_the_whole(gpu, blocks, cut):
     _logits(ctx, bgr, cut, -1, out)
     torch.cuda.synchronize()
     assert torch.equal(out, whole)
+
+
+def test_the_plan_without_the_overlay_computes_the_forward(gpu, blocks):
+    """What DESIGN 6.23 promises of the plan's own launches (plan_op, launch_op, the per-kernel table): issued one by
+    one over a poisoned arena they compute the paired forward's logits, bit for bit, and leave the overlay alone. The
+    pair's output tensor is one place, however the forward that wrote it was cut."""
+    B, H, W = 2, 72, 104
+    ctx = ENET(weights=blocks, precision="fp32").ctx
+    bgr = _bgr(B, H, W)
+    want = _logits(ctx, bgr).clone()
+    whole = torch.empty((B, H // 4, W // 4, 64 * 4), dtype=torch.uint8, device=gpu)
+    ctx.read_block_output(3, whole)
+    ctx.poison_arena(POISON)
+    out = _logits(ctx, bgr)                                  # the binding the single launches run under
+    out.zero_()
+    for i in range(ctx.plan_info(B, H, W, N.OUT_LOGITS_F32, bgr_input=True)[0]):
+        ctx.launch_op(B, H, W, i)
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)
+    assert [p[0] for p in ctx.pair_plan()] == [2, 4]
+    ctx.poison_arena(POISON)
+    _logits(ctx, bgr, 0, 3, out)                             # the first pair cut between its blocks
+    _logits(ctx, bgr, 3, -1, out)
+    cut = torch.empty_like(whole)
+    ctx.read_block_output(3, cut)
+    torch.cuda.synchronize()
+    assert torch.equal(cut, whole) and torch.equal(out, want)
 
 
 def _scaled(name, unit, factor):
