@@ -48,13 +48,18 @@ def _stale(target: Path, deps) -> bool:
 
 
 def build_native(force: bool = False, verbose: bool = False, stamps: bool = False, variant: str = "",
-                 defines=()) -> Path:
+                 defines=(), only=()) -> Path:
     """stamps=True: the debug variant libbugseg_stamps.so (-DBUGSEG_STAMPS: in-kernel phase clocks,
     scripts/stamp_probe.py); variant="name" with defines=("-DX=1", ...): an A/B build
     libbugseg_<name>.so (loaded through BUGSEG_LIB by measurement scripts). Neither is loaded by the
-    product path."""
+    product path. only=("x.hip", ...): the defines reach these sources alone, so the variant compiles
+    them and links the default build's objects (built first where stale) for every other source."""
     if stamps:
         variant, defines = "stamps", ("-DBUGSEG_STAMPS", *defines)
+    if not variant:
+        only = ()
+    if only:
+        build_native(verbose=verbose)
     obj_dir = OBJ / variant if variant else OBJ
     lib = PKG / f"libbugseg_{variant}.so" if variant else LIB
     obj_dir.mkdir(parents=True, exist_ok=True)
@@ -63,6 +68,8 @@ def build_native(force: bool = False, verbose: bool = False, stamps: bool = Fals
              f"-I{ROOT / 'include'}", f"-I{CSRC}", *defines]
     jobs = []
     for s in SOURCES:
+        if only and s not in only:
+            continue
         src = CSRC / s
         obj = obj_dir / (s + ".o")
         if force or _stale(obj, [src, *HEADERS]):
@@ -80,7 +87,7 @@ def build_native(force: bool = False, verbose: bool = False, stamps: bool = Fals
 
     with ThreadPoolExecutor(max_workers=min(4, max(1, len(jobs)))) as ex:
         list(ex.map(run, jobs))
-    objs = [obj_dir / (s + ".o") for s in SOURCES]
+    objs = [(obj_dir if not only or s in only else OBJ) / (s + ".o") for s in SOURCES]
     if force or jobs or _stale(lib, objs):
         tmp = lib.with_suffix(".so.tmp")
         cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(tmp), *map(str, objs)]
@@ -93,5 +100,6 @@ def build_native(force: bool = False, verbose: bool = False, stamps: bool = Fals
 
 if __name__ == "__main__":
     var = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--variant=")), "")
+    only = next((tuple(a.split("=", 1)[1].split(",")) for a in sys.argv if a.startswith("--only=")), ())
     print(build_native(force="--force" in sys.argv, verbose=True, stamps="--stamps" in sys.argv, variant=var,
-                       defines=tuple(a for a in sys.argv if a.startswith("-D"))))
+                       defines=tuple(a for a in sys.argv if a.startswith("-D")), only=only))

@@ -13,6 +13,9 @@
 // with bneck_kernel's products in bneck_kernel's order: the split-f16 MFMAs of mfma_common.h, the HL weight
 // layout, t0 as hi / lo planes (bneck_kernels.hip PL), bias-initialised accumulators, PReLU as max(v, s v).
 // y in LDS holds the bits the unpaired launch stores to HBM, so out is bit-identical to the two launches'.
+// The tile's memory traffic runs beside its compute: A1 leaves the raw x of tile +- 1 in the y region, dead until
+// A3, which takes its residual from there (BNECK_PAIR_XLDS), and the next tile's x is loaded into registers while
+// A2 .. B3 of this one run (BNECK_PAIR_PREF), so B2 + B3's stores are the only global traffic a tile waits behind.
 //
 // Range scaling. The unpaired second launch derives its exponents from the MEASURED max |y|, which does not
 // exist inside one launch, and no rigorous bound replaces it: the row-sum bound of y is ~800 x its measured
@@ -48,6 +51,27 @@ constexpr int PZP = 8;                                                      // z
 #endif
 constexpr int PYS = BNECK_PAIR_YSTR;
 static_assert(PYS >= PC && PYS % 4 == 0, "a y pixel is 64 floats, 16-B aligned");
+// The residual x of block A over tile +- 1: 1 = A1 leaves the raw x it loaded in the (then dead) y region and A3
+// reads it where it writes y; 0 = A3 re-reads it from global memory (L2)
+#ifndef BNECK_PAIR_XLDS
+#define BNECK_PAIR_XLDS 1
+#endif
+// The next tile's x in flight during the current tile: the first BNECK_PAIR_PREF fragments of every wave (0 = none,
+// 1 = each wave's first, 2 = all) are loaded BNECK_PAIR_PREFAT (0 = before B2 + B3, 1 = before B1, 2 = before
+// A2 + A3, which touch no global memory under XLDS) and held in registers across the loop-end barrier; the rest
+// in A1 as before, behind the first fragment's projection. The defaults by measurement
+#ifndef BNECK_PAIR_PREF
+#define BNECK_PAIR_PREF 1
+#endif
+#ifndef BNECK_PAIR_PREFAT
+#define BNECK_PAIR_PREFAT 2
+#endif
+// Debug build only (-DBUGSEG_STAMPS, scripts/pair_stamp_probe.py): bneck_kernels.hip's phase clocks, here
+// 0 tile top, 1 A1's loads landed, 2 A1 end, 3 A2 + A3 end, 4 B1 end, 5 B2 + B3 end (each behind its barrier)
+#ifndef STAMP
+#define STAMP(k) do {} while (0)
+#define STAMP_WG() do {} while (0)
+#endif
 
 // The LDS map (floats): both blocks' weights and constants, the zero pad, y over tile +- 1, then the t0 region:
 // t0_A over tile +- 2 as a hi and a lo plane of 8 dwords per pixel, later t0_B over tile +- 1 in the same bytes
@@ -194,49 +218,86 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
     };
 
     const int wword = tile_walk_mirror(grp, CH, a.ntiles, a.rev);
-    for (int it = slot; it < CH; it += nslots) {
-        int tile = grp * CH + it;
-        if (tile >= a.ntiles) break;
-        tile = tile_walk_flip(wword, tile);
+    // the workgroup's tile of iteration it, or -1 past its last
+    auto tile_at = [&](int it) -> int {
+        const int tile = grp * CH + it;
+        return it < CH && tile < a.ntiles ? tile_walk_flip(wword, tile) : -1;
+    };
+    // a tile's origin (oy0, ox0) and its frame's byte offset
+    auto origin = [&](int tile, int &oy0, int &ox0, uint32_t &xn) {
         const int txi = tile % a.tiles_x, t2 = tile / a.tiles_x;
         const int tyi = t2 % a.tiles_y, n = t2 / a.tiles_y;
-        const int oy0 = a.oy_base + tyi * TH, ox0 = txi * TW;
-        const uint32_t xn = (uint32_t)(n * a.H * a.W) * (uint32_t)(PC * 4);   // frame byte offset
-        // byte offset of channel 0 of image pixel (y, x), or OOB outside the image
-        auto pix = [&](int y, int x) -> uint32_t {
-            uint32_t v = xn + (__umul24((uint32_t)y, (uint32_t)a.W) + (uint32_t)x) * (uint32_t)(PC * 4);
-            asm volatile("" : "+v"(v));
-            return (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W ? v : OOB;
-        };
+        oy0 = a.oy_base + tyi * TH; ox0 = txi * TW;
+        xn = (uint32_t)(n * a.H * a.W) * (uint32_t)(PC * 4);
+    };
+    // byte offset of channel 0 of pixel (y, x) of the frame at xn, or OOB outside the image
+    auto pixn = [&](uint32_t xn, int y, int x) -> uint32_t {
+        uint32_t v = xn + (__umul24((uint32_t)y, (uint32_t)a.W) + (uint32_t)x) * (uint32_t)(PC * 4);
+        asm volatile("" : "+v"(v));
+        return (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W ? v : OOB;
+    };
+    // A1's loads: x of the wave's fragments c0 .. c1 - 1 of t0_A's plane of `tile` (every offset OOB, so zeros and
+    // nothing dereferenced, for tile < 0), lane (col, kq) channels 8 (4 s + kq) .. + 7 of plane pixel 16 f + col
+    constexpr int NPF = BNECK_PAIR_PREF < F::NCA ? BNECK_PAIR_PREF : F::NCA;   // fragments held across the barrier
+    RawF xf[F::NCA][PKS1];
+    uint32_t pof[F::NCA];
+    auto a1_loads = [&](int tile, int c0, int c1) {
+        int oy0 = 0, ox0 = 0;
+        uint32_t xn = 0;
+        if (tile >= 0) origin(tile, oy0, ox0, xn);     // wave-uniform
+#pragma unroll
+        for (int c = 0; c < F::NCA; ++c) {
+            const int f = wave + NW * c;
+            if (c < c0 || c >= c1) continue;
+            if (f >= F::NFA) break;                    // wave-uniform
+            const int h = f * 16 + col, hy = h / HWA, hx = h - hy * HWA;
+            pof[c] = h < HRA && tile >= 0 ? pixn(xn, oy0 - 2 + hy, ox0 - 2 + hx) : OOB;
+#pragma unroll
+            for (int s = 0; s < PKS1; ++s) bld8(xf[c][s], rxb, pof[c] == OOB ? OOB : pof[c] + (uint32_t)((s * 4 + kq) * 32));
+        }
+    };
+    if (NPF) a1_loads(tile_at(slot), 0, NPF);
+    for (int it = slot; it < CH; it += nslots) {
+        const int tile = tile_at(it);
+        if (tile < 0) break;
+        int oy0, ox0;
+        uint32_t xn;
+        origin(tile, oy0, ox0, xn);
+        auto pix = [&](int y, int x) -> uint32_t { return pixn(xn, y, x); };
         const float *w1, *w2, *w3, *cb1;
+        STAMP(0); STAMP_WG();
 
-        // ---- A1: t0_A over tile +- 2. Every load of the wave's fragments is issued before the first MFMA
+        // ---- A1: t0_A over tile +- 2. Every load of the wave's fragments is issued before the first MFMA (the
+        // first NPF of them by the previous tile). XLDS: the raw x of tile +- 1 goes to the y region as loaded
         blk(0, w1, w2, w3, cb1);
-        {
-            RawF xf[F::NCA][PKS1];
-            uint32_t po[F::NCA];
+        a1_loads(tile, NPF, F::NCA);
+#ifdef BUGSEG_STAMPS
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        STAMP(1);
+#endif
 #pragma unroll
-            for (int c = 0; c < F::NCA; ++c) {
-                const int f = wave + NW * c;
-                if (f >= F::NFA) break;               // wave-uniform
-                const int h = f * 16 + col, hy = h / HWA, hx = h - hy * HWA;
-                po[c] = h < HRA ? pix(oy0 - 2 + hy, ox0 - 2 + hx) : OOB;
+        for (int c = 0; c < F::NCA; ++c) {
+            const int f = wave + NW * c;
+            if (f >= F::NFA) break;
+            const int h = f * 16 + col;
+            if (BNECK_PAIR_XLDS) {
+                const int hy = h / HWA, hx = h - hy * HWA;
+                if (hy >= 1 && hy <= TH + 2 && hx >= 1 && hx <= TW + 2) {   // inside tile +- 1 (h < HRA follows)
+                    float *xq = ys + ((hy - 1) * HWB + hx - 1) * PYS + kq * 8;
 #pragma unroll
-                for (int s = 0; s < PKS1; ++s) bld8(xf[c][s], rxb, po[c] == OOB ? OOB : po[c] + (uint32_t)((s * 4 + kq) * 32));
+                    for (int s = 0; s < PKS1; ++s) { st4(xq + s * 32, xf[c][s].a); st4(xq + s * 32 + 4, xf[c][s].b); }
+                }
             }
-#pragma unroll
-            for (int c = 0; c < F::NCA; ++c) {
-                const int f = wave + NW * c;
-                if (f >= F::NFA) break;
-                const int h = f * 16 + col;
-                float4 v = project(w1, cb1, xf[c]);
-                if (po[c] == OOB) v = zero4;
-                if (h < HRA) st4pl(t0, F::PLOA, h, kq * 4, v);
-            }
+            float4 v = project(w1, cb1, xf[c]);
+            if (pof[c] == OOB) v = zero4;
+            if (h < HRA) st4pl(t0, F::PLOA, h, kq * 4, v);
         }
         __syncthreads();
+        STAMP(2);
+        if (NPF && BNECK_PAIR_PREFAT == 2) a1_loads(tile_at(it + nslots), 0, NPF);
 
-        // ---- A2 + A3: y over tile +- 1 into LDS, 0 outside the image; the residual x re-read (L2)
+        // ---- A2 + A3: y over tile +- 1 into LDS, 0 outside the image; the residual x from the y region
+        // (XLDS) or re-read (L2)
 #pragma unroll
         for (int c = 0; c < F::NCB; ++c) {
             const int f = wave + NW * c;
@@ -244,9 +305,13 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
             const int q = f * 16 + col, qq = q < HRB ? q : 0;
             const int ry = qq / HWB, rx = qq - ry * HWB;
             const uint32_t po = q < HRB ? pix(oy0 - 1 + ry, ox0 - 1 + rx) : OOB;
+            // XLDS: the lane reads its four residual values where it then writes y (a lane past the plane reads
+            // pixel 0's and drops the result)
             uint4 res[PNR3];
 #pragma unroll
-            for (int r = 0; r < PNR3; ++r) res[r] = bld16(rxb, po == OOB ? OOB : po + (uint32_t)((r * 16 + kq * 4) * 4));
+            for (int r = 0; r < PNR3; ++r)
+                res[r] = BNECK_PAIR_XLDS ? __builtin_bit_cast(uint4, ld4(ys + qq * PYS + r * 16 + kq * 4))
+                                         : bld16(rxb, po == OOB ? OOB : po + (uint32_t)((r * 16 + kq * 4) * 4));
             RawF tf;
             middle(w2, cb1 + 32, ry * HWA + rx, HWA, F::PLOA, tf);
 #pragma unroll
@@ -258,9 +323,11 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
             }
         }
         __syncthreads();
+        STAMP(3);
 
         // ---- B1: t0_B over tile +- 1 from y, into the t0 region (t0_A is dead)
         blk(1, w1, w2, w3, cb1);
+        if (NPF && BNECK_PAIR_PREFAT == 1) a1_loads(tile_at(it + nslots), 0, NPF);
 #pragma unroll
         for (int c = 0; c < F::NCB; ++c) {
             const int f = wave + NW * c;
@@ -276,6 +343,8 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
             if (q < HRB) st4pl(t0, F::PLOB, q, kq * 4, v);
         }
         __syncthreads();
+        STAMP(4);
+        if (NPF && BNECK_PAIR_PREFAT == 0) a1_loads(tile_at(it + nslots), 0, NPF);
 
         // ---- B2 + B3: the tile's rows, residual y from LDS, whole-line stores (bneck_kernels.hip LINES): rows
         // 2u / 2u + 1 of pixels col and col ^ 8 traded across lanes 8 apart, then line u of each pixel
@@ -311,6 +380,7 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
             }
         }
         __syncthreads();                              // the next tile writes t0 and y
+        STAMP(5);
     }
     rng_commit_wg(amy, a.rg.amax_out, t0, NW);
     rng_commit_wg(amo, b.rg.amax_out, t0, NW);
