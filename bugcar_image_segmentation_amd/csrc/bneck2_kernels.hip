@@ -57,17 +57,9 @@ constexpr int P2_ZP = 32;
 constexpr int P2_TSF = P2_HR * P2_PSTR;                      // floats per t0 buffer
 constexpr size_t P2_LDS = (size_t)(P2_W1 + P2_W2 + P2_W3 + P2_CONSTS + P2_ZP + 2 * P2_TSF) * 4;
 static_assert(P2_LDS <= 160 * 1024, "two t0 buffers and one weight copy in 160 KB");
+constexpr int P2_CH1 = 2;                                    // phase-1 fragments whose x loads fly together (VGPRs: 32 each)
+constexpr int P2_U2 = 1;                                     // middle-conv k-steps unrolled together
 }  // namespace
-
-#ifndef BNECK2_CH1
-#define BNECK2_CH1 2      // phase-1 fragments whose x loads fly together (VGPRs: 32 each)
-#endif
-#ifndef BNECK2_U2
-#define BNECK2_U2 1       // middle-conv k-steps unrolled together
-#endif
-#ifndef BNECK2_FENCE1
-#define BNECK2_FENCE1 1   // phase 1: no weight read hoisted across k-steps (hoisted, they need 64 VGPRs)
-#endif
 
 template <bool SCL>
 __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, float *smem) {
@@ -145,12 +137,12 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
         const uint32_t xn = (uint32_t)(n * a.H * a.W) * (uint32_t)(P2_C * 4);
         constexpr int NFW = (P2_NF1 + P2_NWH - 1) / P2_NWH;     // 3: halo fragments per wave (at most)
 #pragma unroll
-        for (int c0 = 0; c0 < NFW; c0 += BNECK2_CH1) {
-            RawF xf[BNECK2_CH1][P2_KS1];
-            bool okc[BNECK2_CH1];
-            int hc[BNECK2_CH1];
+        for (int c0 = 0; c0 < NFW; c0 += P2_CH1) {
+            RawF xf[P2_CH1][P2_KS1];
+            bool okc[P2_CH1];
+            int hc[P2_CH1];
 #pragma unroll
-            for (int c = 0; c < BNECK2_CH1; ++c) {
+            for (int c = 0; c < P2_CH1; ++c) {
                 const int fh = hw + P2_NWH * (c0 + c);
                 if (c0 + c >= NFW || fh >= P2_NF1) break;            // wave-uniform
                 const int h = fh * 16 + col;
@@ -163,7 +155,7 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
                     bld8(xf[c][s], rxb, okc[c] ? xn + ((__umul24((uint32_t)iy, (uint32_t)a.W) + (uint32_t)ix) * P2_C + (s * 4 + kq) * 8) * 4u : OOB);
             }
 #pragma unroll
-            for (int c = 0; c < BNECK2_CH1; ++c) {
+            for (int c = 0; c < P2_CH1; ++c) {
                 if (c0 + c >= NFW || hw + P2_NWH * (c0 + c) >= P2_NF1) break;   // wave-uniform
                 f32x4 acc[P2_NR1];
 #pragma unroll
@@ -182,7 +174,7 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
                         ldw(wf, w1 + (r * 16 + col) * P2_K1S + s * 32, kq);
                         mma(acc[r], wf, xq);
                     }
-                    if (BNECK2_FENCE1) asm volatile("" ::: "memory");   // keeps the next k-step's weight reads here
+                    asm volatile("" ::: "memory");   // keeps the next k-step's weight reads here (hoisted, they need 64 VGPRs)
                 }
                 if constexpr (SCL) {
 #pragma unroll
@@ -240,7 +232,7 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
                 acc[r] = bias4(cb2 + r * 16 + kq * 4);
                 if constexpr (SCL) acc[r] = mul4(acc[r], b2m);
             }
-#pragma unroll BNECK2_U2
+#pragma unroll P2_U2
             for (int s = 0; s < P2_KS2; ++s) {
                 const int ky = s / 3, kx = s - ky * 3;
                 RawS wf[P2_NR1];
@@ -253,7 +245,7 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
                 xf.l = *reinterpret_cast<const uint4 *>(ts + tso(h, 4 + kq));
 #pragma unroll
                 for (int r = 0; r < P2_NR1; ++r) mma(acc[r], wf[r], xf);
-                if (BNECK2_FENCE1) asm volatile("" ::: "memory");
+                asm volatile("" ::: "memory");
             }
             if constexpr (SCL) {
 #pragma unroll
@@ -291,7 +283,7 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
                 const uint32_t cb = (uint32_t)(u * 32 + (lo8 ? 0 : 16) + kq * 4) * 4u;
                 bst16o<16>(rob, pa == OOB ? OOB : pa + cb, lo8 ? u0 : ys);
                 bst16o<16>(rob, pb == OOB ? OOB : pb + cb, lo8 ? ys : u1);
-                if (BNECK2_FENCE1) asm volatile("" ::: "memory");   // the next row pair's weight reads stay here
+                asm volatile("" ::: "memory");   // the next row pair's weight reads stay here
             }
         }
     };
@@ -304,11 +296,8 @@ __device__ __forceinline__ void bneck2_body(const BneckArgs &a, float rlane, flo
             const int i = kk >> 1;
             if (i < nmy) {
                 const int tile = tile_walk(grp, hs + i * nhs, CH, a.ntiles, a.rev);   // (i < nmy: inside the run)
-#ifndef BNECK2_SKIP
-#define BNECK2_SKIP 0
-#endif
-                if ((kk & 1) == 0) { if (BNECK2_SKIP != 1) phase1(tile); }
-                else { if (BNECK2_SKIP != 2) phase23(tile); }
+                if ((kk & 1) == 0) phase1(tile);
+                else phase23(tile);
             }
         }
         __syncthreads();

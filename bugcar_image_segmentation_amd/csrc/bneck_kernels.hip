@@ -37,13 +37,6 @@
 #include <vector>
 
 #include "bugseg_internal.h"
-// output stores: the per-kernel cache-policy choice (OUT_AUX_SEL: sc1 write-through for C >= 64).
-// Round 2, after the kept residual and the LDS-DMA staging: 4-9% faster per launch (C128 20x16
-// 23.3 -> 21.3 us, C64 35.1 -> 34.0 us, forward 0.80 -> 0.77 ms one stream at a time) and equal in
-// the 2-stream bench (round 1 had measured it 2.4% slower there)
-#ifndef BUGSEG_OUT_AUX
-#define BUGSEG_OUT_AUX -1
-#endif
 #include "cls_common.h"
 
 namespace bugseg {
@@ -75,9 +68,13 @@ __device__ __forceinline__ void vm_wait_upto(int n) {
 }
 
 // Tile shape variants per channel count: TH x TW tile pixels, NW waves per workgroup, OCC = waves
-// per SIMD the bf16 build is held to (registers), matching what LDS allows. 128 channels: the LDS
+// per SIMD the 2-byte build is held to (registers), matching what LDS allows. 128 channels: the LDS
 // footprint (weights + halo or output staging, ~75 KB) allows two workgroups per CU, so they are
 // 8-wave; 64 / 16 channels (~28-33 KB): four 4-wave workgroups per CU.
+// OCCF = the same for the fp32 (parity mode) build: 1 = registers unconstrained (LDS bounds the C = 64 / 128
+// forms first; with split-f16 products they are issue / latency bound at 2-3 waves per SIMD), except C = 16
+// (at 5 it spilled 32 B with the split t0: 102.0 vs 90.8 us per launch at 4) and the 8 x 16 C = 64 form
+// (127 VGPRs, no spills at 4: 139.8 -> 137.9 us per launch; unconstrained 154 VGPRs, 3 waves per SIMD)
 template <int C, int V> struct BShape;
 // RP = residual fragments each wave prefetches before the middle conv (a ring refilled in phase 3
 // when a wave has more fragments than that: an L2 round trip then sits on the phase-3 path).
@@ -86,22 +83,22 @@ template <int C, int V> struct BShape;
 // are the tile's one-row halo and its horizontal taps stay inside the tile — masked at the image
 // edge, no horizontal halo stored. 4 x 80 tiles cover 60 x 80 at d = 8 and d = 16 in 16 tiles per
 // frame (the phase sub-images, 8 x 10 and 4 x 5, are far too small for square tiles).
-template <> struct BShape<128, 0> { static constexpr int TH = 16, TW = 16, NW = 8, OCC = 4, RP = 2, RD = 0, WIDE = 1; };
-template <> struct BShape<128, 1> { static constexpr int TH = 20, TW = 16, NW = 8, OCC = 4, RP = 2, RD = 0, WIDE = 1; };
-template <> struct BShape<128, 2> { static constexpr int TH = 4, TW = 80, NW = 8, OCC = 4, RP = 2, RD = 1, WIDE = 0; };
-template <> struct BShape<128, 3> { static constexpr int TH = 4, TW = 64, NW = 8, OCC = 4, RP = 2, RD = 1, WIDE = 1; };
+template <> struct BShape<128, 0> { static constexpr int TH = 16, TW = 16, NW = 8, OCC = 4, OCCF = 1, RP = 2, RD = 0, WIDE = 1; };
+template <> struct BShape<128, 1> { static constexpr int TH = 20, TW = 16, NW = 8, OCC = 4, OCCF = 1, RP = 2, RD = 0, WIDE = 1; };
+template <> struct BShape<128, 2> { static constexpr int TH = 4, TW = 80, NW = 8, OCC = 4, OCCF = 1, RP = 2, RD = 1, WIDE = 0; };
+template <> struct BShape<128, 3> { static constexpr int TH = 4, TW = 64, NW = 8, OCC = 4, OCCF = 1, RP = 2, RD = 1, WIDE = 1; };
 // 8 x 16: the small-batch forms (batch 1: 40 C128 tiles at 60 x 80 instead of 15; 150 C64 tiles at
 // 120 x 160 instead of 80), picked by the runtime's round model only when whole rounds are few
-template <> struct BShape<128, 4> { static constexpr int TH = 8, TW = 16, NW = 8, OCC = 4, RP = 1, RD = 0, WIDE = 1; };
-template <> struct BShape<64, 0> { static constexpr int TH = 16, TW = 16, NW = 4, OCC = 5, RP = 4, RD = 0, WIDE = 1; };
-template <> struct BShape<64, 2> { static constexpr int TH = 8, TW = 16, NW = 4, OCC = 5, RP = 2, RD = 0, WIDE = 1; };
-template <> struct BShape<64, 1> { static constexpr int TH = 20, TW = 16, NW = 4, OCC = 5, RP = 3, RD = 0, WIDE = 1; };
-template <> struct BShape<16, 0> { static constexpr int TH = 16, TW = 16, NW = 4, OCC = 6, RP = 4, RD = 0, WIDE = 1; };
+template <> struct BShape<128, 4> { static constexpr int TH = 8, TW = 16, NW = 8, OCC = 4, OCCF = 1, RP = 1, RD = 0, WIDE = 1; };
+template <> struct BShape<64, 0> { static constexpr int TH = 16, TW = 16, NW = 4, OCC = 5, OCCF = 1, RP = 4, RD = 0, WIDE = 1; };
+template <> struct BShape<64, 2> { static constexpr int TH = 8, TW = 16, NW = 4, OCC = 5, OCCF = 4, RP = 2, RD = 0, WIDE = 1; };
+template <> struct BShape<64, 1> { static constexpr int TH = 20, TW = 16, NW = 4, OCC = 5, OCCF = 1, RP = 3, RD = 0, WIDE = 1; };
+template <> struct BShape<16, 0> { static constexpr int TH = 16, TW = 16, NW = 4, OCC = 6, OCCF = 4, RP = 4, RD = 0, WIDE = 1; };
 // 20 x 16: 7,680 tiles at 32 frames, 5 whole rounds of the 1,536 resident slots (16 x 16: 9,600 tiles,
 // 6.25 rounds -> 7); the cost model picks it (32 x 16 and 16 x 32 tiles measured slower in round 3:
 // 56.9 / 56.6 vs 49.4-50.4 us per launch, and were removed). Measured (round 3, fp16, B = 32): 48.0-48.4 vs 48.6-48.8 us
 // per launch — equal within noise: the stage-5 block is not round-quantisation bound
-template <> struct BShape<16, 1> { static constexpr int TH = 20, TW = 16, NW = 4, OCC = 6, RP = 4, RD = 0, WIDE = 1; };
+template <> struct BShape<16, 1> { static constexpr int TH = 20, TW = 16, NW = 4, OCC = 6, OCCF = 4, RP = 4, RD = 0, WIDE = 1; };
 
 // LDS strides (elements). bf16: a 16-lane group of ds_read_b128 (one 16-B k group of 16 pixels or
 // weight rows) is conflict-free when the row stride is 8, 24, 40 or 56 dwords mod 64 (the SQ counters
@@ -112,77 +109,21 @@ template <> struct BShape<16, 1> { static constexpr int TH = 20, TW = 16, NW = 4
 // — 45.8 vs 45.8 us per launch — and slower on C = 64 / 16, 77.0 -> 81.5 / 96.7 -> 108.4 us; round 4)
 // fp32 C = 128 (not the down form): HL, the grouped split layout (see the body) — weight rows and t0 pixels
 // padded to 8 / 40 dwords mod 64, the conflict-free strides for its 16-B-per-lane reads
-#ifndef BNECK_F32_HL
-#define BNECK_F32_HL 1
-#endif
-// fp32 C = 64 (round 6, VERDICT r5 item 7): the weights in the same HL layout (rows 8 / 40 dwords mod 64) and
+// fp32 C = 64 (round 6): the weights in the same HL layout (rows 8 / 40 dwords mod 64) and
 // t0 as two PLANES — every pixel's 16 channels' hi parts (32 B) in one, their lo parts in the other, 8
 // dwords per pixel each, unpadded: the middle conv's 16-lane read groups then hit distinct banks (lanes
 // col and col + 8 of a group read the same bank row but the other 8-channel group) — where the interleaved
 // split layout (hi + lo per group, 20-dword pixels) was 2-way conflicted on every read (SQ: 35% of the
 // C64 forms' LDS cycles), in less LDS (two planes of 8 dwords vs 20 dwords per pixel; the weights' wider
 // pads fit in the difference, so the 8 x 16 form keeps its 4 workgroups per CU)
-#ifndef BNECK_F32_HL64
-#define BNECK_F32_HL64 1
-#endif
-#ifndef BNECK_REG3_C64
-#define BNECK_REG3_C64 0
-#endif
-// fp32 (parity mode) C = 64 with the register epilogue: no staging region, so the LDS footprint is the
-// halo's (8 x 16 tile: 42.7 -> 39.7 KB, 3 -> 4 workgroups per CU); its quads are 16-B chunks already.
-// Measured slower (round 3: 94.1 -> 104.7 us per launch: a pixel's 256 B leave as four 64-B pieces)
-// fp32 C = 64 (non-down) with the register epilogue AND whole-line stores (LINES below; round 6, A/B knob):
-// the residual is loaded in the same line layout and traded back with the same DPP row rotation.
-// Bit-identical (44 fp32 parity cases) but measured slower: 8 x 16 138.8 -> 147.5 us per 64-frame launch
-// (124 VGPRs, no spills; the half-staged LDS epilogue, HSTG, stays)
-#ifndef BNECK_F32_LINES64
-#define BNECK_F32_LINES64 0
-#endif
-#ifndef BNECK_REG3_C64_F32
-#define BNECK_REG3_C64_F32 0
-#endif
-// fp32 C = 64: the staged epilogue one 32-channel half at a time (HSTG below). Measured (round 3, fp32,
-// B = 32): the 8 x 16 form 94.2 -> 89.4 us per launch (3 -> 4 workgroups per CU), fp32 bench
-// 13,890 -> 14,065-14,095 frames/s; bit-identical (GPU-tested)
-#ifndef BNECK_F32_HSTG
-#define BNECK_F32_HSTG 1
-#endif
-#ifndef BNECK_KEEP
-#define BNECK_KEEP 1
-#endif
-// KEEP: the residual is the block input phase 1 already loaded. Phase 1 then walks the tile's
-// interior as phase 3's fragments (a run of one tile row, on the wave that will expand it) and the
-// halo border separately, and each wave keeps its interior fragments' x in registers through
-// phase 2 instead of re-reading them (an L2 / Infinity-Cache round trip per fragment; PMC: the
-// C128 launches fetched 1.67x their compulsory bytes with the re-read). 2-byte storage, symmetric
-// plain blocks, with the staged (C = 64) or the row-pair-swapped (C = 128) epilogue.
-#ifndef BNECK_KEEP_ASYM
-// the asymmetric form keeps its residual too (round 4: with the single-pass 5x1 it spills 3 VGPRs and
-// runs 26.7 vs 26.5 us per launch re-reading, i.e. equal, for ~25 MB less HBM traffic per launch;
-// round 3, before that rewrite, it had spilled more and run 26.2 -> 27.2 us)
-#define BNECK_KEEP_ASYM 1
-#endif
-#ifndef BNECK_KEEP_C64
-// C = 64, 2-byte: the residual kept (16 x 16 and 8 x 16 tiles; the 20 x 16 tile's five fragments per wave
-// exceed the kept-register budget). Round 2 (B = 32, two streams) measured it slower: 41.0 vs 38.0 us per
-// launch. Round 6 (B = 64, one stream): the 20 x 16 form re-reads its residual from HBM (PMC 228 MB read
-// per launch, 1.45x the 157 MB compulsory) while 16 x 16 kept reads 160 MB (1.02x) in 70.9 vs 71.8 us —
-// so it is on, and the tile picker charges the 20 x 16 form for its re-read (bugseg_runtime.cpp)
-#define BNECK_KEEP_C64 1
-#endif
-#ifndef BNECK_KEEP_F32
-#define BNECK_KEEP_F32 1
-#endif
-#ifndef BNECK_KEEP_F32_ASYM
-#define BNECK_KEEP_F32_ASYM 1
-#endif
 
 // One compile-time description per bottleneck form: what the kernel body and the launcher both need — the tile
 // shape, the layout choices and the LDS MAP, the byte offset of every region of the dynamic allocation and its
 // size. bneck_body takes every region pointer from here and the launchers take LDS_BYTES from here (through
 // the form table at the end of this file), so the size a launch asks for and the addresses its kernel writes
-// have one definition, and a -D A/B build of a knob below moves both. TR, SCL and WIN (bneck_body) do not
-// change the layout and are not parameters. CI > 0: the down form; FC >= 0: the class-fused form.
+// have one definition. The layout flags below are statements about forms: the measured alternatives they
+// replaced are listed in DESIGN.md 6.24. TR, SCL and WIN (bneck_body) do not change the layout and are not
+// parameters. CI > 0: the down form; FC >= 0: the class-fused form.
 template <typename T, int C, bool ASYM, int V, int CI = 0, int FC = -1>
 struct BneckForm {
     static constexpr int ES = (int)sizeof(T);
@@ -203,7 +144,7 @@ struct BneckForm {
     static constexpr int NPA = TH * (TW + 4);         // asymmetric: pixels of t1a (the 1x5's halo)
     // strides (see "LDS strides" above)
     static constexpr bool WIDE = BShape<C, V>::WIDE && !ASYM;
-    static constexpr bool HLW = BNECK_F32_HL && ES == 4 && (C == 128 || (C == 64 && BNECK_F32_HL64)) && !DN;   // HL weight rows
+    static constexpr bool HLW = ES == 4 && (C == 128 || C == 64) && !DN;   // HL weight rows
     // HL (fp32 C = 128, round 5): in LDS a 32-element k-step of a split weight row, and a t0 / t1a pixel's
     // 32 channels, hold the four 8-channel groups' hi parts (16 B each) and then their lo parts, instead of
     // hi + lo per group — so each of a lane's two 16-B reads is 4 dwords at 4 kq dwords apart, as in bf16,
@@ -215,7 +156,7 @@ struct BneckForm {
     static_assert(!HL || IS == 32 || (PL && IS == 16), "HL: split t0 of 32 channels (PL: 16)");
     static constexpr int PADW = HLW ? 8 : ES == 2 && (C != 128 || WIDE) ? 16 : 16 / ES;   // weight-row pad (elements)
     static constexpr int PSTR = PL ? 8                                                     // LDS pixel stride (elements; PL: per plane)
-                                : ES != 2 ? (BNECK_F32_HL && IS == 32 ? 40 : IS + 16 / ES) : IS == 32 ? (WIDE ? 48 : 40) : IS;
+                                : ES != 2 ? (IS == 32 ? 40 : IS + 16 / ES) : IS == 32 ? (WIDE ? 48 : 40) : IS;
     static constexpr int K1S = KS1 * 32 + PADW, K2S = KS2 * 32 + PADW, K3S = 32 + PADW;   // weight row strides (elements)
     static constexpr int ZP = HL ? 32 : 16;           // zero-pad elements just below ts (masked-off B fragments read them)
     // phase-3 chunking (see phase 3): bf16 with an even number of 16-row blocks swaps row pairs
@@ -224,21 +165,44 @@ struct BneckForm {
     // pixels would be written as half lines by the register layout, which measured slower there
     // (44.7 vs 43.0 us per launch with t1 in registers).
     // (the down form's C = 64 launch measured faster with the register epilogue: 53 vs 55 us)
-    static constexpr bool REG3 = C != 64 || DN || BNECK_REG3_C64 || (ES == 4 && (BNECK_REG3_C64_F32 || BNECK_F32_LINES64));
+    static constexpr bool REG3 = C != 64 || DN;
     static constexpr bool SWAP = REG3 && ES == 2 && NR3 % 2 == 0;
     static constexpr int EPC = 16 / ES;               // elements per 16-B chunk
     // HSTG (fp32 C = 64, staged epilogue): the fragment is staged one 32-channel half at a time — a
     // pixel's half is 128 B, one whole line, so the stores stay full-line while the staging region
     // halves (the 8 x 16 tile: 42.7 -> 39.7 KB of LDS, 3 -> 4 workgroups per CU)
-    static constexpr bool HSTG = !REG3 && ES == 4 && C == 64 && BNECK_F32_HSTG;
+    static constexpr bool HSTG = !REG3 && ES == 4;
     static constexpr int OSTR = (HSTG ? C / 2 : C) + EPC;    // staged epilogue: row stride (16-B padded)
     // KEEPF (round 4): the fp32 C = 128 forms keep their residual too. One workgroup per CU (LDS), so
     // 256 VGPRs per lane: the 96 of the kept x replace the 64 of the residual ring. A lane's k-step s
     // chunk holds channels 32 s + 8 kq .. + 7 as two quads; phase 3 wants quad 16 r + 4 kq .. + 3 of
     // row block r: a row swap then a half swap per dword gather rows 2 s and 2 s + 1 (as in bf16)
-    static constexpr bool KEEPF = BNECK_KEEP_F32 && !DN && ES == 4 && (!ASYM || BNECK_KEEP_F32_ASYM) && C == 128 && REG3 && !SWAP;
-    static constexpr bool KEEP = (BNECK_KEEP && !DN && ES == 2 && (!ASYM || BNECK_KEEP_ASYM) && (SWAP || !REG3) && (C != 64 || BNECK_KEEP_C64) &&
-                                  NF2 * KS1 * 4 <= (C == 128 ? 48 : 32)) || KEEPF;   // kept VGPRs within the occupancy budget
+    static constexpr bool KEEPF = !DN && ES == 4 && C == 128;
+    // KEEP: the residual is the block input phase 1 already loaded. Phase 1 then walks the tile's
+    // interior as phase 3's fragments (a run of one tile row, on the wave that will expand it) and the
+    // halo border separately, and each wave keeps its interior fragments' x in registers through
+    // phase 2 instead of re-reading them (an L2 / Infinity-Cache round trip per fragment; PMC: the
+    // C128 launches fetched 1.67x their compulsory bytes with the re-read). 2-byte storage: plain blocks with
+    // the staged (C = 64) or the row-pair-swapped (C = 128) epilogue, where the kept VGPRs fit the occupancy
+    // budget (C = 64: 16 x 16 and 8 x 16 tiles; the 20 x 16 tile's five fragments per wave exceed it, and the
+    // tile picker charges that form for its re-read, bugseg_runtime.cpp)
+    static constexpr bool KEEP = (!DN && ES == 2 && (SWAP || !REG3) && NF2 * KS1 * 4 <= (C == 128 ? 48 : 32)) || KEEPF;
+    // ---- tuning constants, by measurement (edit the number for an A/B build)
+    // CH1: phase-1 fragments whose loads fly together. The fp32 down C128 form (the only KS1 >= 8 one) 1 (2: 241
+    // VGPRs, no spills, 115.5-117.0 -> 120.2-121.6 us); KS1 >= 4: all of a wave's fragments; the symmetric 16 x 16
+    // C64 form all of its 5-6 in one round trip (37.3 -> 36.0 us); the other KS1 = 2 forms 4 (down C64: 5 spills
+    // one register, 6 spills 22; at 4 its 6 fragments per wave take two round trips either way)
+    static constexpr int NF1 = (HR + 15) / 16;        // 16-pixel fragments of tile + halo
+    static constexpr int CH1 = KS1 >= 8 ? 1 : KS1 >= 4 ? (NF1 + NW - 1) / NW : KS1 == 2 ? (C == 64 && V == 0 && !DN && !ASYM ? 6 : 4) : 8;
+    // PH2U: k-steps of the symmetric middle conv unrolled together: 3 for C = 128 (9 k-steps; no spills, its
+    // launches 1-4% faster; 2 and 9 spill) and for the fp32 C = 16 / 64 non-down forms (C16 166.8 -> 163.4 us, C64
+    // 8 x 16 145.0 -> 143.9 us), 1 elsewhere (down C64 6% slower at 3, fp32 down C64 12 us slower).
+    // ASYMU: the same for the asymmetric 5x1 / 1x5 passes
+    static constexpr int PH2U = ((C == 128 && !DN && !(KEEP && V == 2)) || (ES == 4 && C != 128 && !DN)) ? 3 : 1, ASYMU = 1;
+    // NBE: border fragments whose loads fly with the kept interior ones; any further ones (a wave with two) are
+    // loaded after, which keeps the x registers within the occupancy budget (C = 64 / 4x80: spills at 1; fp32
+    // C128: 0 measured 1-4 us per 64-frame launch faster)
+    static constexpr int NBE = C == 128 && !RD && !ASYM && ES == 2 ? 1 : 0;
     // otile (class fusion) pixel stride (elements): 80 B (fp32) / 48 B — 5 / 3 16-B units, so the 16-B reads
     // of any 16 consecutive pixels fall in distinct bank groups
     static constexpr int OPS = ES == 4 ? 20 : 24;
@@ -288,24 +252,8 @@ int bneck_variants(int C) { return C == 128 ? 6 : C == 16 ? 2 : 3; }   // C128 v
 // 3x3, and the residual is the main branch — maxpool 2x2 of the input, zero-padded from CI to C
 // channels, its argmax indices written for the paired upsampling block. The pooling uses the
 // projection's own B fragments (lane kq holds taps of one 8-channel group: the 4 taps in-lane for
-// CI >= 32, two taps in-lane + one v_permlane32_swap for CI = 16) and leaves the pooled values in a
-// small global scratch (a.pool) that phase 3 reads back as its residual (L2 hits).
-// fp32 (parity mode): registers unconstrained (LDS bounds the C = 64 / 128 forms first), except C = 16,
-// held to 4 waves per SIMD (5 spilled with the split t0 storage; unconstrained: 16 AGPRs on top of 91 VGPRs)
-#ifndef BNECK_F32_OCC16
-#define BNECK_F32_OCC16 4   // (5 spilled 32 B with the split t0: 102.0 vs 90.8 us per launch at 4)
-#endif
-// fp32 C = 64 / 128: waves per SIMD the build is held to (1 = registers unconstrained; A/B knob, round 4:
-// with split-f16 products the fp32 forms are issue / latency bound at 2-3 waves per SIMD)
-#ifndef BNECK_F32_OCC64
-#define BNECK_F32_OCC64 1
-#endif
-#ifndef BNECK_F32_OCC64_V2
-#define BNECK_F32_OCC64_V2 4   // the 8 x 16 C = 64 form: 127 VGPRs, no spills at 4 (round 5: 139.8 -> 137.9 us per launch; 1 = unconstrained, 154 VGPRs, 3 waves per SIMD)
-#endif
-#ifndef BNECK_F32_OCC128
-#define BNECK_F32_OCC128 1
-#endif
+// CI >= 32, two taps in-lane + one v_permlane32_swap for CI = 16) and leaves the pooled values of each wave's
+// interior fragments in registers, as phase 3's residual (see the down walk in phase 1).
 // fp32 mode range scaling (bugseg_internal.h RangeArgs, mfma_common.h): the exponents of x (measured by
 // the launch that wrote it), t0, t1 (asymmetric: t1a, t1; rigorous bounds from x's range), as the
 // multipliers of the accumulators. `any`: some multiply is needed — the asymmetric 1x5's output aside,
@@ -325,38 +273,13 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     using F = BneckForm<T, C, ASYM, V, CI, FC>;
     constexpr int TH = F::TH, TW = F::TW, NW = F::NW, NT = F::NT, IS = F::IS, NR1 = F::NR1, NR3 = F::NR3;
     constexpr int G1 = F::G1, KS1 = F::KS1, G2 = F::G2, KS2 = F::KS2, HWW = F::HWW, HR = F::HR, NPX = F::NPX, NF2 = F::NF2, NPA = F::NPA;
+    constexpr int NF1 = F::NF1, CH1 = F::CH1, PH2U = F::PH2U, ASYMU = F::ASYMU, NBE = F::NBE;
     constexpr int PSTR = F::PSTR, PLO = F::PLO, K1S = F::K1S, K2S = F::K2S, K3S = F::K3S, ZP = F::ZP, EPC = F::EPC, OSTR = F::OSTR, OPS = F::OPS;
     constexpr bool DN = F::DN, RD = F::RD, CLS = F::CLS, HL = F::HL, PL = F::PL, REG3 = F::REG3, SWAP = F::SWAP, HSTG = F::HSTG, KEEPF = F::KEEPF, KEEP = F::KEEP;
-    // output store policy (mfma_common.h): sc1 for C >= 64; the fp32 C = 64 (non-down) form streams its
-    // output non-temporally (nt) — round 5, B = 64, one stream: the blocks reading it (down C128, up C16)
-    // 14-18 us faster per launch. nt measured worse for the fp32 C16 form (itself +4 us), the down forms
-    // (down C64 +32 us) and the C128 forms (+10%) — A/B knobs BNECK_NT_F32_C64 / _C16 / _DN.
-    // Re-measured under the alternating tile order: the consumers now start on the lines this
-    // form wrote last, and the headline is 0.4% higher with the C64 form's stores left in the cache, so
-    // BNECK_NT_F32_C64 is 0; the other constants measured equal or slower when flipped and keep their values
-#ifndef BNECK_NT_F32_C64
-#define BNECK_NT_F32_C64 0
-#endif
-#ifndef BNECK_NT_F32_C16
-#define BNECK_NT_F32_C16 0
-#endif
-#ifndef BNECK_NT_F32_DN
-#define BNECK_NT_F32_DN 0
-#endif
-#ifndef BNECK_NT_2B_C64
-#define BNECK_NT_2B_C64 1
-#endif
-    constexpr bool NTO = (sizeof(T) == 4 && ((CI == 0 && ((C == 64 && BNECK_NT_F32_C64) || (C == 16 && BNECK_NT_F32_C16))) ||
-                                             (CI != 0 && BNECK_NT_F32_DN))) ||
-                         (sizeof(T) == 2 && CI == 0 && C == 64 && BNECK_NT_2B_C64);
-#ifndef BNECK_AUX_F32_C128
-#define BNECK_AUX_F32_C128 16
-#endif
-#ifndef BNECK_AUX_F32_LOW
-#define BNECK_AUX_F32_LOW 0    // fp32 forms that take the default policy (C16, down C64): A/B knob
-#endif
-    constexpr int OAUX = OUT_AUX_SEL(NTO ? 2 : (sizeof(T) == 4 && C == 128) ? BNECK_AUX_F32_C128
-                                     : (C >= 64 && CI != 16) ? 16 : sizeof(T) == 4 ? BNECK_AUX_F32_LOW : 0);
+    // output store policy (mfma_common.h bst16o): sc1 write-through for C >= 64 (the down C64 form, CI = 16, keeps the
+    // default, as C = 16 does); the 2-byte C = 64 (non-down) form streams its output non-temporally (nt). What was
+    // measured per form and precision: DESIGN.md 6.24
+    constexpr int OAUX = sizeof(T) == 2 && CI == 0 && C == 64 ? 2 : C >= 64 && CI != 16 ? 16 : 0;
     static_assert(!DN || (!ASYM && !TR && !RD && (CI == 16 || CI % 32 == 0)), "down mode: plain tiles");
     constexpr int CG1 = CI / 8;                       // down: 8-channel groups per tap
     constexpr int G3 = IS / 8;                        // expand k groups (<= 4: one step)
@@ -364,91 +287,32 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                   "windowed C128 forms: fp32, asymmetric plain tiles or row-dilated tiles");
     constexpr bool WRD = WIN && RD;                   // row-dilated window: fragments past its last row are skipped
     constexpr int RY = F::RY, RX = F::RX;             // halo rows / columns of the middle conv (tile coordinates)
-    constexpr int NF1 = (HR + 15) / 16;               // 16-pixel fragments of tile + halo
     constexpr int NFT = (NPX + 15) / 16;              // 16-pixel fragments of the tile (NF2 per wave: the last may be partial / absent)
     constexpr int TWA = TW + 4;                       // asymmetric: width of t1a (the 1x5's halo)
     constexpr int NFA = (NPA + 15) / 16;
     constexpr int NF2A = (NFA + NW - 1) / NW;
-#ifndef BNECK_CH1_K2
-#define BNECK_CH1_K2 4   // down C64: 49.9 -> 49.4 us at 5 (one spill; round 2); round 4, with DKEEP: 4 spills none, 48.6-49.5 -> 47.4-47.9 us (its 6 fragments per wave take two round trips either way); 6 spills 22
-#endif
-// k-steps of the symmetric middle conv unrolled together: 3 for C = 128 (9 k-steps; no spills, its
-// launches 1-4% faster), 1 elsewhere (down C64 6% slower at 3; 2 and 9 spill on C = 128).
-// -DBNECK_PH2_UNROLL=N forces one factor everywhere (A/B builds).
-#ifndef BNECK_PH2_UNROLL
-#define BNECK_PH2_UNROLL 0
-#endif
-#ifndef BNECK_ASYM_UNROLL
-#define BNECK_ASYM_UNROLL 1    // k-steps of the asymmetric 5x1 / 1x5 passes unrolled together (A/B knob)
-#endif
-#ifndef BNECK_CH1_C64
-#define BNECK_CH1_C64 6   // the symmetric 16x16 C64 form: all of a wave's 5-6 phase-1 fragments in one round trip (37.3 -> 36.0 us)
-#endif
-#ifndef BNECK_CH1_K8
-#define BNECK_CH1_K8 1
-#endif
-#ifndef BNECK_CH1_K8_F32
-#define BNECK_CH1_K8_F32 1   // fp32 down C128 (the only KS1 >= 8 form): phase-1 fragments in flight (A/B knob; 2: 241 VGPRs, no spills, 115.5-117.0 -> 120.2-121.6 us, round 5)
-#endif
-    constexpr int CH1 = KS1 >= 8 ? (sizeof(T) == 4 ? BNECK_CH1_K8_F32 : BNECK_CH1_K8) : KS1 >= 4 ? (NF1 + NW - 1) / NW
-                    : KS1 == 2 ? (C == 64 && V == 0 && !DN && !ASYM ? BNECK_CH1_C64 : BNECK_CH1_K2) : 8;   // phase-1 fragments whose loads fly together
     constexpr bool HALF = REG3 && sizeof(T) == 2 && NR3 % 2 != 0;
     constexpr int CPP = C / EPC;                      // 16-B chunks per pixel
     constexpr int CPF = 16 * CPP;                     // (staged) 16-B chunks of one 16-pixel fragment
     constexpr int CPL = (CPF + 63) / 64;              // ... per lane
     constexpr int RQ3 = !REG3 ? CPL : SWAP ? NR3 / 2 : NR3;   // residual chunks per lane per fragment
     static_assert(TW % 16 == 0, "a fragment is a run of one tile row");
-#ifndef BNECK_NBE
-#define BNECK_NBE -1     // border fragments loaded with the kept ones (-1: per form, see phase 1)
-#endif
-#ifndef BNECK_CONST_GLDS
-#define BNECK_CONST_GLDS 1   // epilogue constants by LDS-DMA: 0 off, 1 for C != 128 (C64 38.0 -> 36.5 us; C128 23.1 -> 23.5), 2 all
-#endif
-#ifndef BNECK_GLDS_PARTIAL
-#define BNECK_GLDS_PARTIAL 1   // KEEP: the first tile waits for the weights only, not for its x loads
-#endif
     static_assert(!KEEP || !REG3 || (KEEPF ? 2 * KS1 == RQ3 : KS1 == RQ3), "kept x: one 16-B chunk per k-step and row pair");
-#ifndef BNECK_EARLY_FREE
-#define BNECK_EARLY_FREE 0   // A/B knob, off: bit-identical (GPU parity green) but measured neutral to slower (round 5:
-                             // fp32 C128 16x16 85.8-86.2 -> 86.7-87.0 us, fp16 frames/s -0.3%): a tile's critical
-                             // path is its waves with the most fragments, whichever barrier the others wait at
-#endif
-    // EARLY_FREE (kept x, register epilogue): phase 3 touches no LDS but the read-only weights and
-    // constants (t1 goes from the accumulators to B operands in registers), so the t0 region is free
-    // once every wave has finished phase 2. The barrier that protects it moves from the top of the next
-    // tile to the end of phase 2 (the first tile keeps its top barrier: the weight staging), and a wave
-    // done with its stores starts the next tile's projection while the others are still storing
-    constexpr bool EARLY_FREE = BNECK_EARLY_FREE && KEEP && REG3;
-#ifndef BNECK_DKEEP
-#define BNECK_DKEEP 1
-#endif
-    // DKEEP (down forms, 2-byte storage): phase 1 walks the tile as KEEP does and the main-branch pool
-    // of each interior fragment stays in registers, already in the kept-x chunk layout (lane kq:
-    // channels 32 t + 8 kq .. + 7), as phase 3's residual — instead of a global scratch round trip
-    // (PMC: down C64 read + wrote 1.33x, down C128 1.36x their compulsory bytes with the scratch).
-    // Measured (round 3, fp16, B = 32): down C64 52.9 -> 48.1 us, down C128 33.7 -> 28.7 us
-    // fp32 (round 5): the same walk; a pooled chunk is 8 floats (two 16-B words) in the
-    // kept-x layout of KEEPF, turned into phase 3's row quads by the same two lane swaps (PMC before: down
-    // C64 1.27x, down C128 1.37x their compulsory bytes with the scratch round trip)
-#ifndef BNECK_DKEEP_F32
-#define BNECK_DKEEP_F32 1
-#endif
-    constexpr bool DKEEP = BNECK_DKEEP && DN && ((sizeof(T) == 2 && SWAP) || (sizeof(T) == 4 && BNECK_DKEEP_F32 && REG3));
-    constexpr int NPK = DN ? (CI + 31) / 32 : 1;      // DKEEP: pooled chunks (32 channels of the row pair) per lane and fragment
+    // Down forms: phase 1 walks the tile as KEEP does and the main-branch pool of each interior fragment stays
+    // in registers, already in the kept-x chunk layout (lane kq: channels 32 t + 8 kq .. + 7), as phase 3's
+    // residual. fp32: a pooled chunk is 8 floats (two 16-B words) in the kept-x layout of KEEPF, turned into
+    // phase 3's row quads by the same two lane swaps
+    constexpr int NPK = DN ? (CI + 31) / 32 : 1;      // down: pooled chunks (32 channels of the row pair) per lane and fragment
     constexpr int PKW = sizeof(T) == 4 ? 2 : 1;       // 16-B words per pooled chunk
-    // LINES (fp32 register epilogue, C = 128, round 6; on the fp32 down C64 form it cost 4 VGPRs and the third
+    // LINES (every fp32 C = 128 form; on the fp32 down C64 form it cost 4 VGPRs and the third
     // wave per SIMD): an accumulator quad is 16 B (channels 16 r + 4 kq ..
     // + 3 of pixel col), so one store per row r writes 16 pixels x 64 B — half lines. With LINES the quads
     // of rows 2u and 2u + 1 of pixels col and col ^ 8 are traded across lanes 8 apart (one DPP row
     // rotation per dword) and each of the two stores per u writes the whole 128-B line u of 8 pixels.
     // Same values, other lanes: bit-identical (the fp32 up C64 block's form of this cut its HBM writes
     // 422 -> 315 MB and its time 129 -> 111 us per 64-frame launch)
-#ifndef BNECK_F32_LINES
-#define BNECK_F32_LINES 1
-#endif
-    constexpr bool LINES64 = BNECK_F32_LINES64 && sizeof(T) == 4 && REG3 && C == 64 && !DN && !KEEP;   // residual from the ring
-    constexpr bool LINES = (BNECK_F32_LINES && sizeof(T) == 4 && REG3 && C == 128 && (KEEPF || (DKEEP && PKW == 2)) && RQ3 % 2 == 0) ||
-                           LINES64;
+    constexpr bool LINES = sizeof(T) == 4 && C == 128;
+    static_assert(!LINES || (REG3 && RQ3 % 2 == 0 && (KEEPF || DN)), "whole-line stores: row pairs of the register epilogue");
     // FC >= 0 (round 6): ENet's class layer fused into its last bottleneck (C = 16, 16 x 16 tiles), FC =
     // the class map's LUT kind (cls_common.h cls_argmax). Tiles overlap by one row and one column (a
     // 15 x 15 stride): phase 3 leaves the block output of all 16 x 16 tile pixels in LDS (otile) instead
@@ -554,8 +418,8 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)src,
                                                  (__attribute__((address_space(3))) void *)(smem + (size_t)base * 16), 16, 0, 0);
         }
-        if constexpr (BNECK_CONST_GLDS == 2 || (BNECK_CONST_GLDS == 1 && C != 128)) {
-            // the epilogue constants by LDS-DMA as well (one dword per lane, 64 per instruction,
+        if constexpr (C != 128) {
+            // the epilogue constants by LDS-DMA as well (C64 38.0 -> 36.5 us; C128 23.1 -> 23.5, so it copies: one dword per lane, 64 per instruction,
             // spread over the waves): a plain load -> LDS store here would wait (vmcnt, in order)
             // for the weight DMA issued above and serialise the staging ahead of the x loads
             const float *srcs[9] = {a.b1, a.s1, a.b2, a.s2, a.b2b, a.s2b, a.b3, a.s3, a.s_out};
@@ -614,10 +478,9 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     }
     // x / out through buffer descriptors: 32-bit offsets, and an out-of-range offset reads 0 / drops
     // the store (mfma_common.h), so image-border masking costs one select per access
-    // down mode: x is the (2H, 2W, CI) block input; the residual comes from the pooled scratch
+    // down mode: x is the (2H, 2W, CI) block input
     const auto rxb = mkbuf(DN ? a.xin : a.x, DN ? a.xin_bytes : a.x_bytes);
     const auto rob = mkbuf(a.out, a.x_bytes);
-    const auto rpb = mkbuf(a.pool, a.pool_bytes);
     const auto rib = mkbuf(a.idx_out, a.idx_bytes);
     // the fused path is planned only when every slope is <= 1 (bugseg_runtime.cpp fusable_regular),
     // so PReLU is max(v, s*v); accumulators start at the bias
@@ -702,7 +565,9 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
     // PREF (KEEP, register epilogue; A/B knob, off): as phase 3 finishes with a fragment's kept x, the
     // same registers receive that fragment's x of the workgroup's NEXT tile, so its loads fly during the
     // rest of this tile's phase 3. Measured slower (round 5, B = 64: fp32 C128 20x16 90.9 -> 100.6 us,
-    // fp16 33.4 -> 34.4 us; the loads contend with phase 3's stores and cost the fp16 form 5 spilled VGPRs)
+    // fp16 33.4 -> 34.4 us; the loads contend with phase 3's stores and cost the fp16 form 5 spilled VGPRs).
+    // Still a switch, the one settled knob that is: without the loop-carried `pref` the compiler allocates the 26
+    // kept-residual register-epilogue kernels differently, in every source shape tried
 #ifndef BNECK_PREF
 #define BNECK_PREF 0
 #endif
@@ -757,21 +622,6 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
         };
         // byte offset of pixel pi of fragment f (channel 0), or OOB outside the image
         auto pix_base = [&](int f, int pi) -> uint32_t { return pix_off(f, pi, 0); };
-        // residual source: x itself, or (down) the pooled scratch (CI channels; channels >= CI read 0)
-        const auto rrb = DN ? rpb : rxb;
-        const uint32_t pn = (uint32_t)(n * a.H * a.W) * (uint32_t)(CI * sizeof(T));
-        auto res_off = [&](int f, int pi, int ch) -> uint32_t {
-            if constexpr (!DN) {
-                return pix_off(f, pi, ch);
-            } else {
-                const int i = (f * 16) / TW, j = (f * 16) % TW + pi;
-                const int y = oy0 + dt * i, x = ox0 + dtx * j;
-                const bool ok = y < a.H && x < a.W && ch < CI;
-                uint32_t v = pn + ((__umul24((uint32_t)y, (uint32_t)a.W) + (uint32_t)x) * CI + ch) * (uint32_t)sizeof(T);
-                asm volatile("" : "+v"(v));
-                return ok ? v : OOB;
-            }
-        };
         // down: main-branch maxpool of output pixel (y, x) from the projection's B fragments (see the
         // kernel comment); the first maximum in window order wins (strict >, NaN / -inf never chosen:
         // as a key, larger value first, then lower window position; position 4 = no candidate -> 0)
@@ -806,17 +656,9 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                         lo |= (uint32_t)(bp[i] & 3) << (8 * i);
                         hi |= (uint32_t)(bp[4 + i] & 3) << (8 * i);
                     }
-                    if constexpr (DKEEP) {
-                        pk[kslot * PKW] = kval ? make_uint4(pw[0], pw[1], pw[2], pw[3]) : make_uint4(0u, 0u, 0u, 0u);
-                        if constexpr (PKW == 2)
-                            pk[kslot * PKW + 1] = kval ? make_uint4(pw[4], pw[5], pw[6], pw[7]) : make_uint4(0u, 0u, 0u, 0u);
-                    } else {
-                        (void)kslot; (void)kval;
-                        const uint32_t po = wr ? (pix * CI + cc * 8) * (uint32_t)sizeof(T) : OOB;
-#pragma unroll
-                        for (int i = 0; i < (int)(8 * sizeof(T) / 16); ++i)
-                            bst16(rpb, po == OOB ? OOB : po + 16 * i, make_uint4(pw[4 * i], pw[4 * i + 1], pw[4 * i + 2], pw[4 * i + 3]));
-                    }
+                    pk[kslot * PKW] = kval ? make_uint4(pw[0], pw[1], pw[2], pw[3]) : make_uint4(0u, 0u, 0u, 0u);
+                    if constexpr (PKW == 2)
+                        pk[kslot * PKW + 1] = kval ? make_uint4(pw[4], pw[5], pw[6], pw[7]) : make_uint4(0u, 0u, 0u, 0u);
                     __builtin_amdgcn_raw_buffer_store_b64((u32x2_t){lo, hi}, rib, wr ? (int)(pix * a.idxCS + cc * 8) : (int)OOB, 0, 0);
                 };
                 // in window order: strict > from -inf (NaN and -inf never taken), position 4 = none
@@ -869,7 +711,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                         bp[i] = t ? pp : bp[i];
                     }
                     // both halves now agree; lanes 0-31 (groups kq = 0, 1) write
-                    emit(kq & 1, bv, bp, interior && lo_half, 0, lo_half);   // (DKEEP: channels 16-31 are 0)
+                    emit(kq & 1, bv, bp, interior && lo_half, 0, lo_half);   // (channels 16-31 are 0)
                 }
             }
         };
@@ -910,7 +752,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             }
             return ok;
         };
-        // KEEP / DKEEP walk: the tile's interior as phase 3's fragments (a run of one tile row, on the
+        // KEEP / down walk: the tile's interior as phase 3's fragments (a run of one tile row, on the
         // wave that will expand it), then the halo border
         constexpr int NBD = HR - NPX, NFB = (NBD + 15) / 16;   // border pixels / fragments
         constexpr int NBW = (NFB + NW - 1) / NW;      // border fragments per wave (at most)
@@ -943,7 +785,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 }
             }
         };
-        uint4 pres[DKEEP ? NF2 : 1][NPK * PKW];       // DKEEP: pooled residual of the interior fragments
+        uint4 pres[DN ? NF2 : 1][NPK * PKW];          // down: pooled residual of the interior fragments
         if constexpr (KEEP) {
             // every load of the wave's phase-1 work (its interior fragments, kept, and its share of
             // the border) is issued before the first MFMA: one memory round trip per tile
@@ -961,10 +803,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 bh[k] = b < NBD ? bord_h(b) : 0;
                 bok[k] = load_h(bh[k], b < NBD, bx[k]);
             };
-            // the first NBE border fragments fly with the interior ones; any further ones (a wave
-            // with two) are loaded after, which keeps the x registers within the occupancy budget
-            // (C = 64 / 4x80: spills at 1; fp32 C128: 0 measured 1-4 us per 64-frame launch faster, round 5)
-            constexpr int NBE = BNECK_NBE >= 0 ? BNECK_NBE : C == 128 && !RD && !ASYM && sizeof(T) == 2 ? 1 : 0;
+            // the first NBE border fragments fly with the interior ones (BneckForm::NBE)
 #pragma unroll
             for (int k = 0; k < NBE && k < NBW; ++k)
                 if (wb + NW * k < NFB && needb(wb + NW * k)) load_b(k);     // wave-uniform
@@ -979,10 +818,10 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 for (int j = 0; j < NF2; ++j) nld += wave + NW * j < NFT && need1(wave + NW * j) ? KS1 * LPS : 0;
 #pragma unroll
                 for (int k = 0; k < NBE && k < NBW; ++k) nld += wb + NW * k < NFB && needb(wb + NW * k) ? KS1 * LPS : 0;
-                vm_wait_upto(BNECK_GLDS_PARTIAL ? (nld < 24 ? nld & ~1 : 24) : 0);   // (fewer outstanding: still after the weights)
+                vm_wait_upto(nld < 24 ? nld & ~1 : 24);   // (fewer outstanding: still after the weights)
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (!EARLY_FREE || first) __builtin_amdgcn_s_barrier();   // weights staged (first tile) / previous tile done with ts
+            __builtin_amdgcn_s_barrier();   // weights staged (first tile) / previous tile done with ts
             asm volatile("" ::: "memory");
             if constexpr (F32 && !SCL) {
                 // the range words arrived with the loads issued before them: bail out to the scaled body
@@ -1004,7 +843,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 if (k >= NBE) load_b(k);
                 proj(bh[k], fb * 16 + col < NBD, bok[k], bx[k]);
             }
-        } else if constexpr (DKEEP) {
+        } else if constexpr (DN) {
             // down forms: the wave's interior fragments, then its border share, CH1 fragments' loads in
             // flight at a time (the 2x2 stride-2 taps of the block input)
             constexpr int NQ = NF2 + NBW;
@@ -1077,16 +916,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 for (int s = 0; s < KS1; ++s) {
                     const int g = s * 4 + kq;
                     const bool ld = okc[c] && g < G1;
-                    if constexpr (DN) {
-                        // 2x2 stride-2 tap (tap = g / CG1: dy = tap >> 1, dx = tap & 1), pack_conv's K order
-                        const int tap = g / CG1, cc = g - tap * CG1;
-                        const uint32_t sy = (uint32_t)(2 * iy + (tap >> 1)), sx = (uint32_t)(2 * ix + (tap & 1));
-                        uint32_t v = xin_n + ((__umul24(sy, (uint32_t)(2 * a.W)) + sx) * CI + cc * 8) * (uint32_t)sizeof(T);
-                        asm volatile("" : "+v"(v));
-                        bld8(xf[c][s], rxb, ld ? v : OOB);
-                    } else {
-                        bld8(xf[c][s], rxb, ld ? xn + ((__umul24((uint32_t)iy, (uint32_t)a.W) + (uint32_t)ix) * C + g * 8) * (uint32_t)sizeof(T) : OOB);
-                    }
+                    bld8(xf[c][s], rxb, ld ? xn + ((__umul24((uint32_t)iy, (uint32_t)a.W) + (uint32_t)ix) * C + g * 8) * (uint32_t)sizeof(T) : OOB);
                 }
             }
 #pragma unroll
@@ -1103,12 +933,6 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                         if (!okc[c]) v = make_float4(0.f, 0.f, 0.f, 0.f);
                         st4t(ts + h * PSTR + ch, ch, v);
                     }
-                }
-                if constexpr (DN) {
-                    const int hy = h / HWW, hx = h - hy * HWW;
-                    const bool interior = okc[c] && hy >= 1 && hy <= TH && hx >= 1 && hx <= TW;
-                    uint4 pkd[NPK * PKW];
-                    pool_store(xf[c], interior, oy0 + (hy - 1), ox0 + (hx - 1), pkd);
                 }
             }
         }
@@ -1134,35 +958,20 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 const int f = wave + NW * j;
 #pragma unroll
                 for (int k = 0; k < CPL; ++k) {
-                    const uint32_t off = res_off(f, sc_px(k), sc_ch(k) * EPC);
-                    r[k] = bld16(rrb, HSTG || sc_q(k) < CPF ? off : OOB);
+                    const uint32_t off = pix_off(f, sc_px(k), sc_ch(k) * EPC);
+                    r[k] = bld16(rxb, HSTG || sc_q(k) < CPF ? off : OOB);
                 }
                 return;
             }
-            if constexpr (LINES64) {
-                // whole lines, as LINES stores them: per u, line u of pixels col and col ^ 8 (the lane's 16 B
-                // of each); phase 3 trades them back into its row 2u / 2u + 1 quads (see there)
-                const uint32_t pc = pix_base(wave + NW * j, col), po8 = pix_base(wave + NW * j, col ^ 8);
-                const bool lo8 = col < 8;
-                const uint32_t pa = lo8 ? pc : po8, pb = lo8 ? po8 : pc;
-#pragma unroll
-                for (int u = 0; u < RQ3 / 2; ++u) {
-                    const uint32_t cb = (uint32_t)(u * 32 + (lo8 ? 0 : 16) + kq * 4) * (uint32_t)sizeof(T);
-                    r[2 * u] = bld16(rrb, pa == OOB ? OOB : pa + cb);
-                    r[2 * u + 1] = bld16(rrb, pb == OOB ? OOB : pb + cb);
-                }
-                return;
-            }
-            const uint32_t po = DN ? 0u : pix_base(wave + NW * j, col);
+            const uint32_t po = pix_base(wave + NW * j, col);
 #pragma unroll
             for (int t = 0; t < RQ3; ++t) {
-                const uint32_t off = DN ? res_off(wave + NW * j, col, chunk_ch(t))
-                                        : po == OOB ? OOB : po + (uint32_t)chunk_ch(t) * (uint32_t)sizeof(T);
+                const uint32_t off = po == OOB ? OOB : po + (uint32_t)chunk_ch(t) * (uint32_t)sizeof(T);
                 if constexpr (HALF) {
-                    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rrb, (int)off, 0, 0);
+                    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rxb, (int)off, 0, 0);
                     r[t] = make_uint4(v.x, v.y, 0u, 0u);
                 } else {
-                    r[t] = bld16(rrb, off);
+                    r[t] = bld16(rxb, off);
                 }
             }
         };
@@ -1170,7 +979,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #pragma unroll
             for (int j = 0; j < RP; ++j) load_res(j, res[j]);
         };
-        if constexpr (!ASYM && !KEEP && !DKEEP) prefetch_res();
+        if constexpr (!ASYM && !KEEP && !DN) prefetch_res();
 
         // t1 never goes through LDS: each wave's middle-conv accumulators (quads: lane kq holds channels
         // 4kq..4kq+3 of a pixel) are rounded as the unfused plan stores them and turned into the
@@ -1209,10 +1018,6 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             for (int j = 0; j < NF2; ++j)
 #pragma unroll
                 for (int r = 0; r < NR1; ++r) acc[j][r] = bias_m(cb2 + r * 16 + kq * 4, b2m, SCL);
-            // (fp32 C = 16 / 64 non-down forms: 3 as well — round 5, B = 64: C16 166.8 -> 163.4 us, C64 8x16
-            // 145.0 -> 143.9 us; the fp32 down C64 form lost 12 us at 3, so it keeps 1)
-            constexpr int PH2U = BNECK_PH2_UNROLL > 0 ? BNECK_PH2_UNROLL
-                               : ((C == 128 && !DN && !(KEEP && V == 2)) || (sizeof(T) == 4 && C != 128 && !DN)) ? 3 : 1;
 #pragma unroll PH2U
             for (int s = 0; s < KS2; ++s) {
                 const int g = s * 4 + kq;
@@ -1259,7 +1064,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             for (int j = 0; j < NF2A; ++j)
 #pragma unroll
                 for (int r = 0; r < NR1; ++r) acc5[j][r] = bias_m(cb2 + r * 16 + kq * 4, b2m, SCL);
-#pragma unroll BNECK_ASYM_UNROLL
+#pragma unroll ASYMU
             for (int s = 0; s < KS2; ++s) {
                 const int g = s * 4 + kq;
                 const int tap = g / (IS / 8), coff = (g - tap * (IS / 8)) * 8;
@@ -1330,7 +1135,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 for (int j = 0; j < NF2; ++j)
 #pragma unroll
                     for (int r = 0; r < NR1; ++r) acc[j][r] = bias_m(cb2b + r * 16 + kq * 4, b2bm, SCL);
-#pragma unroll BNECK_ASYM_UNROLL
+#pragma unroll ASYMU
                 for (int s = 0; s < KS2; ++s) {
                     const int g = s * 4 + kq;
                     const int tap = g / (IS / 8), coff = (g - tap * (IS / 8)) * 8;
@@ -1469,7 +1274,6 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             STAMP(6);
             continue;
         }
-        if constexpr (EARLY_FREE) __syncthreads();        // every wave done reading t0 / t1a: the next tile may write them
         STAMP(5);
 #pragma unroll
         for (int j = 0; j < NF2; ++j) {
@@ -1477,7 +1281,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
             if constexpr (WRD)
                 if (!live(wave + NW * j)) continue;
             const uint32_t po = pix_base(wave + NW * j, col);
-            // kept fp32 x (KEEPF) / pooled fp32 main branch (DKEEP) -> residual quads in place: chunk s
+            // kept fp32 x (KEEPF) / pooled fp32 main branch (down) -> residual quads in place: chunk s
             // (lane kq: channels 32 s + 8 kq .. + 7) becomes .a = row 2 s, .b = row 2 s + 1
             auto to_quads = [&](RawF &k) {
                 uint32_t a[4] = {__float_as_uint(k.a.x), __float_as_uint(k.a.y), __float_as_uint(k.a.z), __float_as_uint(k.a.w)};
@@ -1490,7 +1294,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                 k.a = make_float4(__uint_as_float(a[0]), __uint_as_float(a[1]), __uint_as_float(a[2]), __uint_as_float(a[3]));
                 k.b = make_float4(__uint_as_float(b[0]), __uint_as_float(b[1]), __uint_as_float(b[2]), __uint_as_float(b[3]));
             };
-            if constexpr (DKEEP && PKW == 2) {
+            if constexpr (DN && PKW == 2) {
 #pragma unroll
                 for (int s = 0; s < NPK; ++s) to_quads(reinterpret_cast<RawF &>(pres[j][2 * s]));
             }
@@ -1515,27 +1319,11 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 #pragma unroll
                 for (int u = 0; u < RQ3 / 2; ++u) {
                     float4 v2[2];
-                    // LINES64: the ring holds line u of pixels pa / pb (load_res); lane col's row 2u quad is its
-                    // own first word (lo8) or lane col - 8's second, row 2u + 1 the mirror image
-                    uint4 rl[2];
-                    if constexpr (LINES64) {
-                        const uint4 l1 = res[j % RP][2 * u], l2 = res[j % RP][2 * u + 1];
-                        const uint4 xs = lo8 ? l2 : l1;
-                        uint4 ys;
-                        ys.x = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xs.x, 0x128, 0xf, 0xf, false);
-                        ys.y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xs.y, 0x128, 0xf, 0xf, false);
-                        ys.z = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xs.z, 0x128, 0xf, 0xf, false);
-                        ys.w = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xs.w, 0x128, 0xf, 0xf, false);
-                        rl[0] = lo8 ? l1 : ys;
-                        rl[1] = lo8 ? ys : l2;
-                    }
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int t = 2 * u + h;
                         uint4 rc;
-                        if constexpr (LINES64) {
-                            rc = rl[h];
-                        } else if constexpr (KEEPF) {
+                        if constexpr (KEEPF) {
                             const RawF &k = reinterpret_cast<const RawF &>(kx[j][t >> 1]);
                             rc = __builtin_bit_cast(uint4, (t & 1) ? k.b : k.a);
                         } else {
@@ -1559,8 +1347,6 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                     bst16o<OAUX>(rob, pa == OOB ? OOB : pa + cb, lo8 ? u0 : ys);
                     bst16o<OAUX>(rob, pb == OOB ? OOB : pb + cb, lo8 ? ys : u1);
                 }
-                if constexpr (LINES64)   // (the ring's refill, as below)
-                    if (j + RP < NF2 && wave + NW * (j + RP) < NFT) load_res(j + RP, res[j % RP]);
                 continue;
             }
 #pragma unroll
@@ -1571,8 +1357,8 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                     const RawF &k = reinterpret_cast<const RawF &>(kx[j][t >> 1]);
                     rc = __builtin_bit_cast(uint4, (t & 1) ? k.b : k.a);
                 } else if constexpr (KEEP) rc = reinterpret_cast<const RawH &>(kx[j][t]).v;
-                else if constexpr (DKEEP && PKW == 2) rc = t < 2 * NPK ? pres[j][t < 2 * NPK ? t : 0] : make_uint4(0u, 0u, 0u, 0u);
-                else if constexpr (DKEEP) rc = t < NPK ? pres[j][t < NPK ? t : 0] : make_uint4(0u, 0u, 0u, 0u);
+                else if constexpr (DN && PKW == 2) rc = t < 2 * NPK ? pres[j][t < 2 * NPK ? t : 0] : make_uint4(0u, 0u, 0u, 0u);
+                else if constexpr (DN) rc = t < NPK ? pres[j][t < NPK ? t : 0] : make_uint4(0u, 0u, 0u, 0u);
                 else rc = res[j % RP][t];
                 if constexpr (SWAP) {
                     const int r0 = 2 * t, r1 = 2 * t + 1;
@@ -1585,7 +1371,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                     mma(acc1, w1, tf[j]);
                     // residual chunk -> quads of rows r0 / r1
                     uint32_t a0 = rc.x, a1 = rc.y, b0 = rc.z, b1 = rc.w;
-                    if constexpr (KEEP || DKEEP) {
+                    if constexpr (KEEP || DN) {
                         // kept x (lane kq: channels 32 t + 8 kq .. + 7, dwords d0..d3): row r0's quad
                         // of lane kq lives in lane kq / 2 (d0, d1 or d2, d3), row r1's in lane 2 + kq / 2;
                         // a row swap then a half swap of (d0, d2) and of (d1, d3) gathers both
@@ -1629,7 +1415,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
                     }
                 }
             }
-            if constexpr (!KEEP && !DKEEP)
+            if constexpr (!KEEP && !DN)
                 if (j + RP < NF2 && wave + NW * (j + RP) < NFT) load_res(j + RP, res[j % RP]);
             if constexpr (PREF) {
                 if (has_next) {
@@ -1744,7 +1530,7 @@ __device__ __forceinline__ bool bneck_body(const BneckArgs &a, float rlane) {
 }
 
 template <typename T, int C, bool ASYM, int V, bool TR, int CI = 0>
-__global__ void __launch_bounds__((BShape<C, V>::NW * 64), (sizeof(T) == 2 ? BShape<C, V>::OCC : C == 16 ? BNECK_F32_OCC16 : C == 64 ? (V == 2 ? BNECK_F32_OCC64_V2 : BNECK_F32_OCC64) : BNECK_F32_OCC128)) bneck_kernel(const BneckArgs a) {
+__global__ void __launch_bounds__((BShape<C, V>::NW * 64), (sizeof(T) == 2 ? BShape<C, V>::OCC : BShape<C, V>::OCCF)) bneck_kernel(const BneckArgs a) {
     if constexpr (sizeof(T) == 4) {
         const float rl = rng_lane(a.rg);              // issued first, consumed after the first tile's loads
         if (!bneck_body<T, C, ASYM, V, TR, CI, false>(a, rl)) bneck_body<T, C, ASYM, V, TR, CI, true>(a, rl);
@@ -1756,7 +1542,7 @@ __global__ void __launch_bounds__((BShape<C, V>::NW * 64), (sizeof(T) == 2 ? BSh
 // The row-windowed fp32 C = 128 forms (bneck_body WIN): their own kernels, so the unwindowed ones keep their
 // symbols and code
 template <typename T, int C, bool ASYM, int V>
-__global__ void __launch_bounds__((BShape<C, V>::NW * 64), BNECK_F32_OCC128) bneck_win_kernel(const BneckArgs a) {
+__global__ void __launch_bounds__((BShape<C, V>::NW * 64), (BShape<C, V>::OCCF)) bneck_win_kernel(const BneckArgs a) {
     static_assert(sizeof(T) == 4 && C == 128, "windowed forms: fp32 C = 128");
     const float rl = rng_lane(a.rg);
     if (!bneck_body<T, C, ASYM, V, false, 0, false, -1, true>(a, rl)) bneck_body<T, C, ASYM, V, false, 0, true, -1, true>(a, rl);
@@ -1767,7 +1553,7 @@ __global__ void __launch_bounds__((BShape<C, V>::NW * 64), BNECK_F32_OCC128) bne
 // words, every workgroup evaluates both blocks' exponents and returns when all are 0; otherwise the launch is
 // bneck_kernel's. Their own kernels, outside the form table: the unguarded ones keep their symbols and code.
 template <int V>
-__global__ void __launch_bounds__((BShape<64, V>::NW * 64), (V == 2 ? BNECK_F32_OCC64_V2 : BNECK_F32_OCC64)) bneck_guard64_kernel(const BneckArgs a, const BneckGuardArgs g) {
+__global__ void __launch_bounds__((BShape<64, V>::NW * 64), (BShape<64, V>::OCCF)) bneck_guard64_kernel(const BneckArgs a, const BneckGuardArgs g) {
     span_enter(a.span);                               // (a launch that only checks is stamped too: armed spans cover every op)
     const float mx = rng_reduce(rng_lane(g.ra)), my = rng_reduce(rng_lane(g.rb));
     if (!bneck_range<false>(g.ra, mx).any && !bneck_range<false>(g.rb, my).any) {
@@ -1782,7 +1568,7 @@ __global__ void __launch_bounds__((BShape<64, V>::NW * 64), (V == 2 ? BNECK_F32_
 
 // C = 16 with the class layer fused (FC = the class map's LUT kind); launch bounds as the C = 16 form
 template <typename T, int FC>
-__global__ void __launch_bounds__(256, (sizeof(T) == 2 ? BShape<16, 0>::OCC : BNECK_F32_OCC16)) bneck_cls_kernel(const BneckArgs a) {
+__global__ void __launch_bounds__(256, (sizeof(T) == 2 ? BShape<16, 0>::OCC : BShape<16, 0>::OCCF)) bneck_cls_kernel(const BneckArgs a) {
     if constexpr (sizeof(T) == 4) {
         const float rl = rng_lane(a.rg);
         if (!bneck_body<T, 16, false, 0, false, 0, false, FC>(a, rl)) bneck_body<T, 16, false, 0, false, 0, true, FC>(a, rl);
@@ -1863,7 +1649,7 @@ void bneck_shape(int C, int v, int &th, int &tw, int &nw, int *rd) {
     if (rd) *rd = e ? e->rd : 0;
 }
 
-// the C = 64 2-byte forms that keep their residual in registers (BNECK_KEEP_C64): all but 20 x 16
+// the C = 64 2-byte forms that keep their residual in registers (BneckForm::KEEP): all but 20 x 16
 bool bneck_keeps_c64(int prec, int v) {
     const BneckEntry *e = bneck_form(prec, 64, false, v, false, 0, false);
     return e && e->keep;

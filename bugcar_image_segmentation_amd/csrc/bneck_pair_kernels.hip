@@ -46,10 +46,7 @@ constexpr int PWF = PW1 + PW2 + PW3;                                        // o
 constexpr int PCST = 4 * 16 + 3 * PC;                                       // cb1 cs1 cb2 cs2 | cb3 cs3 cso
 constexpr int PBLK = PWF + PCST;                                            // one block: 26,624 B
 constexpr int PZP = 8;                                                      // zero pad (masked-off B fragments)
-#ifndef BNECK_PAIR_YSTR
-#define BNECK_PAIR_YSTR 68   // y pixel stride (dwords): 256 B + 16 B pad
-#endif
-constexpr int PYS = BNECK_PAIR_YSTR;
+constexpr int PYS = 68;                                                     // y pixel stride (dwords): 256 B + 16 B pad
 static_assert(PYS >= PC && PYS % 4 == 0, "a y pixel is 64 floats, 16-B aligned");
 // The residual x of block A over tile +- 1: 1 = A1 leaves the raw x it loaded in the (then dead) y region and A3
 // reads it where it writes y; 0 = A3 re-reads it from global memory (L2)
@@ -57,14 +54,12 @@ static_assert(PYS >= PC && PYS % 4 == 0, "a y pixel is 64 floats, 16-B aligned")
 #define BNECK_PAIR_XLDS 1
 #endif
 // The next tile's x in flight during the current tile: the first BNECK_PAIR_PREF fragments of every wave (0 = none,
-// 1 = each wave's first, 2 = all) are loaded BNECK_PAIR_PREFAT (0 = before B2 + B3, 1 = before B1, 2 = before
-// A2 + A3, which touch no global memory under XLDS) and held in registers across the loop-end barrier; the rest
-// in A1 as before, behind the first fragment's projection. The defaults by measurement
+// 1 = each wave's first, 2 = all) are loaded before A2 + A3, which touch no global memory under XLDS, and held in
+// registers across the loop-end barrier; the rest in A1 as before, behind the first fragment's projection. The
+// defaults by measurement. These two stay -D switches: the serial tile (both 0) is built as the
+// pair_serial variant by tests/test_gpu_bneck_pair_overlap.py
 #ifndef BNECK_PAIR_PREF
 #define BNECK_PAIR_PREF 1
-#endif
-#ifndef BNECK_PAIR_PREFAT
-#define BNECK_PAIR_PREFAT 2
 #endif
 // Debug build only (-DBUGSEG_STAMPS, scripts/pair_stamp_probe.py): bneck_kernels.hip's phase clocks, here
 // 0 tile top, 1 A1's loads landed, 2 A1 end, 3 A2 + A3 end, 4 B1 end, 5 B2 + B3 end (each behind its barrier)
@@ -294,7 +289,7 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
         }
         __syncthreads();
         STAMP(2);
-        if (NPF && BNECK_PAIR_PREFAT == 2) a1_loads(tile_at(it + nslots), 0, NPF);
+        if (NPF) a1_loads(tile_at(it + nslots), 0, NPF);
 
         // ---- A2 + A3: y over tile +- 1 into LDS, 0 outside the image; the residual x from the y region
         // (XLDS) or re-read (L2)
@@ -327,7 +322,6 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
 
         // ---- B1: t0_B over tile +- 1 from y, into the t0 region (t0_A is dead)
         blk(1, w1, w2, w3, cb1);
-        if (NPF && BNECK_PAIR_PREFAT == 1) a1_loads(tile_at(it + nslots), 0, NPF);
 #pragma unroll
         for (int c = 0; c < F::NCB; ++c) {
             const int f = wave + NW * c;
@@ -344,7 +338,6 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
         }
         __syncthreads();
         STAMP(4);
-        if (NPF && BNECK_PAIR_PREFAT == 0) a1_loads(tile_at(it + nslots), 0, NPF);
 
         // ---- B2 + B3: the tile's rows, residual y from LDS, whole-line stores (bneck_kernels.hip LINES): rows
         // 2u / 2u + 1 of pixels col and col ^ 8 traded across lanes 8 apart, then line u of each pixel
@@ -388,17 +381,12 @@ __global__ void __launch_bounds__(NW * 64, 1) bneck_pair_kernel(const BneckPairA
 }
 
 // ---- the built form: tile height and waves by measurement
-#ifndef BNECK_PAIR_TH
-#define BNECK_PAIR_TH 12
-#endif
-#ifndef BNECK_PAIR_NW
-#define BNECK_PAIR_NW 16
-#endif
-using PairBuilt = PairForm<BNECK_PAIR_TH, BNECK_PAIR_NW>;
-static const void *pair_fun() { return (const void *)bneck_pair_kernel<BNECK_PAIR_TH, BNECK_PAIR_NW>; }
+constexpr int PAIR_TH = 12, PAIR_NW = 16;
+using PairBuilt = PairForm<PAIR_TH, PAIR_NW>;
+static const void *pair_fun() { return (const void *)bneck_pair_kernel<PAIR_TH, PAIR_NW>; }
 
 void bneck_pair_shape(int &th, int &tw, int &threads, size_t &lds) {
-    th = BNECK_PAIR_TH; tw = PairBuilt::TW; threads = PairBuilt::NT; lds = PairBuilt::LDS_BYTES;
+    th = PAIR_TH; tw = PairBuilt::TW; threads = PairBuilt::NT; lds = PairBuilt::LDS_BYTES;
 }
 
 hipError_t launch_bneck_pair(const Knobs &k, const BneckPairArgs &a, hipStream_t s) {

@@ -175,12 +175,12 @@ struct BneckArgs {
     uint32_t x_bytes;                                 // bytes of x (== out)
     int slopes_le1;                                   // every PReLU slope <= 1: max(v, s*v)
     // downsampling blocks (cin > 0 in launch_bneck): x is unused; xin = block input (B, 2H, 2W, cin),
-    // pool = scratch for the pooled main branch (B, H, W, cin), idx_out = its window positions
+    // idx_out = the window positions of the pooled main branch (the pooled values stay in registers)
     const void *xin;
-    void *pool;
+    void *pool;                                       // unused (kept: without it the down forms spill more SGPRs)
     uint8_t *idx_out;
     int idxCS;
-    uint32_t xin_bytes, pool_bytes, idx_bytes;
+    uint32_t xin_bytes, pool_bytes, idx_bytes;        // pool_bytes: unused, as pool
     RangeArgs rg;        // fp32 mode: sw = {w1, w2, w2b, w3}; n / c: t0, t1 (asym: t1a), t1 (asym)
     unsigned long long *span;   // launch span (bugseg_debug_set_spans), or null
     // the class layer fused into the C = 16 block (launch_bneck_cls; out is not written): its packed weights

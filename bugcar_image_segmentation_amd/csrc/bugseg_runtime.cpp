@@ -228,10 +228,7 @@ struct WinPlan {
 // i and i + 1 as one paired launch where the overlay has a pair (i, i + 1) and both lie in the forward's op range.
 // pair_firsts and pair_actions are the whole rule: build_pairs turns them into finished launches when the plan is
 // built, enet_forward switches on the actions of its op range, and bugseg_debug_pair_walk shows the same two to the
-// tests. BNECK_PAIR64 = 0 builds a library without it (A/B builds).
-#ifndef BNECK_PAIR64
-#define BNECK_PAIR64 1
-#endif
+// tests. A forced tile variant (BUGSEG_BNECK_VARIANT, BUGSEG_BNECK_VARIANT_C64) or BUGSEG_NO_FUSE=1 plans without it.
 // What the walk needs of an op: ok — a fused fp32 C = 64 regular d = 1 bottleneck on an h x w grid in an untransposed
 // form, before the row-windowed decoder ops; in, out — which of the arena's two activation buffers it reads and
 // writes (0, 1; -1: another buffer).
@@ -1117,10 +1114,11 @@ struct Walker {
         if (!fill) szIdx[bi] = (size_t)B * so.H * so.W * idxCS;
         const int dv = cur.C == b.attrs[0] ? fusable_down(ctx, b, *ids) : -1;
         const Shape sp{so.H, so.W, idxCS};
+        // (sizes T for the pooled-values scratch the fused form had; kept so that the arena's size does not move)
         if (dv >= 0) szT = std::max(szT, tbytes(sp));
         if (fill && dv >= 0) {
             // one launch: 2x2 projection + 3x3 + expansion + pooled main branch (pooled values
-            // through the T[0] scratch, read back as the residual)
+            // in registers, as the residual)
             Op op;
             BneckLaunch &l = op.l.emplace<BneckLaunch>();
             l.C = b.attrs[1]; l.var = dv; l.cin = b.attrs[0];
@@ -1134,8 +1132,6 @@ struct Walker {
             wire_bneck(q, P(0), P(1), P(1), P(2));
             q.xin = curp;                             // (x_bytes: build_plan, as for every fused bottleneck)
             q.xin_bytes = clamp31(tbytes(cur));
-            q.pool = T[0];
-            q.pool_bytes = clamp31(tbytes(sp));
             q.idx_out = idx[bi]; q.idxCS = idxCS;
             q.idx_bytes = clamp31((size_t)B * so.H * so.W * idxCS);
             range_io(q.rg, curp, dst);
@@ -1143,7 +1139,7 @@ struct Walker {
             double wb, fl;
             sums(3, px, wb, fl);
             op.flops = fl;
-            // x read once, out + indices written once (the pooled scratch round trip is L2)
+            // x read once, out + indices written once
             op.bytes = (double)tbytes(cur) + (double)tbytes(so) + px * idxCS + wb;
             op.layer_bytes = (double)tbytes(cur) * 2 + 2.0 * (tbytes(s1) + tbytes(s2)) + (double)tbytes(so) +
                              px * idxCS + wb;
@@ -1386,7 +1382,7 @@ void build_pairs(bugseg_ctx *ctx, unsigned char *const X[2], unsigned char *spar
     pl.pairs.clear();
     pl.firsts.clear();
     const Knobs &k = ctx->knobs;
-    if (BNECK_PAIR64 && ctx->prec == PREC_F32 && !k.no_fuse && k.bneck_variant < 0 && k.bneck_variant_c64 < 0) {
+    if (ctx->prec == PREC_F32 && !k.no_fuse && k.bneck_variant < 0 && k.bneck_variant_c64 < 0) {
         auto buf = [&](const void *p) { return p == X[0] ? 0 : p == X[1] ? 1 : -1; };
         std::vector<PairCand> c((size_t)n);
         for (int i = 0; i < n - WIN_OPS; ++i) {
@@ -1472,7 +1468,7 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
     pl.ops = std::move(w.ops);
     int issued = 0;
     for (Op &op : pl.ops) { op.pos = issued; issued += op.launches; }
-    // the spare buffer: T[1] (the fused plan's launches use T[0] alone: the down blocks' pooled scratch)
+    // the spare buffer: T[1] (the fused plan's launches use none of the T buffers)
     build_pairs(ctx, w.X, w.T[1], al(w.szT));
     pl.cls_ok = false;
     pl.cls_on = false;

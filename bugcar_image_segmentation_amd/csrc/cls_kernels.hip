@@ -29,24 +29,12 @@ namespace bugseg {
 #ifndef CLS_ABL
 #define CLS_ABL 0
 #endif
-#ifndef CLS_AUX
-#define CLS_AUX 0          // class-map store policy (A/B knob; the BEV rasteriser reads them next)
-#endif
-#ifndef CLS_SPLIT1
-#define CLS_SPLIT1 0       // fp32: each tap's operand split once per group for both blocks (A/B knob; round 6, with
-                           // VGPR-form MFMAs: 109 -> 113 us per 64-frame launch — the up-front splits delay the MFMAs)
-#endif
-#ifndef CLS_BIAS_REG
-#define CLS_BIAS_REG 1
-#endif
+constexpr int CLS_OCC_F32 = 1;   // fp32: waves per SIMD the build is held to (3: 28 VGPRs spilled, 109 -> 257 us)
 // (Round 4 measured a low-register form — weights from LDS, the two blocks one after the other, 7 waves
 // per SIMD instead of 4 — at 37.5 vs 34.7 us per 32-frame launch (fp16) and 75.3 vs 74.7 (fp32): the
 // class layer is not occupancy-bound. Removed.)
 // LK: the class map's group-max argmax (cls_common.h cls_argmax)
 template <typename T, bool LOGITS, int LK = 0>
-#ifndef CLS_OCC_F32
-#define CLS_OCC_F32 1      // fp32: waves per SIMD the build is held to (A/B knob; 3: 28 VGPRs spilled, 109 -> 257 us)
-#endif
 __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_kernel(const ConvArgs a) {
     span_enter(a.span);
     constexpr int CLS_TAPS = 4;
@@ -85,7 +73,7 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
 
     // The accumulators start at the bias. pack_tconv (bugseg_runtime.cpp) writes the same per-class bias
     // into all four phases' rows, so sbias[(2b + h) * 16 + k] is one 16-vector for every block and lane
-    // half: CLS_BIAS_REG holds it in 16 loop-long registers instead of reading it from LDS per group.
+    // half: BREG holds it in 16 loop-long registers instead of reading it from LDS per group.
     auto ldbias = [&](int b) {
         // (the opaque offset keeps the compiler from hoisting these reads out of the group loop)
         int boff = (2 * b + h) * 16;
@@ -100,7 +88,7 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
         return v;
     };
     // (2-byte class maps only: the logits form and fp32 have no registers to spare)
-    constexpr bool BREG = CLS_BIAS_REG && !LOGITS && sizeof(T) == 2;
+    constexpr bool BREG = !LOGITS && sizeof(T) == 2;
     f32x16 bvec;
     if constexpr (BREG) bvec = ldbias(0);
     // fp32 mode range scaling (bugseg_internal.h RangeArgs): the input measured by its producer, the
@@ -193,18 +181,6 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
         // lets the waits before the MFMAs name only this group's loads (a conditional prefetch
         // made the compiler wait vmcnt(3), i.e. for the next group's first load as well).
         load(grp_of(k + nw), nxt, qn);
-        // CLS_SPLIT1 (fp32): the four taps' hi / lo parts, scaled first when the launch scales (the same
-        // parts the per-block split would make: bit-identical)
-        constexpr bool S1 = F32 && CLS_SPLIT1;
-        f16x8 sxh[S1 ? CLS_TAPS : 1], sxl[S1 ? CLS_TAPS : 1];
-        if constexpr (S1) {
-#pragma unroll
-            for (int s = 0; s < CLS_TAPS; ++s) {
-                RawF xq = reinterpret_cast<const RawF &>(cur[s]);
-                if (scl) mul8(xq, xm);
-                split_f16(xq, sxh[s], sxl[s]);
-            }
-        }
         // per block: accumulators from the bias, the taps' MFMAs, (parity runs) the logits, and the
         // argmax over this lane's classes = the sequential strict > scan from -inf of tf.math.argmax
         // (models.py:55): the maximum (v_max ignores NaN), then its first index; no class equal to the
@@ -212,10 +188,6 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
         // first, then the two argmax scans interleaved
         auto taps = [&](int b, f32x16 &acc, auto sc) {
             auto tap = [&](int s) {
-                if constexpr (S1) {
-                    if constexpr (F32) mma32s(acc, reinterpret_cast<const RawS &>(wr[b][s]), sxh[s], sxl[s]);
-                    return;
-                }
                 Raw xq = cur[s];
                 if constexpr (decltype(sc)::value) mul8(reinterpret_cast<RawF &>(xq), xm);
                 mma32(acc, wr[b][s], xq);
@@ -266,7 +238,7 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? 4 : CLS_OCC_F32) cls_ker
             // (a row window's first / last output row may be the other row of its input row: not written)
             const bool wr = q.ok && 2 * q.y + h >= a.orow0 && 2 * q.y + h < a.orow1;
             if (!(CLS_ABL & 4) || c0 == 77)
-                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(c0 | (c1 << 8)), rcls, wr ? (int)o : (int)OOB, 0, CLS_AUX);
+                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(c0 | (c1 << 8)), rcls, wr ? (int)o : (int)OOB, 0, 0);
         }
     };
     Raw xa[CLS_TAPS], xb[CLS_TAPS];

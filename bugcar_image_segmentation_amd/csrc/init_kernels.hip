@@ -26,11 +26,6 @@
 #include <type_traits>
 
 #include "bugseg_internal.h"
-// output stores: sc1 write-through (OUT_AUX_SEL, as bneck_kernels.hip): measured 44.9-46.9 -> 43.7-44.2
-// us, the 2-stream bench unchanged
-#ifndef BUGSEG_OUT_AUX
-#define BUGSEG_OUT_AUX -1
-#endif
 #include "mfma_common.h"
 
 namespace bugseg {
@@ -41,25 +36,11 @@ namespace bugseg {
 #define INIT_ABL 0
 #endif
 
-#ifndef INIT_POOL_PK
-#define INIT_POOL_PK 1
-#endif
 constexpr int IT_H = 8, IT_W = 32;                        // output tile
 constexpr int IP_H = 2 * IT_H + 1, IP_W = 2 * IT_W + 1;   // input patch (pixels)
 constexpr int IP_RS = IP_W * 3 + 1;                       // LDS patch row stride (elements, even)
 constexpr int IP_PATCH = (IP_H * IP_RS + 7) & ~7;           // one patch buffer (elements, 16-B multiple)
-#ifndef INIT_NT_2B
-#define INIT_NT_2B 0      // 2-byte output stores non-temporal (A/B knob)
-#endif
-#ifndef INIT_NT_F32
-#define INIT_NT_F32 1     // fp32 output stores non-temporal: the down block that reads them 11 us faster, this 2 us slower (round 5)
-#endif
-#ifndef INIT_DB
-#define INIT_DB 1
-#endif
-#ifndef INIT_OCC2
-#define INIT_OCC2 6                                          // 2-byte storage: waves per SIMD the registers allow
-#endif
+constexpr int INIT_OCC2 = 6;                              // 2-byte storage: waves per SIMD the registers allow
 
 // k -> (window row, element of the row's 9-run), the B/A fragment K order described above
 __device__ __forceinline__ void init_k(int kq, int j, int &dy, int &e) {
@@ -70,9 +51,9 @@ __device__ __forceinline__ void init_k(int kq, int j, int &dy, int &e) {
 template <typename T, bool BGR>
 __global__ void __launch_bounds__(256, sizeof(T) == 2 ? INIT_OCC2 : 1) init_kernel(const ConvArgs a) {   // (fp16 with the packed pool took 82 registers: 5 waves per SIMD)
     span_enter(a.span);
-    // INIT_DB: two patch buffers — the next tile's patch is stored while this one is computed, one
-    // barrier per tile instead of two
-    __shared__ __attribute__((aligned(16))) T patch_buf[(INIT_DB ? 2 : 1) * IP_PATCH];
+    // two patch buffers: the next tile's patch is stored while this one is computed, one barrier per tile
+    // instead of two
+    __shared__ __attribute__((aligned(16))) T patch_buf[2 * IP_PATCH];
     __shared__ float lut[BGR ? 3 * 256 : 1];
     using Raw = typename Tr<T>::Raw;
     using WRaw = typename WTr<T>::Raw;   // weight operand (fp32 mode: split-f16 parts)
@@ -180,13 +161,8 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? INIT_OCC2 : 1) init_kern
             else raw[r] = __builtin_amdgcn_raw_buffer_load_b32(rin, off, 0, 0);
         }
     };
-    // INIT_PF: the next tile's patch loads are issued as soon as this tile's patch is in LDS, so they
-    // fly during this tile's MFMA / pool / stores (the raw registers are free by then). Measured
-    // (round 3, fp16, B = 32): 44.5 -> 43.6 us per launch (68 VGPRs, 6 waves per SIMD; the grid is
-    // the resident workgroup count)
-#ifndef INIT_PF
-#define INIT_PF 1
-#endif
+    // (the next tile's patch loads are issued as soon as this tile's patch is in LDS, so they fly during
+    // this tile's MFMA / pool / stores: the raw registers are free by then)
     // this thread's patch column of tile t, from the raw bytes, into patch buffer dst
     // (rows outside the frame exist only in the first and last tile rows: a uniform fast path)
     auto store_patch = [&](const Tile &t, T *dst) {
@@ -212,13 +188,11 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? INIT_OCC2 : 1) init_kern
         else store_rows(std::false_type());
     };
     if (walk(slot) >= 0) load_raw(geom(walk(slot)));
-    if constexpr (INIT_DB) {
-        // prologue: the first tile's patch into buffer 0, the second tile's loads in flight
-        __syncthreads();   // lut staged
-        if (walk(slot) >= 0) {
-            store_patch(geom(walk(slot)), patch_buf);
-            if (walk(slot + nslots) >= 0) load_raw(geom(walk(slot + nslots)));
-        }
+    // prologue: the first tile's patch into buffer 0, the second tile's loads in flight
+    __syncthreads();   // lut staged
+    if (walk(slot) >= 0) {
+        store_patch(geom(walk(slot)), patch_buf);
+        if (walk(slot + nslots) >= 0) load_raw(geom(walk(slot + nslots)));
     }
     int pbuf = 0;
     for (int it = slot; it < CH; it += nslots) {
@@ -227,28 +201,17 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? INIT_OCC2 : 1) init_kern
         const Tile tg = geom(tile);
         const int n = tg.n, ty0 = tg.ty0, tx0 = tg.tx0, iy0 = tg.iy0, ix0 = tg.ix0;
         const T *patch = patch_buf + pbuf * IP_PATCH;
-        if constexpr (INIT_DB) {
-            __syncthreads();   // this tile's patch complete; the other buffer's last reader (the previous tile) done
-            const int tn = walk(it + nslots);   // (the walk's next tile: same XCD group, next slot round)
-            if (tn >= 0) {
-                store_patch(geom(tn), patch_buf + (pbuf ^ 1) * IP_PATCH);
-                if (walk(it + 2 * nslots) >= 0) load_raw(geom(walk(it + 2 * nslots)));
-            }
-            pbuf ^= 1;
-        } else {
-            if (!INIT_PF && it != slot) load_raw(tg);
-            __syncthreads();   // lut staged / previous tile done with the patch
-            store_patch(tg, patch_buf);
-            if (INIT_PF) {
-                const int tn = walk(it + nslots);   // (the walk's next tile: same XCD group, next slot round)
-                if (tn >= 0) load_raw(geom(tn));
-            }
-            __syncthreads();
+        __syncthreads();   // this tile's patch complete; the other buffer's last reader (the previous tile) done
+        const int tn = walk(it + nslots);   // (the walk's next tile: same XCD group, next slot round)
+        if (tn >= 0) {
+            store_patch(geom(tn), patch_buf + (pbuf ^ 1) * IP_PATCH);
+            if (walk(it + 2 * nslots) >= 0) load_raw(geom(walk(it + 2 * nslots)));
         }
+        pbuf ^= 1;
 
         // ---- pool maxima: lane (col, kq) -> pixel col of fragment f = kq (row 2*wave + (f>>1))
         float pm[3];
-        if (__is_same(T, _Float16) && INIT_POOL_PK && !a.pool_scan) {
+        if (__is_same(T, _Float16) && !a.pool_scan) {
             // fp16 (round 4): a window row's 9 elements (3 pixels x 3 channels) as 5 aligned dwords
             // (ds_read_b32; the row starts 4-B aligned) and the maxima as packed f16 pairs — (ch0, ch1)
             // from dwords 0, 1:2 (shifted by one element) and 3, ch2 from halves of dwords 1, 2 and 4.
@@ -354,10 +317,11 @@ __global__ void __launch_bounds__(256, sizeof(T) == 2 ? INIT_OCC2 : 1) init_kern
                 if (ok) rng_acc4(amo, v);
             }
             const uint32_t off = ok ? (uint32_t)(((n * a.Hg + oy) * a.Wg + ox) * a.outC + c0) * (uint32_t)sizeof(T) : OOB;
+            // output store policy (mfma_common.h bst16o): sc1 write-through in 2-byte storage, non-temporal in fp32
             if constexpr (sizeof(T) == 2) {
-                bst8o<INIT_NT_2B ? 2 : OUT_AUX_SEL(16)>(rout, off, pack4<T>(v));
+                bst8o<16>(rout, off, pack4<T>(v));
             } else {
-                bst16o<INIT_NT_F32 ? 2 : OUT_AUX_SEL(16)>(rout, off, __builtin_bit_cast(uint4, v));
+                bst16o<2>(rout, off, __builtin_bit_cast(uint4, v));
             }
         }
     }

@@ -26,18 +26,16 @@
 
 namespace bugseg {
 
-// threads per workgroup: the 2-byte CIN = 128 form (46 KB of weights in LDS: 3 workgroups per CU) runs
-// 8 waves per workgroup (UP_NT128), so the weights staged once per CU serve twice the waves
-#ifndef UP_NT128
-#define UP_NT128 512
-#endif
 // One compile-time description per form, shared by the kernel and its launcher: the workgroup size, the rows
 // of the three GEMMs and the LDS map (byte offsets of the weights of the three GEMMs and of their per-row
 // constants, and the size of the dynamic allocation).
 template <typename T, int CIN, int I, int COUT>
 struct UpForm {
     static constexpr int ES = (int)sizeof(T);
-    static constexpr int NT = ES == 2 && CIN >= 128 ? UP_NT128 : 256;
+    // threads per workgroup: the 2-byte CIN = 128 form (46 KB of weights in LDS: 3 workgroups per CU) runs
+    // 8 waves per workgroup, so the weights staged once per CU serve twice the waves
+    static constexpr int NT = ES == 2 && CIN >= 128 ? 512 : 256;
+    static constexpr int OCC = ES == 2 ? (CIN >= 128 ? 4 : 3) : 1;   // waves per SIMD the build is held to
     static constexpr int NR1 = (COUT + I) / 16;       // GEMM 1 rows: main then e1
     static constexpr int NR2 = 4 * I / 16;            // tconv rows (4 phases)
     static constexpr int NR3 = COUT / 16;             // expansion rows
@@ -61,27 +59,15 @@ struct UpForm {
 };
 
 template <typename T, int CIN, int I, int COUT>
-__global__ void __launch_bounds__((UpForm<T, CIN, I, COUT>::NT), (sizeof(T) == 2 ? (CIN >= 128 ? (UP_NT128 == 512 ? 4 : 2) : 3) : 1)) up_kernel(const UpArgs a) {
+__global__ void __launch_bounds__((UpForm<T, CIN, I, COUT>::NT), (UpForm<T, CIN, I, COUT>::OCC)) up_kernel(const UpArgs a) {
     span_enter(a.span);
     using Raw = typename Tr<T>::Raw;
     using WRaw = typename WTr<T>::Raw;   // weight operand (fp32 mode: split-f16 parts)
     using F = UpForm<T, CIN, I, COUT>;
     constexpr int ES = F::ES;
-// fp32, the 128 -> 64 block: non-temporal output stores (round 5, B = 64, one stream: the bottleneck that
-// reads them 13 us faster, this launch 7 us slower; the 64 -> 16 block lost 26 us for 7, so it keeps
-// the default) — A/B knob UP_NT_F32 (0 off, 1 that block, 2 both)
-#ifndef UP_NT_F32
-#define UP_NT_F32 1
-#endif
-#ifndef UP_AUX_F32_LOW
-#define UP_AUX_F32_LOW 0       // fp32 64 -> 16 block's policy (A/B knob)
-#endif
-#ifndef UP_NT_2B
-#define UP_NT_2B 0
-#endif
-    constexpr int OAUX = (sizeof(T) == 4 && (UP_NT_F32 == 2 || (UP_NT_F32 == 1 && CIN >= 128))) || (sizeof(T) == 2 && UP_NT_2B && CIN >= 128) ? 2
-                       : sizeof(T) == 4 && CIN < 128 ? UP_AUX_F32_LOW
-                       : OUT_AUX_SEL(CIN >= 128 ? 16 : 0);   // sc1 output stores (mfma_common.h)
+    // output store policy (mfma_common.h bst16o): the fp32 128 -> 64 block streams its output non-temporally,
+    // every other form stores with the default policy (DESIGN 6.24 has the measurements)
+    constexpr int OAUX = ES == 4 && CIN >= 128 ? 2 : 0;
     constexpr int NR1 = F::NR1, NR2 = F::NR2, NR3 = F::NR3;   // rows of GEMM 1 (main then e1), the tconv, the expansion
     constexpr int NM = COUT / 16, NE = I / 16;        // row fragments of main / e1 (per tconv phase)
     constexpr int KS1 = CIN / 32;                     // GEMM 1 k-steps
@@ -94,16 +80,7 @@ __global__ void __launch_bounds__((UpForm<T, CIN, I, COUT>::NT), (sizeof(T) == 2
 // 2 t + 1 of pixels col and col ^ 8 are traded across lanes 8 apart (one DPP row rotation per dword),
 // so each of the two stores per t writes the whole line t of 8 pixels (lanes col and col ^ 8: the
 // line's two 64-B halves). Same values, other lanes: bit-identical output
-#ifndef UP_F32_LINES
-#define UP_F32_LINES 1
-#endif
-#ifndef UP_F32_LINES16
-#define UP_F32_LINES16 0    // the C16 block's phase-pair form: measured slower (round 6, A/B: up C16 122 -> 134 us per 64-frame launch)
-#endif
-    constexpr bool LINES = ES == 4 && NR3 % 2 == 0 && UP_F32_LINES;
-    // COUT = 16 (a pixel = 64 B): the two column phases of an output row are adjacent pixels, one line —
-    // the even phase's quad waits in registers and is traded and stored with the odd one's
-    constexpr bool LINES16 = ES == 4 && NR3 == 1 && UP_F32_LINES16;
+    constexpr bool LINES = ES == 4 && NR3 % 2 == 0;
     // bias placement of the unfused launches (bias_in_acc of their row counts): the main and e1
     // 1x1s both accumulate from the bias (the host plans this kernel only then), the tconv and the
     // expansion as their own row counts say
@@ -254,7 +231,7 @@ __global__ void __launch_bounds__((UpForm<T, CIN, I, COUT>::NT), (sizeof(T) == 2
         // col - 8 and col: the output base of the fragment's other pixel f * 16 + (col ^ 8)
         uint32_t obase_o = 0u;
         bool pv_o = false;
-        if constexpr (LINES || LINES16) {
+        if constexpr (LINES) {
             const int po = f * 16 + (col ^ 8);
             pv_o = po < a.M;
             const uint32_t ppo = pv_o ? (uint32_t)po : 0u;
@@ -262,7 +239,6 @@ __global__ void __launch_bounds__((UpForm<T, CIN, I, COUT>::NT), (sizeof(T) == 2
             const int yo = (int)fdiv((uint32_t)rro, a.mW, a.sW), xo = rro - yo * a.w;
             obase_o = pv_o ? (uint32_t)((no * 2 * a.h + 2 * yo) * (2 * a.w) + 2 * xo) : 0u;
         }
-        float4 ev_prev = make_float4(0.f, 0.f, 0.f, 0.f);   // LINES16: the even phase's quad
         // (not unrolled: one phase's weight fragments live at a time)
 #pragma unroll 1
         for (int ph = 0; ph < 4; ++ph) {
@@ -315,28 +291,6 @@ __global__ void __launch_bounds__((UpForm<T, CIN, I, COUT>::NT), (sizeof(T) == 2
                     pl16swap(x1, y1);
                     const int ch = (2 * t + (kq & 1)) * 16 + 8 * (kq >> 1);
                     bst16o<OAUX>(ro, pv ? (opix * COUT + ch) * ES : OOB, make_uint4(x0, x1, y0, y1));
-                }
-            } else if constexpr (LINES16) {
-                const float4 v = ep3(0);
-                rng_acc4(amo, v);
-                if ((ph & 1) == 0) {
-                    ev_prev = v;
-                } else {
-                    // line of input pixel p: output pixels (2y + ph / 2, 2x) and (.., 2x + 1), 32 channels
-                    const bool lo8 = col < 8;
-                    const uint32_t phe = pho - 1u;             // the even pixel of this row
-                    const uint32_t pa = (lo8 ? obase : obase_o) + phe, pb = (lo8 ? obase_o : obase) + phe;
-                    const bool va = lo8 ? pv : pv_o, vb = lo8 ? pv_o : pv;
-                    const uint4 u0 = __builtin_bit_cast(uint4, ev_prev), u1 = __builtin_bit_cast(uint4, v);
-                    const uint4 xs = lo8 ? u1 : u0;
-                    uint4 ys;
-                    ys.x = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xs.x, 0x128, 0xf, 0xf, false);
-                    ys.y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xs.y, 0x128, 0xf, 0xf, false);
-                    ys.z = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xs.z, 0x128, 0xf, 0xf, false);
-                    ys.w = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xs.w, 0x128, 0xf, 0xf, false);
-                    const int ch = (lo8 ? 0 : 16) + kq * 4;   // channel 16 + c of the even pixel = c of the odd one
-                    bst16o<OAUX>(ro, va ? (pa * COUT + ch) * ES : OOB, lo8 ? u0 : ys);
-                    bst16o<OAUX>(ro, vb ? (pb * COUT + ch) * ES : OOB, lo8 ? ys : u1);
                 }
             } else if constexpr (LINES) {
                 const bool lo8 = col < 8;

@@ -1,4 +1,4 @@
-"""Per-layer SQ counter table from rocprofv3 --pmc runs of scripts/bneck_ablate.py (one variant).
+"""Per-layer SQ counter table from rocprofv3 --pmc runs of scripts/probe_forward.py.
 
 Dispatches are grouped into forwards at each initial-block launch and averaged per position, like
 layer_times.py. Prints per-wave instruction counts and wait fractions per layer.
