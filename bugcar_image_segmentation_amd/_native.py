@@ -35,6 +35,7 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_bev_warp_image", "bugseg_hough_trig", "bugseg_hough_workspace_bytes", "bugseg_hough_lines",
             "bugseg_debug_hough_stage",
             "bugseg_quad_workspace_bytes", "bugseg_find_quad", "bugseg_quad_moments", "bugseg_debug_quad_stage",
+            "bugseg_map_fuse",
             "bugseg_dl_create", "bugseg_dl_destroy", "bugseg_dl_load_weights", "bugseg_dl_set_plan",
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
@@ -79,6 +80,13 @@ class QuadParams(ctypes.Structure):
     """bugseg_quad_params: calibration.quad_params builds and checks them."""
     _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("channels", ctypes.c_int), ("bright", ctypes.c_int),
                 ("threshold", ctypes.c_int), ("min_area", ctypes.c_int), ("band", ctypes.c_int * 2)]
+
+
+class MapParams(ctypes.Structure):
+    """bugseg_map_params: mapping.map_params builds and checks them."""
+    _fields_ = [("map_rows", ctypes.c_int), ("map_cols", ctypes.c_int), ("grid_rows", ctypes.c_int),
+                ("grid_cols", ctypes.c_int), ("ros_layout", ctypes.c_int), ("l_occ", ctypes.c_int),
+                ("l_free", ctypes.c_int), ("l_min", ctypes.c_int), ("l_max", ctypes.c_int), ("cull", ctypes.c_int)]
 
 
 class ConfusionParams(ctypes.Structure):
@@ -160,6 +168,7 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_find_quad": (i, [vp, vp, i, ctypes.POINTER(QuadParams), vp, vp, vp, vp, vp, vp, vp, sz, vp]),
             "bugseg_quad_moments": (i, [vp, vp, i, ctypes.POINTER(QuadParams), i, vp, vp, vp, sz, vp]),
             "bugseg_debug_quad_stage": (i, [vp, vp, i, ctypes.POINTER(QuadParams), i, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+            "bugseg_map_fuse": (i, [vp, vp, i, ctypes.POINTER(MapParams), vp, vp, vp, vp, vp]),
             "bugseg_dl_create": (i, [i, i, ctypes.POINTER(vp)]),
             "bugseg_dl_destroy": (i, [vp]),
             "bugseg_dl_load_weights": (i, [vp, vp, sz]),
@@ -523,6 +532,15 @@ class Context:
         ptr = lambda t: 0 if t is None else t.data_ptr()
         self._raise_any(self.lib.bugseg_quad_moments(self.h, ptr(frames), B, ctypes.byref(params), int(band), ptr(corners2),
                                                      ptr(moments), *w, sh))
+
+    def map_fuse(self, grids, B, params: MapParams, record, state, lut, out, stream=None):
+        """bugseg_map_fuse: (B, h, w) int8 grids and the update record (int64 words, mapping.pose_record) -> the
+        int16 torus `state` (Hm, Wm) and the int8 payload `out` (Hm, Wm). One launch, no workspace. Any refusal, a
+        bad argument included, raises BugsegError and launches nothing."""
+        sh, _, _ = self._stream_ws(out if out is not None else state, stream)
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        self._raise_any(self.lib.bugseg_map_fuse(self.h, ptr(grids), B, ctypes.byref(params), ptr(record), ptr(state),
+                                                 ptr(lut), ptr(out), sh))
 
     def plan_info(self, B, H, W, out_kind, bgr_input=False):
         """-> (launches, per-layer algorithmic bytes, plan compulsory bytes, flops) of one forward."""

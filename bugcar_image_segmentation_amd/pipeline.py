@@ -317,6 +317,18 @@ class OccupancyPipeline:
         from .hostio import HostStream
         return HostStream(self, batch, frame_hw=frame_hw, depth=depth, graph=graph)
 
+    def local_map(self, size_cells, **kw):
+        """A mapping.LocalMap for this pipeline's grids: their cell size, shape and layout, on the
+        model's device; size_cells = (Hm, Wm) and the keywords are LocalMap's. `map.update(pipe.run(frames), poses)`
+        fuses a batch, and map.fuse can be captured in one graph with run. Refused for the binary laserscan output,
+        whose (2, B, ...) pair is not a batch of grids."""
+        p = self._params()
+        if self.binary and p.laserscan:
+            raise ValueError("local_map needs a batch of grids: the binary laserscan output is the reference's pair")
+        from .mapping import LocalMap
+        kw.setdefault("device", self._ctxs[0].device)
+        return LocalMap(size_cells, self.grid[2], (p.occ_h, p.occ_w), ros_layout=self.ros_layout, **kw)
+
     def run_host(self, frames_np) -> np.ndarray:
         """One batch of host frames, (B, H0, W0, 3) uint8, -> its grids as an owned int8 array, through
         a depth-1 HostStream kept per (B, H0, W0) (rebuilt when the calibration or the grid changed,

@@ -426,6 +426,42 @@ int bugseg_debug_quad_stage(bugseg_ctx *ctx, const uint8_t *frames_dev, int B, c
                             int32_t *corners_dev, int64_t *moments_dev, void *workspace_dev, size_t workspace_bytes,
                             void *stream);
 
+/* The rolling local map: B occupancy grids, each taken at its own pose, fused in time order into a
+ * world-aligned log-odds map that scrolls with the vehicle. Integers only on the device; mapping.LocalMap owns the
+ * buffers and mapping.pose_record builds the record.
+ *   map_rows, map_cols    the window, Hm x Wm cells; window cell (i, j) is world cell (wx0 + j, wy0 + i), so the
+ *                         window row by row is nav_msgs/OccupancyGrid data order
+ *   grid_rows, grid_cols  a grid, h x w cells (forward x left), stored (h, w) with the base point at the bottom
+ *                         centre, or with ros_layout non-zero (w, h) as G[::-1, ::-1].T
+ *   l_occ, l_free         what a cell of value 100 adds and a cell of value 0 takes away; any other value is no
+ *                         observation
+ *   l_min, l_max          the clamp; the look-up table has l_max - l_min + 1 entries
+ *   cull                  non-zero: a workgroup leaves out the frames whose footprint cannot reach its tile (the
+ *                         result is the same; bench_local_map.py measures both)
+ * Limits: every side 1..4096, B 1..4096, -32768 < l_min < 0 < l_max <= 32767, l_occ and l_free at least 1. */
+typedef struct { int map_rows, map_cols, grid_rows, grid_cols, ros_layout, l_occ, l_free, l_min, l_max, cull; } bugseg_map_params;
+
+#define BUGSEG_MAP_UNOBSERVED (-32768)  /* the state of a cell that was never observed */
+/* The update record, int64 words in device memory: a header, then one frame record per grid.
+ *   header  [0] wx0, [1] wy0: the window's origin in world cells; [2], [3]: the origin the state was last written
+ *           with; [4] non-zero: the map is fresh and nothing stored is kept; [5..7] zero
+ *   frame   C, S, Ox, Oy: forward = (C j + S i + Ox) >> 16 and left = (-S j + C i + Oy) / 2^16 cells at window cell
+ *           (i, j). C = S = 0, which no yaw gives, marks a frame without a pose: it is skipped */
+#define BUGSEG_MAP_RECORD_HEADER 8
+#define BUGSEG_MAP_RECORD_FRAME 4
+
+/* grids_dev int8 (B, h, w) [or (B, w, h)] and record_dev (8 + 4 B int64 words) -> state_dev, int16 (Hm, Wm) stored as
+ * a torus (world cell (X, Y) lives in slot (Y mod Hm, X mod Wm), floor-mod), and out_dev, int8 (Hm, Wm) in window
+ * order: -1 for a cell never observed, else lut_dev[L - l_min]. A window cell keeps its stored state when the map
+ * is not fresh and its world cell lay in the previous window, and starts unobserved otherwise, whatever the slot
+ * holds: the state needs no memset. The frames are fused in the order 0..B-1 (the clamp makes the order matter).
+ * One launch, no workspace; the call never synchronises, allocates nothing and may be captured into a graph, where
+ * it reads whatever the record holds when the graph runs. BUGSEG_EINVAL, and nothing is launched: a NULL argument,
+ * parameters outside the limits above, record_dev not 8-byte or state_dev not 2-byte aligned, a written buffer
+ * that overlaps another buffer. */
+int bugseg_map_fuse(bugseg_ctx *ctx, const int8_t *grids_dev, int B, const bugseg_map_params *p, const int64_t *record_dev,
+                    int16_t *state_dev, const int8_t *lut_dev, int8_t *out_dev, void *stream);
+
 /* Evaluation of class maps: the confusion matrix of predictions against labels, both u8 maps
  * in device memory. A label pixel (y, x) of a gt_rows x gt_cols label map is compared with the prediction at
  * sy = min(y * pred_rows / gt_rows, pred_rows - 1), sx = min(x * pred_cols / gt_cols, pred_cols - 1), exact
