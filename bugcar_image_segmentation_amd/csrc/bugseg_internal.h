@@ -314,7 +314,7 @@ struct BevArgs {
     // variant 0 leaves `out` to the final laserscan kernel
     int laserscan;
     uint8_t *cells;      // (B, occ_h, occ_w)
-    // polar tables (host-built, bugseg_runtime.cpp polar_tables) and per-row minima
+    // polar tables (host-built, bev_runtime.cpp polar_tables) and per-row minima
     const int32_t *fmap; // (ph, pw): source cell x | y << 16, or -1
     const int32_t *imap; // (occ_h, occ_w): polar rho | row << 16, or -1
     int pw, ph;
@@ -326,7 +326,7 @@ struct BevArgs {
     // built once per calibration by launch_bev_table and shared by every frame
     uint4 *wtab;
     // band-staged form: the (band, row part) work items (bev_items_offset in the table), far bands first;
-    // set by the host from the band records after the table build (bugseg_runtime.cpp bev_occgrid)
+    // set by the host from the band records after the table build (bev_runtime.cpp bev_table)
     int nitems;
 };
 hipError_t launch_bev(const Knobs &k, const BevArgs &a, hipStream_t s);   // the form: Knobs::bev_*
@@ -359,9 +359,12 @@ __host__ __device__ inline size_t bev_items_offset(int occ_w, int occ_h) {
 // thread's when ctx is null) and return `code`; ctx_device: the HIP device the context was created on.
 int ctx_fail(bugseg_ctx *ctx, int code, const char *msg);
 int ctx_device(const bugseg_ctx *ctx);
-// ctx_clahe_tables: the context's device copy of clahe_kernels.hip's conversion tables; the first call
-// uploads `host` (`bytes` long) on the context's private setup stream and waits for it there, so it works
-// while `stream` is being captured (as the resize tables). Freed with the context. BUGSEG_OK or an error.
+// for bev_runtime.cpp: the context's knobs, its context-lifetime device memory (ctx_memory.h) and its BEV state
+const Knobs &ctx_knobs(const bugseg_ctx *ctx);
+class CtxMemory &ctx_memory(bugseg_ctx *ctx);
+struct BevState &ctx_bev(bugseg_ctx *ctx);
+// ctx_clahe_tables: the context's device copy of clahe_kernels.hip's conversion tables, freed with it; the first call
+// uploads `host` (`bytes` long) through CtxMemory::upload, so it works while `stream` is being captured. BUGSEG_OK or an error.
 int ctx_clahe_tables(bugseg_ctx *ctx, const void *host, size_t bytes, void *stream, const void **dev);
 // launch_fail: the error the last kernel launch left, recorded as "<op> launch: <HIP's text>" (BUGSEG_EHIP);
 // BUGSEG_OK (0) when it left none.

@@ -23,6 +23,7 @@
 #include <variant>
 
 #include "bugseg_internal.h"
+#include "bev_runtime.h"
 #include "../../include/bugseg.h"
 
 using namespace bugseg;
@@ -307,9 +308,8 @@ inline int pow2_nr(int npad) {   // 16-row fragments, rounded up to 1, 2, 4 or 8
 }  // namespace
 
 struct bugseg_ctx {
-    explicit bugseg_ctx(const Knobs &k) : knobs(k) {}
+    bugseg_ctx(const Knobs &k, int device) : knobs(k), mem(device) {}
     const Knobs knobs;                             // the BUGSEG_* knobs as bugseg_create read them (knobs.h)
-    int device = 0;
     int prec = PREC_F32;
     float naff[6] = {};                            // exact affine form of the normalisation table (find_affine)
     bool naff_on = false;                          // ... found (never searched for under Knobs::init_table)
@@ -327,34 +327,11 @@ struct bugseg_ctx {
     void *dev_w = nullptr;
     void *dev_luts = nullptr;                      // [0..15] lut3, [16..31] binary, then 3x256 f64 norm lut
     Plan plan;
-    // preprocess resize tables (mode 2), one per recent (H0, W0, H, W): read-only once built, shared by
-    // every stream; pinned: used by a call that was captured into a graph — never evicted while the
-    // context lives (as the BEV and polar tables)
-    struct PreTab { int key[4] = {0, 0, 0, 0}; void *tab = nullptr; bool pinned = false; };
-    std::vector<PreTab> pre_tabs;
-    // Private non-blocking stream for one-time table builds: a table is built and waited for there
-    // before the caller's work is enqueued, so it never needs a sync of the caller's (or any other)
-    // stream, and a first call made while the caller's stream is being captured into a graph works.
-    hipStream_t setup = nullptr;
-    // laserscan mode: polar tables per grid geometry (occ_w, occ_h, variant), read-only once built
-    struct PolarTab { int key[3] = {0, 0, -1}; int pw = 0, ph = 0; void *tab = nullptr; bool pinned = false; };
-    std::vector<PolarTab> polar_tabs;  // tab: fmap (ph*pw int32) then imap (occ_h*occ_w int32)
-    // laserscan batch scratch of bugseg_bev_occgrid (the caller-workspace entry bugseg_bev_occgrid_ws
-    // needs none): cells (B*occ_h*occ_w u8, 256-B aligned) then rmin (B*ph int32). Keyed by stream
-    // so that calls enqueued on different streams of one context never share intermediate buffers.
-    struct LsScratch { void *stream = nullptr; void *p = nullptr; size_t bytes = 0; uint64_t used = 0; bool pinned = false; };
-    std::vector<LsScratch> ls_scratch;
-    uint64_t use_clock = 0;
-    // BEV warp-tap tables (bev_kernels.hip bev_table_kernel), one per recent geometry (read-only
-    // once built, shared by every stream); key = the geometry fields of BevArgs. pinned: used by a
-    // call that was captured into a graph — never evicted while the context lives.
-    // row0, row1: the class-map rows [row0, row1) that carry weight in some tap (bugseg_bev_source_rows)
-    struct BevTab { std::vector<unsigned char> key; uint4 *tab = nullptr; bool pinned = false; int nitems = 0; int row0 = 0, row1 = 0; };
-    std::vector<BevTab> bev_tabs;
-    // memory retired while a stream was capturing (a graph may reference it): freed at destroy
-    std::vector<void *> graveyard;
-    // clahe_kernels.hip's conversion tables (ctx_clahe_tables): uploaded on first use, read-only afterwards
-    void *clahe_tabs = nullptr;
+    CtxMemory mem;                                 // the device, the setup stream, the graveyard (ctx_memory.h)
+    struct NoPayload {};
+    TableCache<std::array<int, 4>, NoPayload> pre_tabs;   // preprocess resize tables (mode 2) by (H0, W0, H, W)
+    BevState bev;                                  // the BEV rasteriser's tables and scratch (bev_runtime.cpp)
+    void *clahe_tabs = nullptr;                    // clahe_kernels.hip's conversion tables (ctx_clahe_tables)
 };
 
 namespace {
@@ -363,38 +340,6 @@ int fail(bugseg_ctx *c, int code, const std::string &m) {
     if (c) c->err = m;
     else g_thread_err = m;
     return code;
-}
-
-// True when `stream` is being captured into a graph (or its capture state cannot be read, which HIP
-// reports for the legacy stream while another stream captures: treated as capturing, so nothing
-// that synchronises is attempted).
-bool stream_capturing(void *stream) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess) return true;
-    return st != hipStreamCaptureStatusNone;
-}
-
-// Lets this thread allocate and wait on the private setup stream while one of its streams is
-// capturing in the global mode (torch.cuda.graph's default): those calls do not touch the capture.
-struct RelaxCapture {
-    hipStreamCaptureMode m = hipStreamCaptureModeRelaxed;
-    RelaxCapture() { (void)hipThreadExchangeStreamCaptureMode(&m); }
-    ~RelaxCapture() { (void)hipThreadExchangeStreamCaptureMode(&m); }
-};
-
-hipStream_t setup_stream(bugseg_ctx *c) {
-    if (!c->setup && hipStreamCreateWithFlags(&c->setup, hipStreamNonBlocking) != hipSuccess) c->setup = nullptr;
-    return c->setup;
-}
-
-// Free device memory that work already enqueued on some stream may still read. Outside a capture
-// that takes a device sync (only the rare evictions come here: a 5th table geometry, a 9th stream
-// on the scratch-owning entry); during a capture the memory is kept until the context is destroyed.
-void retire(bugseg_ctx *c, void *p, bool capturing) {
-    if (!p) return;
-    if (capturing) { c->graveyard.push_back(p); return; }
-    (void)hipDeviceSynchronize();
-    (void)hipFree(p);
 }
 
 // ---------------------------------------------------------------- blob parsing
@@ -945,7 +890,7 @@ int fusable_down(const bugseg_ctx *ctx, const BlockDesc &b, const std::vector<in
 int pick_bneck_variant(const bugseg_ctx *ctx, int C, bool asym, int d, int B, int H, int W, int &tiles_y, int &tiles_x,
                        int &tr, int &rdv) {
     int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) cus = 256;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->mem.device) != hipSuccess || cus <= 0) cus = 256;
     const Knobs &k = ctx->knobs;
     int force = k.bneck_variant;                                           // -1: none
     const int fc = C == 128 ? k.bneck_variant_c128 : C == 64 ? k.bneck_variant_c64 : C == 16 ? k.bneck_variant_c16 : -1;
@@ -1437,7 +1382,7 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
     RelaxCapture relax;                 // the first forward at a shape may itself be captured
     if (pl.arena) {
         // a forward of the old shape may still be running (or be part of a captured graph)
-        retire(ctx, pl.arena, cap || pl.pinned);
+        ctx->mem.retire(pl.arena, cap || pl.pinned);
         pl.arena = nullptr;
         pl.pinned = false;
     }
@@ -1695,28 +1640,20 @@ void linear_coeffs(int dsize, int ssize, double scale, int *ofs, short *a01) {
 
 namespace bugseg {
 int ctx_fail(bugseg_ctx *ctx, int code, const char *msg) { return fail(ctx, code, msg); }
-int ctx_device(const bugseg_ctx *ctx) { return ctx->device; }
+int ctx_device(const bugseg_ctx *ctx) { return ctx->mem.device; }
 int launch_fail(bugseg_ctx *ctx, const char *op) {
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) return BUGSEG_OK;
     return fail(ctx, BUGSEG_EHIP, std::string(op) + " launch: " + hipGetErrorString(e));
 }
+const Knobs &ctx_knobs(const bugseg_ctx *ctx) { return ctx->knobs; }
+CtxMemory &ctx_memory(bugseg_ctx *ctx) { return ctx->mem; }
+BevState &ctx_bev(bugseg_ctx *ctx) { return ctx->bev; }
 int ctx_clahe_tables(bugseg_ctx *ctx, const void *host, size_t bytes, void *stream, const void **dev) {
-    (void)stream;       // never touched: the upload runs and is waited for on the private setup stream
-    if (!ctx->clahe_tabs) {
-        DeviceGuard g(ctx->device);
-        RelaxCapture relax;
-        hipStream_t st = setup_stream(ctx);
-        void *t = nullptr;
-        hipError_t e = st ? hipMalloc(&t, bytes) : hipErrorInvalidValue;
-        if (e == hipSuccess) e = hipMemcpyAsync(t, host, bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            if (t) (void)hipFree(t);
+    (void)stream;       // never touched: the upload runs and is waited for on the setup stream
+    if (!ctx->clahe_tabs)
+        if (hipError_t e = ctx->mem.upload({{host, bytes}}, &ctx->clahe_tabs))
             return fail(ctx, BUGSEG_EHIP, std::string("clahe table upload failed: ") + hipGetErrorString(e));
-        }
-        ctx->clahe_tabs = t;
-    }
     *dev = ctx->clahe_tabs;
     return BUGSEG_OK;
 }
@@ -1740,9 +1677,8 @@ int bugseg_create(int device, int precision, bugseg_ctx **out) {
     Knobs knobs;
     std::string bad;
     if (!read_knobs(knobs, bad)) return fail(nullptr, BUGSEG_EINVAL, bad);
-    bugseg_ctx *c = new (std::nothrow) bugseg_ctx(knobs);
+    bugseg_ctx *c = new (std::nothrow) bugseg_ctx(knobs, device);
     if (!c) return fail(nullptr, BUGSEG_ENOMEM, "out of host memory");
-    c->device = device;
     c->prec = precision == BUGSEG_BF16 ? PREC_BF16 : precision == BUGSEG_F16 ? PREC_F16 : PREC_F32;
     DeviceGuard g(device);
     // class remap tables (models.py:56-58 and :79-80) + the normalisation table (models.py:17-18, 91)
@@ -1760,13 +1696,11 @@ int bugseg_create(int device, int precision, bugseg_ctx **out) {
         }
 
     {
-        // uploaded on the context's private stream (never the legacy stream, which would join a capture
-        // in progress on another stream), so a context may be created while a stream is capturing
+        // on the setup stream (never the legacy stream, which would join a capture in progress on another
+        // stream), so a context may be created while a stream is capturing
         RelaxCapture relax;
-        hipStream_t s = setup_stream(c);
-        hipError_t e = s ? hipMalloc(&c->dev_luts, sizeof(tab)) : hipErrorInvalidValue;
-        if (e == hipSuccess) e = hipMemcpyAsync(c->dev_luts, tab, sizeof(tab), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        hipError_t e = c->mem.upload({{tab, sizeof(tab)}}, &c->dev_luts);
+        hipStream_t s = c->mem.setup_stream();
         // bf16 / fp16: the fused initial block evaluates the table as one fmaf per byte when an f32
         // pair (a, b) near (1 / (256 std), -mean / std) reproduces all 256 stored values of a channel
         // bit for bit (searched on the device, with its own conversions: init_kernels.hip
@@ -1805,8 +1739,6 @@ int bugseg_create(int device, int precision, bugseg_ctx **out) {
             c->naff_on = all;
         }
         if (e != hipSuccess) {
-            if (c->dev_luts) (void)hipFree(c->dev_luts);
-            if (c->setup) (void)hipStreamDestroy(c->setup);
             delete c;
             return fail(nullptr, BUGSEG_EHIP, std::string("device allocation failed: ") + hipGetErrorString(e));
         }
@@ -1817,25 +1749,19 @@ int bugseg_create(int device, int precision, bugseg_ctx **out) {
 
 int bugseg_destroy(bugseg_ctx *ctx) {
     if (!ctx) return BUGSEG_OK;
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     (void)hipDeviceSynchronize();
     if (ctx->dev_w) (void)hipFree(ctx->dev_w);
     if (ctx->dev_luts) (void)hipFree(ctx->dev_luts);
     if (ctx->plan.arena) (void)hipFree(ctx->plan.arena);
-    for (auto &t : ctx->pre_tabs) if (t.tab) (void)hipFree(t.tab);
-    for (auto &t : ctx->polar_tabs) if (t.tab) (void)hipFree(t.tab);
-    for (auto &s : ctx->ls_scratch) if (s.p) (void)hipFree(s.p);
-    for (auto &t : ctx->bev_tabs) if (t.tab) (void)hipFree(t.tab);
-    for (void *p : ctx->graveyard) (void)hipFree(p);
     if (ctx->clahe_tabs) (void)hipFree(ctx->clahe_tabs);
-    if (ctx->setup) (void)hipStreamDestroy(ctx->setup);
-    delete ctx;
+    delete ctx;                                       // the caches, the graveyard and the setup stream
     return BUGSEG_OK;
 }
 
 int bugseg_load_weights(bugseg_ctx *ctx, const void *blob, size_t bytes) {
     if (!ctx || !blob) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     std::vector<BlockDesc> blocks;
     int ncls = 0;
     std::string why;
@@ -1844,16 +1770,11 @@ int bugseg_load_weights(bugseg_ctx *ctx, const void *blob, size_t bytes) {
     ctx->ncls = ncls;
     ctx->loaded = false;
     if (!pack_all(ctx, why)) return fail(ctx, BUGSEG_EFORMAT, "weight blob: " + why);
-    (void)hipDeviceSynchronize();
-    if (ctx->dev_w) {
-        // a captured graph's kernels hold pointers into the old weights (and arena): kept until destroy
-        if (ctx->plan.pinned) ctx->graveyard.push_back(ctx->dev_w);
-        else (void)hipFree(ctx->dev_w);
-        ctx->dev_w = nullptr;
-    }
+    // a captured graph's kernels hold pointers into the old weights and arena: then kept until destroy
+    ctx->mem.retire(ctx->dev_w, ctx->plan.pinned);
+    ctx->dev_w = nullptr;
     if (ctx->plan.arena) {
-        if (ctx->plan.pinned) ctx->graveyard.push_back(ctx->plan.arena);   // a captured graph may use it
-        else (void)hipFree(ctx->plan.arena);
+        ctx->mem.retire(ctx->plan.arena, ctx->plan.pinned);
         ctx->plan = Plan();
     }
     if (hipMalloc(&ctx->dev_w, ctx->host_w.size()) != hipSuccess ||
@@ -1875,7 +1796,7 @@ int bugseg_preprocess(bugseg_ctx *ctx, const uint8_t *bgr, int B, int H0, int W0
     if (!ctx || !bgr || !out) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     if (B <= 0 || H0 <= 0 || W0 <= 0 || H <= 0 || W <= 0) return fail(ctx, BUGSEG_EINVAL, "bad shape");
     if (out_layout < BUGSEG_PRE_ENGINE || out_layout > BUGSEG_PRE_BGR_U8) return fail(ctx, BUGSEG_EINVAL, "bad out_layout");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     PreArgs a;
     std::memset(&a, 0, sizeof(a));
     a.bgr = bgr; a.B = B; a.H0 = H0; a.W0 = W0; a.H = H; a.W = W;
@@ -1892,46 +1813,18 @@ int bugseg_preprocess(bugseg_ctx *ctx, const uint8_t *bgr, int B, int H0, int W0
             a.mode = 1;
         } else {
             a.mode = 2;
-            const int key[4] = {H0, W0, H, W};
-            const size_t need = (size_t)W * 4 + (size_t)W * 4 + (size_t)H * 4 + (size_t)H * 4;
-            const bool cap = stream_capturing(stream);
-            bugseg_ctx::PreTab *hit = nullptr;
-            for (auto &t : ctx->pre_tabs)
-                if (std::memcmp(t.key, key, sizeof(key)) == 0) hit = &t;
-            if (!hit) {
-                std::vector<unsigned char> h(need);
-                int *xo = (int *)h.data();
-                short *xa = (short *)(h.data() + (size_t)W * 4);
-                int *yo = (int *)(h.data() + (size_t)W * 8);
-                short *yb = (short *)(h.data() + (size_t)W * 8 + (size_t)H * 4);
-                linear_coeffs(W, W0, sx, xo, xa);
-                linear_coeffs(H, H0, sy, yo, yb);
-                if (ctx->pre_tabs.size() >= 4) {            // keep 4 geometries: evict the oldest unpinned one
-                    for (size_t i = 0; i < ctx->pre_tabs.size(); ++i)
-                        if (!ctx->pre_tabs[i].pinned) {
-                            // work enqueued on any stream may still read it: retire syncs (or defers)
-                            retire(ctx, ctx->pre_tabs[i].tab, cap);
-                            ctx->pre_tabs.erase(ctx->pre_tabs.begin() + (long)i);
-                            break;
-                        }
-                }
-                // built on the private stream and waited for there, so the caller's stream is never
-                // synchronised and a capture in progress on it stays valid
-                bugseg_ctx::PreTab t;
-                std::memcpy(t.key, key, sizeof(key));
-                RelaxCapture relax;
-                hipStream_t st = setup_stream(ctx);
-                hipError_t e = st ? hipMalloc(&t.tab, need) : hipErrorInvalidValue;
-                if (e == hipSuccess) e = hipMemcpyAsync(t.tab, h.data(), need, hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) e = hipStreamSynchronize(st);
-                if (e != hipSuccess) {
-                    if (t.tab) (void)hipFree(t.tab);
-                    return fail(ctx, BUGSEG_EHIP, std::string("resize table upload failed: ") + hipGetErrorString(e));
-                }
-                ctx->pre_tabs.push_back(t);
-                hit = &ctx->pre_tabs.back();
-            }
-            if (cap) hit->pinned = true;
+            int rc = BUGSEG_OK;
+            const auto *hit = ctx->pre_tabs.get(ctx->mem, {H0, W0, H, W}, stream_capturing(stream), true, &rc, [&](auto &t) -> int {
+                std::vector<int> xo((size_t)W), yo((size_t)H);
+                std::vector<short> xa(2 * (size_t)W), yb(2 * (size_t)H);
+                linear_coeffs(W, W0, sx, xo.data(), xa.data());
+                linear_coeffs(H, H0, sy, yo.data(), yb.data());
+                const hipError_t e = ctx->mem.upload({{xo.data(), (size_t)W * 4}, {xa.data(), (size_t)W * 4}, {yo.data(), (size_t)H * 4},
+                                                      {yb.data(), (size_t)H * 4}}, &t.tab);
+                if (e == hipSuccess) return BUGSEG_OK;
+                return fail(ctx, BUGSEG_EHIP, std::string("resize table upload failed: ") + hipGetErrorString(e));
+            });
+            if (!hit) return rc;
             unsigned char *t = (unsigned char *)hit->tab;
             a.xofs = (const int *)t;
             a.xa = (const short *)(t + (size_t)W * 4);
@@ -1947,7 +1840,7 @@ int bugseg_preprocess(bugseg_ctx *ctx, const uint8_t *bgr, int B, int H0, int W0
 int bugseg_nchw_to_input(bugseg_ctx *ctx, const void *x, int is_f64, int B, int H, int W, void *out, void *stream) {
     if (!ctx || !x || !out) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     if (B <= 0 || H <= 0 || W <= 0) return fail(ctx, BUGSEG_EINVAL, "bad shape");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     NchwArgs a{x, is_f64 ? 1 : 0, B, H, W, ctx->prec, out};
     hipError_t e = launch_nchw_to_input(a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("layout launch: ") + hipGetErrorString(e));
@@ -2054,7 +1947,7 @@ static int enet_forward(bugseg_ctx *ctx, const void *in, bool bgr, int B, int H,
     if (!ctx || !in || !out) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     if (!ctx->loaded) return fail(ctx, BUGSEG_ESTATE, "no weights loaded");
     if (out_kind < BUGSEG_OUT_LOGITS_F32 || out_kind > BUGSEG_OUT_BINARY_U8) return fail(ctx, BUGSEG_EINVAL, "bad out_kind");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     std::string why;
     if (!build_plan(ctx, B, H, W, why, stream)) return fail(ctx, BUGSEG_EINVAL, why);
     Plan &pl = ctx->plan;
@@ -2111,393 +2004,10 @@ int bugseg_enet_forward_bgr_rows(bugseg_ctx *ctx, const uint8_t *bgr, int B, int
     return enet_forward(ctx, bgr, true, B, H, W, out_kind, out, stream, first_op, last_op, row0, row1);
 }
 
-}  // extern "C"
-
-namespace {
-
-// ---- laserscan-like mode: cv::warpPolar's remap tables (imgwarp.cpp 4.x), built on the host once
-// per geometry. Forward: polar (rho, phi) -> grid cell, phi the row of a ph x pw polar image,
-// x = (float)(rho*Kmag) * cos(Kangle*phi) + cx in double, rounded to float, then half-to-even to a
-// short (remap INTER_NEAREST). Inverse: grid cell -> (rho, polar row) through hal::magnitude32f /
-// fastAtan32f (the AVX2 dispatch: fused polynomial) on float offsets, the BORDER_WRAP row of
-// copyMakeBorder folded into the row index. -1 = outside (BORDER_TRANSPARENT).
-#pragma clang fp contract(off)
-const float kAtanP1 = 0.9997878412794807f * (float)(180 / 3.1415926535897932384626433832795);
-const float kAtanP3 = -0.3258083974640975f * (float)(180 / 3.1415926535897932384626433832795);
-const float kAtanP5 = 0.1555786518463281f * (float)(180 / 3.1415926535897932384626433832795);
-const float kAtanP7 = -0.04432655554792128f * (float)(180 / 3.1415926535897932384626433832795);
-
-float fast_atan_rad(float y, float x) {
-    const float ax = std::fabs(x), ay = std::fabs(y);
-    const float c = std::min(ax, ay) / (std::max(ax, ay) + (float)2.220446049250313e-16);
-    const float cc = c * c;
-    float a = std::fma(std::fma(std::fma(cc, kAtanP7, kAtanP5), cc, kAtanP3), cc, kAtanP1) * c;
-    if (!(ax >= ay)) a = 90.f - a;
-    if (x < 0) a = 180.f - a;
-    if (y < 0) a = 360.f - a;
-    return a * (float)(3.1415926535897932384626433832795 / 180);
-}
-
-int round_short(float v) {
-    const long r = std::lrint(v);
-    return (int)(r < -32768 ? -32768 : r > 32767 ? 32767 : r);
-}
-
-void polar_tables(int pw, int ph, double max_radius, float cx, float cy, int w, int h, std::vector<int32_t> &fmap,
-                  std::vector<int32_t> &imap) {
-    const double CV_2PI = 6.283185307179586476925286766559;
-    const double Kangle = CV_2PI / ph, Kmag = max_radius / pw;
-    fmap.resize((size_t)pw * ph);
-    for (int phi = 0; phi < ph; ++phi) {
-        const double KKy = Kangle * phi, cp = std::cos(KKy), sp = std::sin(KKy);
-        for (int rho = 0; rho < pw; ++rho) {
-            const float r = (float)(rho * Kmag);
-            const float mx = (float)(r * cp + (double)cx), my = (float)(r * sp + (double)cy);
-            const int sx = round_short(mx), sy = round_short(my);
-            fmap[(size_t)phi * pw + rho] = ((unsigned)sx < (unsigned)w && (unsigned)sy < (unsigned)h) ? (sx | (sy << 16)) : -1;
-        }
-    }
-    imap.resize((size_t)w * h);
-    for (int y = 0; y < h; ++y)
-        for (int x = 0; x < w; ++x) {
-            const float bx = (float)x - cx, by = (float)y - cy;
-            const float mag = std::sqrt(std::fma(bx, bx, by * by));
-            const float ang = fast_atan_rad(by, bx);
-            const double rho = mag / Kmag, phi = ang / Kangle;
-            const float mx = (float)rho, my = (float)phi + 1;
-            const int X = round_short(mx), Y = round_short(my);
-            int32_t v = -1;
-            if ((unsigned)X < (unsigned)pw && (unsigned)Y < (unsigned)(ph + 2)) {
-                const int row = Y == 0 ? ph - 1 : (Y == ph + 1 ? 0 : Y - 1);
-                v = X | (row << 16);
-            }
-            imap[(size_t)y * w + x] = v;
-        }
-}
-#pragma clang fp contract(on)
-
-// warpPolar dsize: (-1, -1) -> (round(L), round(L*pi)) for create_occupancy_grid (bev.py:219); the
-// explicit (w, h) of create_occupancy_grid_binary (bev.py:146). False if the tables cannot hold it.
-bool polar_dims(const bugseg_bev_params *p, int &pw, int &ph) {
-    const int w = p->occ_w, h = p->occ_h, L = std::max(w, h);
-    pw = p->variant ? w : (int)std::lrint((double)L);
-    ph = p->variant ? h : (int)std::lrint((double)L * 3.1415926535897932384626433832795);
-    return pw > 0 && ph > 0 && pw <= 32767 && ph <= 32767 && w <= 32767 && h <= 32767;
-}
-
-// Laserscan batch scratch: cells (B*occ_h*occ_w u8, 256-B aligned) then rmin (B*ph int32).
-size_t ls_cells_bytes(int B, const bugseg_bev_params *p) { return ((size_t)B * p->occ_w * p->occ_h + 255) & ~(size_t)255; }
-size_t ls_workspace_bytes(int B, const bugseg_bev_params *p, int ph) {
-    return ls_cells_bytes(B, p) + (size_t)B * ph * sizeof(int32_t);
-}
-
-// The polar tables of a laserscan call (built once per grid geometry on the setup stream, waited
-// for there); fills a.fmap / imap / pw / ph / hit.
-int prepare_polar(bugseg_ctx *ctx, const bugseg_bev_params *p, BevArgs &a, bool cap) {
-    const int w = p->occ_w, h = p->occ_h, L = std::max(w, h);
-    int pw, ph;
-    if (!polar_dims(p, pw, ph)) return fail(ctx, BUGSEG_EINVAL, "laserscan grid too large for the polar tables");
-    bugseg_ctx::PolarTab *hit = nullptr;
-    for (auto &t : ctx->polar_tabs)
-        if (t.key[0] == w && t.key[1] == h && t.key[2] == p->variant) hit = &t;
-    if (!hit) {
-        std::vector<int32_t> fmap, imap;
-        polar_tables(pw, ph, (double)L, (float)(w / 2.0 - 1), (float)h, w, h, fmap, imap);
-        if (ctx->polar_tabs.size() >= 4) {            // keep 4 geometries: evict the oldest unpinned one
-            for (size_t i = 0; i < ctx->polar_tabs.size(); ++i)
-                if (!ctx->polar_tabs[i].pinned) {
-                    retire(ctx, ctx->polar_tabs[i].tab, cap);
-                    ctx->polar_tabs.erase(ctx->polar_tabs.begin() + (long)i);
-                    break;
-                }
-        }
-        RelaxCapture relax;
-        hipStream_t s = setup_stream(ctx);
-        if (!s) return fail(ctx, BUGSEG_EHIP, "could not create the table-build stream");
-        bugseg_ctx::PolarTab t;
-        t.key[0] = w; t.key[1] = h; t.key[2] = p->variant;
-        t.pw = pw; t.ph = ph;
-        const size_t bytes = (fmap.size() + imap.size()) * sizeof(int32_t);
-        if (hipMalloc(&t.tab, bytes) != hipSuccess) return fail(ctx, BUGSEG_ENOMEM, "polar table allocation failed");
-        hipError_t e = hipMemcpyAsync(t.tab, fmap.data(), fmap.size() * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((int32_t *)t.tab + fmap.size(), imap.data(), imap.size() * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(t.tab);
-            return fail(ctx, BUGSEG_EHIP, std::string("polar table upload: ") + hipGetErrorString(e));
-        }
-        ctx->polar_tabs.push_back(t);
-        hit = &ctx->polar_tabs.back();
-    }
-    if (cap) hit->pinned = true;
-    a.laserscan = 1;
-    a.fmap = (const int32_t *)hit->tab;
-    a.imap = (const int32_t *)hit->tab + (size_t)pw * ph;
-    a.pw = pw; a.ph = ph;
-    a.hit = p->variant ? 100 : 3;
-    return BUGSEG_OK;
-}
-
-// The scratch-owning entry's per-stream laserscan scratch (bugseg_bev_occgrid without a workspace).
-int internal_scratch(bugseg_ctx *ctx, void *stream, size_t need, bool cap, void *&out) {
-    bugseg_ctx::LsScratch *sc = nullptr;
-    for (auto &x : ctx->ls_scratch) if (x.stream == stream) sc = &x;
-    if (!sc) {
-        if (ctx->ls_scratch.size() >= 8) {            // 8 streams: evict the least recently used unpinned one
-            long victim = -1;
-            for (size_t i = 0; i < ctx->ls_scratch.size(); ++i)
-                if (!ctx->ls_scratch[i].pinned && (victim < 0 || ctx->ls_scratch[i].used < ctx->ls_scratch[(size_t)victim].used))
-                    victim = (long)i;
-            if (victim >= 0) {
-                retire(ctx, ctx->ls_scratch[(size_t)victim].p, cap);
-                ctx->ls_scratch.erase(ctx->ls_scratch.begin() + victim);
-            }
-        }
-        ctx->ls_scratch.push_back(bugseg_ctx::LsScratch());
-        sc = &ctx->ls_scratch.back();
-        sc->stream = stream;
-    }
-    sc->used = ++ctx->use_clock;
-    if (need > sc->bytes) {
-        // work already enqueued on this stream (or captured from it) may still use the old buffer
-        retire(ctx, sc->p, cap || sc->pinned);
-        sc->p = nullptr;
-        sc->bytes = 0;
-        RelaxCapture relax;
-        if (hipMalloc(&sc->p, need) != hipSuccess) return fail(ctx, BUGSEG_ENOMEM, "laserscan scratch allocation failed");
-        sc->bytes = need;
-    }
-    if (cap) sc->pinned = true;
-    out = sc->p;
-    return BUGSEG_OK;
-}
-
-// what warp_tap (bev_kernels.hip) reads: the sizes of the source and of the warped image, the inverse matrix and
-// the x-block width; every other field of `a` is zeroed. The sizes are positive (the callers check).
-void warp_geometry(const bugseg_bev_params *p, BevArgs &a) {
-    std::memset(&a, 0, sizeof(a));
-    a.in_rows = p->in_rows; a.in_cols = p->in_cols;
-    {
-        // cv::invert(M) closed-form 3x3 branch (DECOMP_LU), as warpPerspective does without WARP_INVERSE_MAP
-#pragma clang fp contract(off)
-        const double *S = p->M;
-        double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
-        if (d != 0.0) {
-            d = 1.0 / d;
-            a.Mi[0] = (S[4] * S[8] - S[5] * S[7]) * d;
-            a.Mi[1] = (S[2] * S[7] - S[1] * S[8]) * d;
-            a.Mi[2] = (S[1] * S[5] - S[2] * S[4]) * d;
-            a.Mi[3] = (S[5] * S[6] - S[3] * S[8]) * d;
-            a.Mi[4] = (S[0] * S[8] - S[2] * S[6]) * d;
-            a.Mi[5] = (S[2] * S[3] - S[0] * S[5]) * d;
-            a.Mi[6] = (S[3] * S[7] - S[4] * S[6]) * d;
-            a.Mi[7] = (S[1] * S[6] - S[0] * S[7]) * d;
-            a.Mi[8] = (S[0] * S[4] - S[1] * S[3]) * d;
-        }
-    }
-    const int bh0 = std::min(16, p->warp_h);
-    a.bw0 = std::min(1024 / bh0, p->warp_w);
-    a.warp_w = p->warp_w; a.warp_h = p->warp_h;
-}
-
-// the geometry fields of the rasteriser's arguments from the caller's parameters (checked)
-int bev_geometry(bugseg_ctx *ctx, const bugseg_bev_params *p, BevArgs &a) {
-    if (p->in_rows <= 0 || p->in_cols <= 0 || p->warp_w <= 0 || p->warp_h <= 0 || p->occ_w <= 0 ||
-        p->occ_h <= 0 || p->occ_w_px <= 0 || p->occ_h_px <= 0)
-        return fail(ctx, BUGSEG_EINVAL, "bad BEV geometry");
-    if (p->variant != 0 && p->variant != 1) return fail(ctx, BUGSEG_EINVAL, "variant must be 0 or 1");
-    if (p->laserscan != 0 && p->laserscan != 1) return fail(ctx, BUGSEG_EINVAL, "laserscan must be 0 or 1");
-    warp_geometry(p, a);
-    a.occ_w_px = p->occ_w_px; a.occ_h_px = p->occ_h_px; a.occ_w = p->occ_w; a.occ_h = p->occ_h;
-    a.left_x = p->left_x; a.top_y = p->top_y;
-    a.ifx = 1.0 / ((double)p->occ_w / p->occ_w_px);
-    a.ify = 1.0 / ((double)p->occ_h / p->occ_h_px);
-    a.ros_layout = p->ros_layout;
-    a.variant = p->variant;
-    return BUGSEG_OK;
-}
-
-// The geometry's warp-tap table: built once on the setup stream and waited for there, then shared
-// read-only by every call on any stream. cap: the caller's stream is being captured (nothing synchronises
-// the device, and with pin the table is never evicted while the context lives).
-int bev_table(bugseg_ctx *ctx, BevArgs &a, bool cap, bugseg_ctx::BevTab *&hit, bool pin = true) {
-    {
-        std::vector<unsigned char> key(sizeof(double) * 11 + sizeof(int) * 12);
-        unsigned char *kp = key.data();
-        auto put = [&](const void *v, size_t n) { std::memcpy(kp, v, n); kp += n; };
-        put(a.Mi, sizeof(a.Mi)); put(&a.ifx, sizeof(double)); put(&a.ify, sizeof(double));
-        const int ik[12] = {a.in_rows, a.in_cols, a.bw0, a.warp_w, a.warp_h, a.occ_w_px, a.occ_h_px, a.occ_w, a.occ_h,
-                            a.left_x, a.top_y, 0};
-        put(ik, sizeof(ik));
-        hit = nullptr;
-        for (auto &t : ctx->bev_tabs) if (t.key == key) hit = &t;
-        if (!hit) {
-            const size_t cells = (size_t)a.occ_h * a.occ_w;
-            if (cells * BEV_SLOTS > (size_t)1 << 31) return fail(ctx, BUGSEG_EINVAL, "occupancy grid too large");
-            if (ctx->bev_tabs.size() >= 4) {            // keep 4 geometries: evict the oldest unpinned one
-                for (size_t i = 0; i < ctx->bev_tabs.size(); ++i)
-                    if (!ctx->bev_tabs[i].pinned) {
-                        retire(ctx, ctx->bev_tabs[i].tab, cap);
-                        ctx->bev_tabs.erase(ctx->bev_tabs.begin() + (long)i);
-                        break;
-                    }
-            }
-            RelaxCapture relax;
-            hipStream_t s = setup_stream(ctx);
-            if (!s) return fail(ctx, BUGSEG_EHIP, "could not create the table-build stream");
-            bugseg_ctx::BevTab t;
-            t.key = key;
-            if (hipMalloc(&t.tab, bev_table_bytes(a.occ_w, a.occ_h)) != hipSuccess)
-                return fail(ctx, BUGSEG_ENOMEM, "BEV table allocation failed");
-            a.wtab = t.tab;
-            hipError_t e = launch_bev_table(a, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);   // only the build itself is waited for
-            // the band-staged form's work items from the band records: one per (band, row part), the
-            // far bands first: with the item-major workgroup order their workgroups (the longest-lived,
-            // in-kernel clocks: 20 us at the median against 15 for the near bands) are dispatched first.
-            // 26.2 -> 23.7 us per 32 frames against nearest-first (scripts/gpu_r4_far.sh)
-            const int nb = bev_bands(a.occ_h);
-            std::vector<int4> rec((size_t)nb * BEV_BOXREC);
-            std::vector<int2> items;
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(rec.data(), (unsigned char *)t.tab + bev_records_offset(a.occ_w, a.occ_h),
-                                   rec.size() * sizeof(int4), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e == hipSuccess) {
-                // (BUGSEG_BEV_NEAR_FIRST=1: the earlier order, nearest bands first; A/B)
-                const bool near_first = ctx->knobs.bev_near_first;
-                for (int i = 0; i < nb; ++i) {
-                    const int b = near_first ? nb - 1 - i : i;
-                    for (int k = 0; k < std::max(1, std::min(BEV_BAND, rec[(size_t)b * BEV_BOXREC].x)); ++k) items.push_back(make_int2(b, k));
-                }
-                // the class-map rows the rasteriser's result depends on (bugseg_bev_source_rows): the union
-                // of the bands' spans (header .z, .w; lo > hi: no tap of the band carries weight)
-                int lo = 1 << 30, hi = -(1 << 30);
-                for (int b = 0; b < nb; ++b) {
-                    const int4 h = rec[(size_t)b * BEV_BOXREC];
-                    if (h.z <= h.w) { lo = std::min(lo, h.z); hi = std::max(hi, h.w); }
-                }
-                t.row0 = lo <= hi ? std::max(lo, 0) : 0;
-                t.row1 = lo <= hi ? std::min(hi + 1, a.in_rows) : 0;
-                e = hipMemcpyAsync((unsigned char *)t.tab + bev_items_offset(a.occ_w, a.occ_h), items.data(),
-                                   items.size() * sizeof(int2), hipMemcpyHostToDevice, s);
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            t.nitems = (int)items.size();
-            if (e != hipSuccess) {
-                (void)hipFree(t.tab);
-                return fail(ctx, BUGSEG_EHIP, std::string("BEV table: ") + hipGetErrorString(e));
-            }
-
-            ctx->bev_tabs.push_back(std::move(t));
-            hit = &ctx->bev_tabs.back();
-        }
-        if (cap && pin) hit->pinned = true;
-        a.wtab = hit->tab;
-        a.nitems = hit->nitems;
-    }
-    return BUGSEG_OK;
-}
-
-int bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_params *p, int8_t *out, bool own_ws,
-                void *ws, size_t ws_bytes, void *stream) {
-    if (!ctx || !seg || !p || !out) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
-    if (B <= 0) return fail(ctx, BUGSEG_EINVAL, "bad BEV geometry");
-    BevArgs a;
-    int rc0 = bev_geometry(ctx, p, a);
-    if (rc0 != BUGSEG_OK) return rc0;
-    DeviceGuard g(ctx->device);
-    a.seg = seg; a.B = B;
-    a.out = out;
-    if (p->laserscan) {
-        // check the workspace before anything is built or enqueued
-        int pw, ph;
-        if (!polar_dims(p, pw, ph)) return fail(ctx, BUGSEG_EINVAL, "laserscan grid too large for the polar tables");
-        if (!own_ws && (!ws || ws_bytes < ls_workspace_bytes(B, p, ph)))
-            return fail(ctx, BUGSEG_EINVAL, "laserscan workspace missing or smaller than bugseg_bev_workspace_bytes()");
-    }
-    const bool cap = stream_capturing(stream);
-    bugseg_ctx::BevTab *hit = nullptr;
-    rc0 = bev_table(ctx, a, cap, hit);
-    if (rc0 != BUGSEG_OK) return rc0;
-    if (p->laserscan) {
-        int rc = prepare_polar(ctx, p, a, cap);
-        if (rc != BUGSEG_OK) return rc;
-        if (own_ws) {
-            rc = internal_scratch(ctx, stream, ls_workspace_bytes(B, p, a.ph), cap, ws);
-            if (rc != BUGSEG_OK) return rc;
-        }
-        a.cells = (uint8_t *)ws;
-        a.rmin = (int32_t *)((unsigned char *)ws + ls_cells_bytes(B, p));
-    }
-    hipError_t e = launch_bev(ctx->knobs, a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("bev launch: ") + hipGetErrorString(e));
-    return BUGSEG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int bugseg_bev_occgrid(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_params *p, int8_t *out, void *stream) {
-    return bev_occgrid(ctx, seg, B, p, out, true, nullptr, 0, stream);
-}
-
-int bugseg_bev_source_rows(bugseg_ctx *ctx, const bugseg_bev_params *p, int in_rows, int in_cols, int *row0, int *row1) {
-    if (!ctx || !p || !row0 || !row1) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
-    if (in_rows != p->in_rows || in_cols != p->in_cols)
-        return fail(ctx, BUGSEG_EINVAL, "source rows: the class map is not the size the parameters name");
-    BevArgs a;
-    int rc = bev_geometry(ctx, p, a);
-    if (rc != BUGSEG_OK) return rc;
-    DeviceGuard g(ctx->device);
-    // (the entry takes no stream, so it behaves as under a capture: the build runs and is waited for on the
-    // setup stream and an evicted table is kept until destroy, never freed behind a device sync; the table
-    // is pinned by the first captured bugseg_bev_occgrid call that uses it)
-    bugseg_ctx::BevTab *hit = nullptr;
-    rc = bev_table(ctx, a, true, hit, false);
-    if (rc != BUGSEG_OK) return rc;
-    *row0 = hit->row0;
-    *row1 = hit->row1;
-    return BUGSEG_OK;
-}
-
-size_t bugseg_bev_workspace_bytes(const bugseg_bev_params *p, int B) {
-    int pw, ph;
-    if (!p || B <= 0 || p->occ_w <= 0 || p->occ_h <= 0 || !p->laserscan || !polar_dims(p, pw, ph)) return 0;
-    return ls_workspace_bytes(B, p, ph);
-}
-
-int bugseg_bev_occgrid_ws(bugseg_ctx *ctx, const uint8_t *seg, int B, const bugseg_bev_params *p, int8_t *out,
-                          void *workspace, size_t workspace_bytes, void *stream) {
-    return bev_occgrid(ctx, seg, B, p, out, false, workspace, workspace_bytes, stream);
-}
-
-int bugseg_bev_warp_image(bugseg_ctx *ctx, const uint8_t *img, int B, int channels, const bugseg_bev_params *p, int gray,
-                          uint8_t *out, void *stream) {
-    if (!ctx || !img || !p || !out) return fail(ctx, BUGSEG_EINVAL, "warp image: NULL argument");
-    if (channels != 1 && channels != 3) return fail(ctx, BUGSEG_EINVAL, "warp image: channels must be 1 or 3");
-    if ((gray != 0 && gray != 1) || (gray && channels != 3)) return fail(ctx, BUGSEG_EINVAL, "warp image: gray is 0 or 1, and 1 only with 3 channels");
-    if (B < 1 || B > 65535 * BEV_WARP_FRAMES) return fail(ctx, BUGSEG_EINVAL, "warp image: B must be at least 1 (and fit the launch grid)");
-    if (p->in_rows <= 0 || p->in_cols <= 0 || p->warp_w <= 0 || p->warp_h <= 0) return fail(ctx, BUGSEG_EINVAL, "warp image: an empty source or result");
-    const size_t in_frame = (size_t)p->in_rows * p->in_cols * channels, out_frame = (size_t)p->warp_w * p->warp_h * (gray ? 1 : channels);
-    if (in_frame > (size_t)INT_MAX || (size_t)p->warp_w * p->warp_h * 3 > (size_t)INT_MAX)
-        return fail(ctx, BUGSEG_EINVAL, "warp image: a frame or a result of 2^31 bytes or more");
-    if (ranges_overlap(out, out_frame * B, img, in_frame * B)) return fail(ctx, BUGSEG_EINVAL, "warp image: out_dev overlaps the input");
-    BevArgs a;
-    warp_geometry(p, a);
-    a.B = B;
-    DeviceGuard g(ctx->device);
-    hipError_t e = launch_bev_warp_image(a, img, channels, gray, out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("warp image launch: ") + hipGetErrorString(e));
-    return BUGSEG_OK;
-}
-
 // ---- test hooks (host only: no device, no HIP call) — tests/asan drives them under ASan + UBSan
 int bugseg_debug_parse_pack(const void *blob, size_t bytes, int precision, int *ncls) {
     if (!blob) return fail(nullptr, BUGSEG_EINVAL, "NULL blob");
-    bugseg_ctx c{Knobs()};                            // host state only (default knobs); nothing to free on the device
+    bugseg_ctx c{Knobs(), 0};                       // host state only (default knobs); nothing to free on the device
     c.prec = precision == BUGSEG_BF16 ? PREC_BF16 : precision == BUGSEG_F16 ? PREC_F16 : PREC_F32;
     std::string why;
     if (!parse_blob(blob, bytes, c.blocks, c.ncls, why)) return fail(nullptr, BUGSEG_EFORMAT, "weight blob: " + why);
@@ -2525,7 +2035,7 @@ int bugseg_debug_pool_indices(bugseg_ctx *ctx, int B, int H, int W, int block, v
     if (bytes != pl.idx_bytes[(size_t)block])
         return fail(ctx, BUGSEG_EINVAL, "index tensor is " + std::to_string(pl.idx_bytes[(size_t)block]) + " bytes");
     if (idx_cs) *idx_cs = cstore(ctx->blocks[(size_t)block].attrs[0]);
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     hipError_t e = hipMemcpyAsync(dst, pl.idx[(size_t)block], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("pool indices copy: ") + hipGetErrorString(e));
     return BUGSEG_OK;
@@ -2579,7 +2089,7 @@ int bugseg_debug_poison_arena(bugseg_ctx *ctx, int byte, void *stream) {
     if (!ctx) return fail(ctx, BUGSEG_EINVAL, "NULL ctx");
     Plan &pl = ctx->plan;
     if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     // activations and pooling indices; the range words after them are cleared by every forward
     hipError_t e = hipMemsetAsync(pl.arena, byte & 255, pl.act_bytes, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("poison arena: ") + hipGetErrorString(e));
@@ -2603,7 +2113,7 @@ int bugseg_debug_stage3_windows(int h, int y0, int y1, int n, const int32_t *blk
 int bugseg_debug_plan_windows(bugseg_ctx *ctx, int row0, int row1, int32_t *win) {
     if (!ctx || !win) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     if (!ctx->plan.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     const WinPlan *wp = window_plan(ctx, row0, row1);
     if (!wp) return 0;
     const int n = (int)ctx->plan.ops.size();
@@ -2623,7 +2133,7 @@ int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_
     // block in the spare buffer (written only when the pair was cut), its second where the pair writes
     const BneckLaunch *b = op >= 0 && op < (int)pl.ops.size() ? std::get_if<BneckLaunch>(&pl.ops[(size_t)op].fwd) : nullptr;
     if (!b || bytes != b->a.x_bytes) return fail(ctx, BUGSEG_EINVAL, "not a fused bottleneck launch, or not its output's size");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     hipError_t e = hipMemcpyAsync(dst_dev, b->a.out, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("read block output: ") + hipGetErrorString(e));
     return BUGSEG_OK;
@@ -2672,27 +2182,11 @@ int bugseg_debug_knobs(const bugseg_ctx *ctx, char *buf, int len) {
     return rc == BUGSEG_OK ? rc : fail(const_cast<bugseg_ctx *>(ctx), rc, err);
 }
 
-int bugseg_debug_polar_tables(int w, int h, int variant, int32_t *fmap, size_t fmap_n, int32_t *imap, size_t imap_n,
-                              int *pw_out, int *ph_out) {
-    if (w <= 0 || h <= 0 || w > 32767 || h > 32767) return fail(nullptr, BUGSEG_EINVAL, "bad grid");
-    const int L = std::max(w, h);
-    const int pw = variant ? w : (int)std::lrint((double)L);
-    const int ph = variant ? h : (int)std::lrint((double)L * 3.1415926535897932384626433832795);
-    if (ph > 32767) return fail(nullptr, BUGSEG_EINVAL, "grid too large for the polar tables");
-    std::vector<int32_t> f, im;
-    polar_tables(pw, ph, (double)L, (float)(w / 2.0 - 1), (float)h, w, h, f, im);
-    if (pw_out) *pw_out = pw;
-    if (ph_out) *ph_out = ph;
-    if (fmap) std::memcpy(fmap, f.data(), std::min(fmap_n, f.size()) * sizeof(int32_t));
-    if (imap) std::memcpy(imap, im.data(), std::min(imap_n, im.size()) * sizeof(int32_t));
-    return BUGSEG_OK;
-}
-
 int bugseg_plan_info(bugseg_ctx *ctx, int B, int H, int W, int out_kind, int bgr_input, int *n_launches, double *alg_bytes,
                      double *plan_bytes, double *flops) {
     if (!ctx) return fail(ctx, BUGSEG_EINVAL, "NULL ctx");
     if (!ctx->loaded) return fail(ctx, BUGSEG_ESTATE, "no weights loaded");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     std::string why;
     if (!build_plan(ctx, B, H, W, why)) return fail(ctx, BUGSEG_EINVAL, why);
     double lb = 0, pb = 0, fl = 0;
@@ -2769,7 +2263,7 @@ int bugseg_plan_launch_op(bugseg_ctx *ctx, int B, int H, int W, int op, void *st
     if (!pl.arena || pl.B != B || pl.H != H || pl.W != W || !pl.bound.in)
         return fail(ctx, BUGSEG_ESTATE, "no forward has run at these dimensions");
     if (op < 0 || op >= (int)pl.ops.size()) return fail(ctx, BUGSEG_EINVAL, "op index out of range");
-    DeviceGuard g(ctx->device);
+    DeviceGuard g(ctx->mem.device);
     hipError_t e = launch_op(ctx, op, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, "launch of op " + std::to_string(op) + ": " + hipGetErrorString(e));
     return BUGSEG_OK;

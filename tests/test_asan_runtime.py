@@ -1,6 +1,6 @@
 """Host ASan + UBSan over the native runtime's input-parsing paths (race /
-memory-error detection on the host C++ build). tests/asan/build.sh compiles the runtime's two
-translation units and tests/asan/asan_driver.cpp with host-only sanitizers; the driver feeds the BSG1
+memory-error detection on the host C++ build). tests/asan/build.sh compiles the host runtime's
+translation units (csrc/*.cpp) and tests/asan/asan_driver.cpp with host-only sanitizers; the driver feeds the BSG1
 weight-blob parser + BN folding + packing, the DeepLab plan validator and the polar-table builder
 with valid inputs, truncations and seeded corruptions. CPU only: no device is touched."""
 import os
