@@ -40,7 +40,8 @@ EXPORTED = ("bugseg_version", "bugseg_create", "bugseg_destroy", "bugseg_load_we
             "bugseg_dl_forward", "bugseg_dl_launch_op", "bugseg_dl_read_buffer", "bugseg_dl_last_error",
             "bugseg_dl_set_class_lut", "bugseg_dl_forward_classes", "bugseg_dl_classes_from_logits",
             "bugseg_debug_parse_pack", "bugseg_debug_polar_tables", "bugseg_debug_ctx_info", "bugseg_debug_tile_walk", "bugseg_debug_set_spans", "bugseg_debug_pool_indices",
-            "bugseg_dl_debug_check_plan", "bugseg_debug_knobs", "bugseg_dl_debug_knobs", "bugseg_debug_fused_forms")
+            "bugseg_dl_debug_check_plan", "bugseg_dl_debug_op_layout", "bugseg_dl_debug_plan_groups",
+            "bugseg_debug_knobs", "bugseg_dl_debug_knobs", "bugseg_debug_fused_forms")
 DL_OP_FIELDS = 32
 
 
@@ -187,6 +188,8 @@ def load_library(path: Path | str | None = None) -> ctypes.CDLL:
             "bugseg_debug_set_spans": (i, [vp, vp, i]),
             "bugseg_debug_pool_indices": (i, [vp, i, i, i, i, vp, sz, ctypes.POINTER(ctypes.c_int), vp]),
             "bugseg_dl_debug_check_plan": (i, [vp, i, vp, i, i, i, i, i, sz]),
+            "bugseg_dl_debug_op_layout": (i, [i, vp, i]),
+            "bugseg_dl_debug_plan_groups": (i, [vp, i, vp]),
             "bugseg_debug_knobs": (i, [vp, vp, i]),
             "bugseg_dl_debug_knobs": (i, [vp, vp, i]),
             "bugseg_debug_fused_forms": (i, [vp, i]),
@@ -221,6 +224,43 @@ def knobs(ctx=None, size: int = 4096, dl: bool = False) -> dict[str, int]:
     else:
         check(lib.bugseg_debug_knobs(ctx, buf, size), ctx)
     return {k: int(v) for k, v in (line.split("=") for line in buf.value.decode().splitlines())}
+
+
+def _dl_check(code: int) -> None:
+    """A host-only bugseg_dl_debug_* hook's return code (its message: bugseg_dl_last_error(NULL))."""
+    if code < 0:
+        msg = load_library().bugseg_dl_last_error(None).decode(errors="replace")
+        raise ValueError(msg) if code == EINVAL else BugsegError(code, msg)
+
+
+def dl_op_layout(kind: int) -> tuple[str, ...]:
+    """Test hook (bugseg_dl_debug_op_layout, host only): the executor's names of the fields after the kind in a
+    DeepLab op record of `kind` (csrc/deeplab_ops.h); deeplab_spec.OP_LAYOUT is the writer's copy."""
+    buf = ctypes.create_string_buffer(1024)
+    n = load_library().bugseg_dl_debug_op_layout(int(kind), buf, len(buf))
+    _dl_check(n)
+    names = tuple(buf.value.decode().split(","))
+    assert len(names) == n
+    return names
+
+
+def dl_check_plan(ops, buf_bytes, B: int, Hc: int, Wc: int, precision: int, w_bytes: int) -> None:
+    """Test hook (bugseg_dl_debug_check_plan, host only): bugseg_dl_set_plan's validation; ValueError with its text."""
+    import numpy as np
+    o = np.ascontiguousarray(ops, dtype=np.int32)
+    b = np.ascontiguousarray(buf_bytes, dtype=np.uint64)
+    _dl_check(load_library().bugseg_dl_debug_check_plan(o.ctypes.data, o.shape[0], b.ctypes.data, b.shape[0], B, Hc, Wc,
+                                                        precision, w_bytes))
+
+
+def dl_plan_groups(ops) -> list[int]:
+    """Test hook (bugseg_dl_debug_plan_groups, host only): per op, how many consecutive CONV ops from it a forward
+    issues as one launch (1: alone)."""
+    import numpy as np
+    o = np.ascontiguousarray(ops, dtype=np.int32)
+    runs = np.zeros(o.shape[0], np.int32)
+    _dl_check(load_library().bugseg_dl_debug_plan_groups(o.ctypes.data, o.shape[0], runs.ctypes.data))
+    return runs.tolist()
 
 
 FORM_COLS = ("kind", "precision", "C", "asym", "variant", "transposed", "cin", "windowed", "lut_kind", "threads",

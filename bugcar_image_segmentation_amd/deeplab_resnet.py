@@ -150,10 +150,10 @@ def lower_resnet(net: DeepLabResNet, B: int, bf16: bool, nb=None, fuse_prep: boo
     Hc, Wc = D.crop_hw(net)
     L.use(0, B * Hc * Wc * 8 * es)
     if not fuse_prep:
-        L.op([D.OP_PREP, 0], "prep", 0, B * Hc * Wc * (3 + 8 * es))
+        L.op(D.OP_PREP, "prep", 0, B * Hc * Wc * (3 + 8 * es), dst=0)
     r0, r1, r2 = net.root
     H, W = L.conv(r0, 0, Hc, Wc, 8, 3, _r8(r0.cout), tag="conv stem", rgb=fuse_prep, geom=_geom(r0, Hc, Wc))
-    if fuse_prep and int(L.ops[-1][31]) != 2:
+    if fuse_prep and D.field(L.ops[-1], "tap") != 2:
         raise ValueError("fuse_prep needs the tap-packed stem (3x3 over the 8-channel input)")
     H, W = L.conv(r1, 3, H, W, r0.cout, 4, r1.cout, tag="conv root", geom=_geom(r1, H, W))
     H, W = L.conv(r2, 4, H, W, r1.cout, 3, r2.cout, tag="conv root", geom=_geom(r2, H, W))

@@ -23,21 +23,14 @@ of the TF DeepLab model zoo (``mobilenet_v2``, depth multiplier 1, output stride
 Parity is UNPINNED against TF on the real deeplab.pb (neither exists here); the oracle is
 ``oracle/deeplab_oracle.py`` on the same synthetic weights.
 
-Op list (``lower``): int32 records of ``OP_FIELDS`` fields, interpreted by deeplab_runtime.cpp:
-  PREP   [1, dst]
-  CONV   [2, src, dst, res, Hin, Win, CS, Hout, Wout, kh, kw, stride, dil, pad_t, pad_l, cinP, NP,
-          w_off, b_off, act, res_cs, out_cs, out_off, cout, out_f32, bias_img_buf, bias_img_stride]
-  DW     [3, src, dst, Hin, Win, C, Hout, Wout, stride, dil, pad_t, pad_l, w_off, b_off, act, in_relu]
-  POOL   [4, src, part, z, H, W, C, CS, chunk_px, nchunks, cmid, cout, wp_off, bp_off, wq_off, bq_off, z_stride, y]
-  ARGMAX [5, logits, h, w, LCS, ncls]
-  RESIZE [6, src, dst, h, w, in_cs, C, Hout, Wout, out_cs, out_off]   (bilinear, align_corners; DeepLabV3+ decoder)
-  MAXPOOL [7, src, dst, Hin, Win, C, Hout, Wout, k, stride, pad_t, pad_l]   (ResNet root pool / subsample)
-CONV act: 0 none, 1 ReLU, 2 ReLU6 (before the residual add), 3 ReLU after the residual add (ResNet).
+Op list (``lower``): int32 records of ``OP_FIELDS`` fields, the kind first, then the fields ``OP_LAYOUT``
+names for that kind; the executor reads them through its own copy of the table (csrc/deeplab_ops.h).
 """
 from __future__ import annotations
 
+import dataclasses
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -45,6 +38,47 @@ import torch
 OP_FIELDS = 32
 OP_PREP, OP_CONV, OP_DW, OP_POOL, OP_ARGMAX, OP_RESIZE, OP_MAXPOOL = 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
+# The fields of a record after its kind, by kind. CONV: act 0 none, 1 ReLU, 2 ReLU6 (before the residual add),
+# 3 ReLU after the residual add (ResNet); res, bias_img, dw_w_off are -1 when absent; dw_w_off / dw_b_off /
+# dw_geom (stride | dil << 8 | pad_t << 16 | pad_l << 24) describe a depthwise conv run inside the operand
+# loads; nb: pixel fragments per wave; tap: 0 plain, 1 tap-packed (4 taps x 8 channels per k-step), 2
+# tap-packed reading the raw u8 frames. RESIZE: bilinear, align_corners (DeepLabV3+ decoder). MAXPOOL:
+# ResNet root pool / subsample.
+OP_LAYOUT = {
+    OP_PREP: ("dst",),
+    OP_CONV: ("src", "dst", "res", "Hin", "Win", "CS", "Hout", "Wout", "kh", "kw", "stride", "dil", "pad_t", "pad_l",
+              "cinP", "NP", "w_off", "b_off", "act", "res_cs", "out_cs", "out_off", "cout", "out_f32", "bias_img",
+              "bias_img_stride", "dw_w_off", "dw_b_off", "dw_geom", "nb", "tap"),
+    OP_DW: ("src", "dst", "Hin", "Win", "C", "Hout", "Wout", "stride", "dil", "pad_t", "pad_l", "w_off", "b_off", "act",
+            "in_relu"),
+    OP_POOL: ("src", "part", "z", "H", "W", "C", "CS", "chunk_px", "nchunks", "cmid", "cout", "wp_off", "bp_off",
+              "wq_off", "bq_off", "z_stride", "y"),
+    OP_ARGMAX: ("logits", "h", "w", "LCS", "ncls"),
+    OP_RESIZE: ("src", "dst", "h", "w", "in_cs", "C", "Hout", "Wout", "out_cs", "out_off"),
+    OP_MAXPOOL: ("src", "dst", "Hin", "Win", "C", "Hout", "Wout", "k", "stride", "pad_t", "pad_l"),
+}
+
+
+def field_pos(kind: int, name: str) -> int:
+    """Position of field `name` in a record of `kind` ("kind" itself: 0)."""
+    if int(kind) not in OP_LAYOUT:
+        raise ValueError(f"unknown op kind {int(kind)}")
+    if name == "kind":
+        return 0
+    if name not in OP_LAYOUT[int(kind)]:
+        raise ValueError(f"op kind {int(kind)} has no field {name!r}")
+    return 1 + OP_LAYOUT[int(kind)].index(name)
+
+
+def field(ops, name: str):
+    """Field `name` of one record, or its column (a view) of an (n, OP_FIELDS) array of records of one kind."""
+    ops = np.asarray(ops)
+    if name == "kind":
+        return ops[..., 0]
+    kinds = set(np.atleast_2d(ops)[:, 0].tolist())
+    if len(kinds) != 1:
+        raise ValueError(f"field {name!r} of records of kinds {sorted(kinds)}")
+    return ops[..., field_pos(kinds.pop(), name)]
 BN_EPS = 1e-3
 CROP = 513
 NUM_CLASSES = 21
@@ -108,7 +142,7 @@ class DeepLab:
     num_classes: int = NUM_CLASSES
     output_stride: int = 8
     crop: int = CROP             # crop height (the export's crop_size[0])
-    meta: dict = field(default_factory=dict)
+    meta: dict = dataclasses.field(default_factory=dict)
     crop_w: int = 0              # crop width when the export's crop is not square (0: = crop)
 
 
@@ -288,8 +322,13 @@ class Lowering:
     def use(self, buf, nbytes):
         self.need[buf] = max(self.need[buf], int(nbytes))
 
-    def op(self, rec, tag, flops, nbytes):
-        self.ops.append(list(rec) + [0] * (OP_FIELDS - len(rec)))
+    def op(self, kind, tag, flops, nbytes, **fields):
+        """One record of `kind`, its fields by name, laid out by OP_LAYOUT; all of them, and no others."""
+        names = OP_LAYOUT.get(kind)
+        if names is None or set(fields) != set(names):
+            raise ValueError(f"op kind {kind}: fields {sorted(fields)}, the layout has {names}")
+        rec = [kind] + [int(fields[n]) for n in names]
+        self.ops.append(rec + [0] * (OP_FIELDS - len(rec)))
         self.info["per_op"].append((tag, float(flops), float(nbytes)))
         self.info["flops"] += flops
         self.info["bytes"] += nbytes
@@ -305,15 +344,15 @@ class Lowering:
             Wo, pl = same_pad(W, k, c.stride, c.dil)
         else:
             Ho, pt, Wo, pl = geom
-        extra = [-1, -1, 0]
+        dw_w_off, dw_b_off, dw_geom = -1, -1, 0
         Hin, Win = H, W
         if dwf is not None:   # (dw conv, its input H, W): this 1x1 runs over the dw output grid
             d, Hin, Win = dwf
             Ho, dpt = same_pad(Hin, 3, d.stride, d.dil)
             Wo, dpl = same_pad(Win, 3, d.stride, d.dil)
             wd, bd = d.folded()
-            extra = [blob.add(wd.reshape(CS, 9).T, True), blob.add(bd.astype(np.float32), False),
-                     d.stride | d.dil << 8 | dpt << 16 | dpl << 24]
+            dw_w_off, dw_b_off = blob.add(wd.reshape(CS, 9).T, True), blob.add(bd.astype(np.float32), False)
+            dw_geom = d.stride | d.dil << 8 | dpt << 16 | dpl << 24
         tp = CS == 8 and dwf is None and k > 1
         wp, bias, cinP, NP = pack_conv(c, CS, self.bf16, tap_packed=tp)
         if zero_bias:
@@ -329,10 +368,12 @@ class Lowering:
             (B * Ho * Wo * cw * es if res >= 0 else 0) + wp.size * es
         t = tag if dwf is None else "conv dw+project"
         nb = self.nb
-        f30 = nb(t, Ho * Wo, cinP * k * k, cw) if callable(nb) else (nb or _pick_nb(t, Ho * Wo, cinP * k * k, cw, B))
-        self.op([OP_CONV, src, dst, res, Hin, Win, CS, Ho, Wo, k, k, c.stride, c.dil, pt, pl, cinP, NP, w_off, b_off,
-                 c.act, out_cs if res >= 0 else 0, out_cs, out_off, cw, int(out_f32), bias_img, bias_img_stride] +
-                extra + [f30, 2 if (rgb and tp) else int(tp)], t, flops, nbytes)
+        nb = nb(t, Ho * Wo, cinP * k * k, cw) if callable(nb) else (nb or _pick_nb(t, Ho * Wo, cinP * k * k, cw, B))
+        self.op(OP_CONV, t, flops, nbytes, src=src, dst=dst, res=res, Hin=Hin, Win=Win, CS=CS, Hout=Ho, Wout=Wo, kh=k, kw=k,
+                stride=c.stride, dil=c.dil, pad_t=pt, pad_l=pl, cinP=cinP, NP=NP, w_off=w_off, b_off=b_off, act=c.act,
+                res_cs=out_cs if res >= 0 else 0, out_cs=out_cs, out_off=out_off, cout=cw, out_f32=out_f32,
+                bias_img=bias_img, bias_img_stride=bias_img_stride, dw_w_off=dw_w_off, dw_b_off=dw_b_off, dw_geom=dw_geom,
+                nb=nb, tap=2 if (rgb and tp) else int(tp))
         return Ho, Wo
 
     def dw(self, d: Conv, src, dst, H, W, C, in_relu=False, geom=None, tag="dw"):
@@ -347,8 +388,9 @@ class Lowering:
         w_off = self.blob.add(wd.reshape(C, 9).T, True)   # [9][C] in the compute type
         b_off = self.blob.add(bd.astype(np.float32), False)
         self.use(dst, B * Ho * Wo * C * es)
-        self.op([OP_DW, src, dst, H, W, C, Ho, Wo, d.stride, d.dil, pt, pl, w_off, b_off, d.act, int(in_relu)], tag,
-                2.0 * B * Ho * Wo * C * 9, B * (H * W + Ho * Wo) * C * es)
+        self.op(OP_DW, tag, 2.0 * B * Ho * Wo * C * 9, B * (H * W + Ho * Wo) * C * es, src=src, dst=dst, Hin=H, Win=W, C=C,
+                Hout=Ho, Wout=Wo, stride=d.stride, dil=d.dil, pad_t=pt, pad_l=pl, w_off=w_off, b_off=b_off, act=d.act,
+                in_relu=in_relu)
         return Ho, Wo
 
     def maxpool(self, src, dst, H, W, C, k, s, tag="maxpool"):
@@ -361,8 +403,8 @@ class Lowering:
             Ho, pt = same_pad(H, k, s, 1)
             Wo, pl = same_pad(W, k, s, 1)
         self.use(dst, B * Ho * Wo * C * es)
-        self.op([OP_MAXPOOL, src, dst, H, W, C, Ho, Wo, k, s, pt, pl], tag, float(B * Ho * Wo * C * k * k),
-                B * (H * W + Ho * Wo) * C * es)
+        self.op(OP_MAXPOOL, tag, float(B * Ho * Wo * C * k * k), B * (H * W + Ho * Wo) * C * es, src=src, dst=dst, Hin=H,
+                Win=W, C=C, Hout=Ho, Wout=Wo, k=k, stride=s, pad_t=pt, pad_l=pl)
         return Ho, Wo
 
     def aspp_pool(self, net, src, h, w, C, part=8, z=9, y=10):
@@ -381,8 +423,9 @@ class Lowering:
         bp_off = self.blob.add(bpool.astype(np.float32), False)
         wq_off = self.blob.add(_round(wproj.reshape(D, -1)[:, :D], self.bf16), False)     # [D (out)][D (pooled ch)]
         bq_off = self.blob.add(bproj.astype(np.float32), False)
-        self.op([OP_POOL, src, part, z, h, w, C, C, chunk, nch, D, D, wp_off, bp_off, wq_off, bq_off, zs, y], "pool",
-                2.0 * B * (D * C + D * D) + B * h * w * C, B * h * w * C * es)
+        self.op(OP_POOL, "pool", 2.0 * B * (D * C + D * D) + B * h * w * C, B * h * w * C * es, src=src, part=part, z=z,
+                H=h, W=w, C=C, CS=C, chunk_px=chunk, nchunks=nch, cmid=D, cout=D, wp_off=wp_off, bp_off=bp_off,
+                wq_off=wq_off, bq_off=bq_off, z_stride=zs, y=y)
         return zs
 
     def projection_conv(self, net):
@@ -394,11 +437,12 @@ class Lowering:
     def resize(self, src, dst, h, w, in_cs, C, Ho, Wo, out_cs, out_off):
         es = self.es
         self.use(dst, self.B * Ho * Wo * out_cs * es)
-        self.op([OP_RESIZE, src, dst, h, w, in_cs, C, Ho, Wo, out_cs, out_off], "resize", 8.0 * self.B * Ho * Wo * C,
-                self.B * (h * w + Ho * Wo) * C * es)
+        self.op(OP_RESIZE, "resize", 8.0 * self.B * Ho * Wo * C, self.B * (h * w + Ho * Wo) * C * es, src=src, dst=dst,
+                h=h, w=w, in_cs=in_cs, C=C, Hout=Ho, Wout=Wo, out_cs=out_cs, out_off=out_off)
 
     def argmax(self, logits, h, w, LCS, ncls, Hc, Wc):
-        self.op([OP_ARGMAX, logits, h, w, LCS, ncls], "argmax", 0, self.B * (h * w * LCS * 4 + Hc * Wc * 8))
+        self.op(OP_ARGMAX, "argmax", 0, self.B * (h * w * LCS * 4 + Hc * Wc * 8), logits=logits, h=h, w=w, LCS=LCS,
+                ncls=ncls)
 
     def result(self):
         self.info["nops"] = len(self.ops)
@@ -410,11 +454,10 @@ def lower(net, B: int, bf16: bool, fuse_dw: bool = False, nb=None, fuse_prep: bo
     Buffers: 0 input, 1/2 block ping-pong, 3 expanded, 4 depthwise out, 5 ASPP concat, 6 projection,
     7 logits (f32), 8 pooling partials (f32), 9 per-image projection bias (f32), 10 image-pooling
     branch output (f32).
-    nb: pixel fragments per wave of the conv kernel (CONV field 30): 2 or 4, a callable
+    nb: pixel fragments per wave of the conv kernel (CONV field nb): 2 or 4, a callable
     (tag, Hout * Wout, K, cout) -> 2 | 4, or None for the measured default (_pick_nb).
     fuse_dw: each block's depthwise conv runs inside its projection's operand loads (CONV fields
-    27-29: dw weight / bias offsets, stride | dil << 8 | pad_t << 16 | pad_l << 24; field 31: the
-    stem's tap packing, 4 taps x 8 channels per k-step); bit-identical to
+    dw_w_off, dw_b_off, dw_geom); bit-identical to
     the default plan (separate DW ops through buffer 4) but measured 2.4x slower (5.1 vs 2.2 ms per
     16-frame forward for the pair): the 9 tap loads of every operand chunk serialise ahead of the
     MFMAs and are recomputed for every 64-channel output tile.
@@ -435,10 +478,10 @@ def lower(net, B: int, bf16: bool, fuse_dw: bool = False, nb=None, fuse_prep: bo
     Hc, Wc = crop_hw(net)
     L.use(0, B * Hc * Wc * 8 * es)
     if not fuse_prep:
-        L.op([OP_PREP, 0], "prep", 0, B * Hc * Wc * (3 + 8 * es))
+        L.op(OP_PREP, "prep", 0, B * Hc * Wc * (3 + 8 * es), dst=0)
     # stem
     H, W = L.conv(net.stem, 0, Hc, Wc, 8, 1, _r8(net.stem.cout), tag="conv stem", rgb=fuse_prep)
-    if fuse_prep and int(L.ops[-1][31]) != 2:
+    if fuse_prep and field(L.ops[-1], "tap") != 2:
         raise ValueError("fuse_prep needs the tap-packed stem (3x3 over the 8-channel input)")
     C = net.stem.cout
     cur = 1

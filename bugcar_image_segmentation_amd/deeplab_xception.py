@@ -195,7 +195,7 @@ def lower_xception(net: DeepLabXception, B: int, bf16: bool, nb=None, fuse_prep:
     Hc, Wc = D.crop_hw(net)
     L.use(0, B * Hc * Wc * 8 * es)
     if not fuse_prep:
-        L.op([D.OP_PREP, 0], "prep", 0, B * Hc * Wc * (3 + 8 * es))
+        L.op(D.OP_PREP, "prep", 0, B * Hc * Wc * (3 + 8 * es), dst=0)
 
     def geom(c: Conv, H, W):
         Ho, pt = xgeom(H, c.k, c.stride, c.dil)
@@ -204,7 +204,7 @@ def lower_xception(net: DeepLabXception, B: int, bf16: bool, nb=None, fuse_prep:
 
     r0, r1 = net.root
     H, W = L.conv(r0, 0, Hc, Wc, 8, 2, _r8(r0.cout), tag="conv stem", rgb=fuse_prep, geom=geom(r0, Hc, Wc))
-    if fuse_prep and int(L.ops[-1][31]) != 2:
+    if fuse_prep and D.field(L.ops[-1], "tap") != 2:
         raise ValueError("fuse_prep needs the tap-packed stem (3x3 over the 8-channel input)")
     H, W = L.conv(r1, 2, H, W, r0.cout, 1, r1.cout, tag="conv root", geom=geom(r1, H, W))
     cur, C = 1, r1.cout

@@ -597,17 +597,26 @@ int bugseg_debug_pool_indices(bugseg_ctx *ctx, int B, int H, int W, int block, v
  * The graph builder is host code (deeplab_spec.py): it folds batch-norm, packs the weights into
  * one blob (bugseg_dl_load_weights) and lowers the network to a flat op list over numbered
  * activation buffers for one batch size and crop (bugseg_dl_set_plan). Op records are
- * BUGSEG_DL_OP_FIELDS int32 each; kinds and field meanings are documented in deeplab_spec.py
- * (lower()) and validated here against the buffers and the blob before the plan is accepted. */
+ * BUGSEG_DL_OP_FIELDS int32 each: the kind, then that kind's fields in the order of
+ * deeplab_spec.OP_LAYOUT (the executor's copy of the table is csrc/deeplab_ops.h, and
+ * bugseg_dl_debug_op_layout reports it); unused trailing fields are 0. A plan is validated against
+ * the buffers and the blob before it is accepted. */
 #define BUGSEG_DL_OP_FIELDS 32
 typedef struct bugseg_dl bugseg_dl;
 
 int bugseg_dl_create(int device, int precision, bugseg_dl **out);
 int bugseg_dl_destroy(bugseg_dl *dl);
-/* weight blob in HOST memory (bf16 / f32 per the precision, as packed by deeplab_spec.pack) */
+/* weight blob in HOST memory (bf16 / f32 per the precision, as packed by deeplab_spec.pack). Loading
+ * drops the current plan (its offsets belong to the old blob). If the upload fails (ENOMEM / EHIP) the
+ * context holds no weights and no plan, as when it was created. */
 int bugseg_dl_load_weights(bugseg_dl *dl, const void *blob, size_t bytes);
 /* ops: nops * BUGSEG_DL_OP_FIELDS int32; buf_bytes[nbufs]: arena layout; B frames of at most
- * Hc x Wc (the crop size: 513 for the standard export) */
+ * Hc x Wc (the crop size: 513 for the standard export). A plan that fails validation (EINVAL) leaves
+ * the current plan in force. A valid one replaces it whole, the last forward's logits and I/O with
+ * it; if its arena cannot be allocated (ENOMEM) the context is left with no plan: every forward is
+ * ESTATE until a set_plan succeeds. Memory a captured graph reads (the arena and weights of a forward,
+ * classes_from_logits or launch_op issued on a capturing stream) is kept until bugseg_dl_destroy when
+ * it is replaced, so such a graph stays replayable across set_plan and load_weights. */
 int bugseg_dl_set_plan(bugseg_dl *dl, const int32_t *ops, int nops, const uint64_t *buf_bytes, int nbufs,
                        int B, int Hc, int Wc);
 /* rgb_dev: (B, H, W, 3) u8 RGB, H <= Hc, W <= Wc (padded with the mean pixel to the crop, as the
@@ -647,6 +656,12 @@ int bugseg_dl_debug_knobs(const bugseg_dl *dl, char *buf, int len);
  * errors go to bugseg_dl_last_error(NULL). */
 int bugseg_dl_debug_check_plan(const int32_t *ops, int nops, const uint64_t *buf_bytes, int nbufs, int B, int Hc, int Wc,
                                int precision, size_t w_bytes);
+/* Test hook (host only): the comma-separated names of the fields that follow the kind in a record of
+ * `kind`, NUL-terminated in buf[len] -> their count; EINVAL for an unknown kind or a short buffer. */
+int bugseg_dl_debug_op_layout(int kind, char *buf, int len);
+/* Test hook (host only): len[i] = the number of consecutive CONV ops from op i that a forward issues as
+ * one launch (1: alone; the members after the first report 1). Only groups: nothing is validated. */
+int bugseg_dl_debug_plan_groups(const int32_t *ops, int nops, int32_t *len);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,8 @@ int main(int argc, char **argv) {
         std::vector<uint64_t> bc(b.begin(), b.begin() + n_bufs);
         tally(bugseg_dl_debug_check_plan(oc.data(), n_ops, bc.data(), n_bufs, B, Hc, Wc, prec,
                                          rng.below(4) ? w_bytes : (size_t)rng.below((uint32_t)w_bytes + 1)));
+        std::vector<int32_t> runs(n_ops);                  // the grouping validates nothing: any record must be safe
+        tally(bugseg_dl_debug_plan_groups(oc.data(), n_ops, runs.data()));
     }
     tally(bugseg_dl_debug_check_plan(nullptr, nops, bufs.data(), nbufs, B, Hc, Wc, prec, w_bytes));
     tally(bugseg_dl_debug_check_plan(ops.data(), 0, bufs.data(), nbufs, B, Hc, Wc, prec, w_bytes));

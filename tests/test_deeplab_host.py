@@ -34,22 +34,23 @@ def test_lowering_is_consistent():
     net = S.build_deeplab(atrous_rates=(12, 24, 36))
     blob, ops, bufs, info = S.lower(net, 2, bf16=True)
     assert ops.shape == (info["nops"], S.OP_FIELDS) and ops.dtype == np.int32
-    kinds = list(ops[:, 0])
+    kinds = list(S.field(ops, "kind"))
     assert kinds[0] == S.OP_CONV and kinds[-1] == S.OP_ARGMAX and kinds.count(S.OP_POOL) == 1
-    assert ops[0, 31] == 2 and S.OP_PREP not in kinds          # preprocessing fused into the stem's loads
+    assert S.field(ops[0], "tap") == 2 and S.OP_PREP not in kinds          # preprocessing fused into the stem's loads
     _, ops_p, _, info_p = S.lower(net, 2, bf16=True, fuse_prep=False)
-    assert ops_p[0, 0] == S.OP_PREP and ops_p[1, 31] == 1 and info_p["nops"] == info["nops"] + 1
+    assert S.field(ops_p[0], "kind") == S.OP_PREP and S.field(ops_p[1], "tap") == 1 and info_p["nops"] == info["nops"] + 1
     assert kinds.count(S.OP_DW) == 17
     _, ops_f, _, info_f = S.lower(net, 2, bf16=True, fuse_dw=True)
-    assert list(ops_f[:, 0]).count(S.OP_DW) == 0 and info["nops"] == info_f["nops"] + 17
+    assert list(S.field(ops_f, "kind")).count(S.OP_DW) == 0 and info["nops"] == info_f["nops"] + 17
     assert [t for t, _, _ in info_f["per_op"]].count("conv dw+project") == 17
     assert info["bytes"] > info_f["bytes"] and info["flops"] == info["flops"]
-    conv = ops[ops[:, 0] == S.OP_CONV]
-    assert np.all(conv[:, 17] % 256 == 0) and np.all(conv[:, 17] < len(blob))   # weight offsets aligned, inside
-    assert np.all(conv[:, 15] % 32 == 0) and np.all(conv[:, 16] % 64 == 0)
+    conv = ops[S.field(ops, "kind") == S.OP_CONV]
+    w_off = S.field(conv, "w_off")
+    assert np.all(w_off % 256 == 0) and np.all(w_off < len(blob))   # weight offsets aligned, inside
+    assert np.all(S.field(conv, "cinP") % 32 == 0) and np.all(S.field(conv, "NP") % 64 == 0)
     # the ASPP branches write disjoint channel ranges of the concat buffer
-    cat = conv[conv[:, 2] == 5]
-    assert sorted(cat[:, 22]) == [0, 256, 512, 768] and np.all(cat[:, 21] == 1024)
+    cat = conv[S.field(conv, "dst") == 5]
+    assert sorted(S.field(cat, "out_off")) == [0, 256, 512, 768] and np.all(S.field(cat, "out_cs") == 1024)
     assert info["feature"] == (65, 65) and info["lcs"] == 24
     assert len(bufs) == 11 and bufs.min() > 0
     # MACs: ~8.5 GMAC/frame at 513 with the zoo head, plus the three dense atrous branches
@@ -122,7 +123,7 @@ def test_non_square_crop_lowering_and_weight_file(tmp_path):
     net = S.build_deeplab(width=0.25, crop=(65, 97))
     assert S.crop_hw(net) == (65, 97)
     _, ops, bufs, info = S.lower(net, 2, bf16=False)
-    assert tuple(ops[0, 4:6]) == (65, 97)                  # stem input H, W = the crop
+    assert (S.field(ops[0], "Hin"), S.field(ops[0], "Win")) == (65, 97)                  # stem input H, W = the crop
     assert info["feature"] == (S.feature_size(net, 65), S.feature_size(net, 97))
     p = tmp_path / "dl.npz"
     S.save(net, p)
@@ -153,10 +154,10 @@ def test_resnet_structure_and_lowering():
     assert sum(u.shortcut is not None for u in net.units) == 4                 # first unit of every block
     assert R.feature_size(net, 513) == 33
     blob, ops, bufs, info = S.lower(net, 2, True)
-    kinds = [int(o[0]) for o in ops]
+    kinds = [int(S.field(o, "kind")) for o in ops]
     assert kinds.count(S.OP_MAXPOOL) == 1 + 2                                  # root pool + 2 subsamples
-    post = [o for o in ops if int(o[0]) == S.OP_CONV and int(o[19]) == 3]
-    assert len(post) == 33 and all(int(o[3]) >= 0 for o in post)             # every unit: residual, ReLU after
+    post = [o for o in ops if int(S.field(o, "kind")) == S.OP_CONV and int(S.field(o, "act")) == 3]
+    assert len(post) == 33 and all(int(S.field(o, "res")) >= 0 for o in post)             # every unit: residual, ReLU after
     assert info["feature"] == (33, 33) and int(bufs[7]) >= 2 * 33 * 33 * info["lcs"] * 4
 
 

@@ -300,7 +300,7 @@ def test_resnet_fp32_small(gpu, depth, units, os_, rates, B, H, W, crop):
     (output stride 16 and 8, multi-grid block 4), dense atrous ASPP; an even, non-square crop."""
     net = R.build_deeplab_resnet(depth=depth, width=0.25, units=units, crop=crop, output_stride=os_, atrous_rates=rates)
     model = DeepLabV3(net=net, precision="fp32")
-    assert any(int(o[0]) == S.OP_MAXPOOL for o in S.lower(net, B, False)[1])
+    assert any(int(S.field(o, "kind")) == S.OP_MAXPOOL for o in S.lower(net, B, False)[1])
     _check_fp32(model, net, _frames(B, H, W, 21 + H), torch.float64)
 
 
