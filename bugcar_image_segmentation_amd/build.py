@@ -18,9 +18,9 @@ CSRC = PKG / "csrc"
 OBJ = PKG / "_build"
 LIB = PKG / "libbugseg.so"
 SOURCES = ["conv_kernels.hip", "cls_kernels.hip", "init_kernels.hip", "bneck_kernels.hip", "bneck2_kernels.hip", "up_kernels.hip", "prep_kernels.hip",
-           "bev_kernels.hip", "deeplab_kernels.hip", "road_kernels.hip", "clahe_kernels.hip", "canny_kernels.hip", "eval_kernels.hip", "hough_kernels.hip", "quad_kernels.hip", "map_kernels.hip", "bugseg_runtime.cpp", "ctx_memory.cpp", "bev_runtime.cpp", "deeplab_runtime.cpp"]
+           "bev_kernels.hip", "deeplab_kernels.hip", "road_kernels.hip", "clahe_kernels.hip", "canny_kernels.hip", "eval_kernels.hip", "hough_kernels.hip", "quad_kernels.hip", "map_kernels.hip", "bugseg_runtime.cpp", "enet_weights.cpp", "ctx_memory.cpp", "bev_runtime.cpp", "deeplab_runtime.cpp"]
 # (bneck_pair_kernels.hip is compiled within bneck_kernels.hip, which includes it at its end)
-HEADERS = [CSRC / "bneck_pair_kernels.hip", CSRC / "bugseg_internal.h", CSRC / "ctx_memory.h", CSRC / "bev_runtime.h", CSRC / "deeplab_internal.h", CSRC / "deeplab_ops.h", CSRC / "knobs.h", CSRC / "mfma_common.h", CSRC / "cls_common.h", CSRC / "ccl_common.h", ROOT / "include" / "bugseg.h"]
+HEADERS = [CSRC / "bneck_pair_kernels.hip", CSRC / "bugseg_internal.h", CSRC / "enet_weights.h", CSRC / "ctx_memory.h", CSRC / "bev_runtime.h", CSRC / "deeplab_internal.h", CSRC / "deeplab_ops.h", CSRC / "knobs.h", CSRC / "mfma_common.h", CSRC / "cls_common.h", CSRC / "ccl_common.h", ROOT / "include" / "bugseg.h"]
 ARCH = os.environ.get("BUGSEG_OFFLOAD_ARCH", "gfx950")
 # per-source code-generation options. The class layer: MFMA results in ordinary VGPRs instead of AGPRs
 # (removes the accumulator copies in and out of AGPRs; round 6, fp32 B = 64: 113.6 -> 107.5 us per launch;

@@ -26,9 +26,7 @@ enum Epi {
     EPI_COUNT = 8
 };
 
-enum Prec { PREC_F32 = 0, PREC_BF16 = 1, PREC_F16 = 2 };
-// bytes per stored element: fp32 parity mode 4; bf16 / f16 storage modes 2
-inline constexpr int prec_es(int prec) { return prec == PREC_F32 ? 4 : 2; }
+// (enum Prec and prec_es: knobs.h)
 
 // ---- fp32 mode: range scaling of the split-f16 operands (round 5; mfma_common.h "range scaling").
 // The fp32 mode's products take f16 hi / lo parts (|v| < 65504, full precision for |v| >= 2^-3), so
@@ -48,8 +46,6 @@ struct RangeArgs {
     float n[3], c[3];       // internal tensors: |t_i| <= n[i] * |t_(i-1)| + c[i], t_(-1) = the input
     int off;                // !Knobs::f32_range: no scaling
 };
-// weight exponent of a matrix whose largest |w| is m (the measured-tensor window of the kernels)
-int range_weight_exp(double m);
 hipError_t launch_amax(const float *x, size_t n, float *slots, hipStream_t s);
 
 struct ConvArgs {

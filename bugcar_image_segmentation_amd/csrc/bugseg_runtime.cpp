@@ -3,9 +3,7 @@
 // Replaces what the reference gets from the TensorFlow C++ runtime (GraphDef import + Session
 // executor, models.py:21-44) and from OpenCV (resize / warpPerspective / morphology / resize-NN,
 // models.py:87-89, bev.py:182-212):
-//   * parses the BSG1 weight blob (enet_spec.py), folds batch-norm into the convolutions in double,
-//     packs every convolution for the MFMA kernels ([Npad][Kpad] rows, 8-channel k groups, tap
-//     table) and uploads all of it in ONE device allocation;
+//   * uploads the parsed and packed BSG1 weight blob (enet_weights.h) in ONE device allocation;
 //   * expands the ENet block list into a launch plan per (B, H, W): one fused conv launch per
 //     convolution (89 for canonical ENet), ping-pong activation buffers + per-downsample pooling
 //     indices carved from ONE device arena, sized for the batch (HBM is 288 GB: the arena for
@@ -23,6 +21,7 @@
 #include <variant>
 
 #include "bugseg_internal.h"
+#include "enet_weights.h"
 #include "bev_runtime.h"
 #include "../../include/bugseg.h"
 
@@ -102,52 +101,9 @@ int bugseg::dump_knobs(const Knobs *k, char *buf, int len, std::string &err) {
     return BUGSEG_OK;
 }
 
-// the weights' exponent for the fp32 mode's split-f16 products: 0 while the largest |w| lies in the
-// kernels' measured window [2^-2, 2^15) (mfma_common.h rng_exp_meas), else the exponent that brings it
-// to [2^14, 2^15), clamped as the kernels clamp
-int bugseg::range_weight_exp(double m) {
-    if (!(m > 0) || !std::isfinite(m)) return 0;
-    int e = 0;
-    (void)std::frexp(m, &e);
-    const int l = e - 1;
-    if (l >= -2 && l < 15) return 0;
-    return std::max(-40, std::min(40, 14 - l));   // (mfma_common.h RNG_EMAX)
-}
-
 namespace {
 
 thread_local std::string g_thread_err;
-
-struct UnitDesc {
-    int kind = 0, cout = 0, cin = 0, kh = 0, kw = 0, stride = 1, pad_h = 0, pad_w = 0, dil_h = 1, dil_w = 1, out_pad = 0;
-    float eps = 0.f;
-    std::vector<float> w, b, gamma, beta, mean, var, slope;
-};
-
-struct BlockDesc {
-    int type = 0;
-    int attrs[8] = {0};
-    std::vector<UnitDesc> units;
-    std::vector<std::vector<float>> extra;
-};
-
-enum { BT_INITIAL = 1, BT_REGULAR = 2, BT_DOWN = 3, BT_UP = 4, BT_FULLCONV = 5 };
-
-// One packed convolution launch (weights resident on the device).
-struct Packed {
-    int Npad = 0, Kpad = 0, Ksteps = 0, nr = 0;
-    int CinS = 0;      // input storage channels
-    int stride = 1;    // on the GEMM grid
-    int cout = 0;      // valid output channels (per phase)
-    int coutP = 0;     // per-phase padded channels
-    int phases = 1;
-    double macs_per_px = 0;   // MACs per GEMM pixel (flop accounting)
-    size_t o_w = 0, o_gtab = 0, o_bias = 0, o_s1 = 0, o_s2 = 0, o_ps = 0;
-    // fp32 mode range scaling (bugseg_internal.h RangeArgs): the weights' exponent (packed w = w * 2^sw)
-    // and per packed row the bound terms of its activated output: sum |w|, |bias|, max(1, |slope|)
-    int sw = 0;
-    std::vector<float> rabs, rbias, rslope;
-};
 
 // One kernel launch of the plan: which launch_* it goes to, that call's dispatch arguments and its argument
 // struct. Everything but span and rev (issue) and the forward's bindings (bind) is final once the plan is built.
@@ -295,15 +251,10 @@ struct Plan {
     bool cls_ok = false, cls_on = false;
     Launch cls_fused, cls_fused_fwd;
     Binding bound;           // the last forward's binding (in == nullptr: none since the plan was built)
+    // A context's plan is a complete plan for its (B, H, W) or Plan(), never a mixture (build_plan)
+    bool empty() const { return !arena; }
+    bool at(int b, int h, int w) const { return arena && B == b && H == h && W == w; }
 };
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-inline int pow2_nr(int npad) {   // 16-row fragments, rounded up to 1, 2, 4 or 8
-    int nr = npad / 16;
-    int p = 1;
-    while (p < nr) p <<= 1;
-    return p;
-}
 
 }  // namespace
 
@@ -317,13 +268,10 @@ struct bugseg_ctx {
     unsigned long long *spans = nullptr;           // bugseg_debug_set_spans: 512 u64 of launch-span slots per op, or null
     int spans_ops = 0;                             // ... for ops [0, spans_ops) only (the caller's buffer size)
     std::string err;
+    // the model: the blob parsed and packed (enet_weights.h) and the device copy of its staging image, installed
+    // together by bugseg_load_weights; loaded == false: w is empty and dev_w null
     bool loaded = false;
-    int ncls = 0;
-    std::vector<BlockDesc> blocks;
-    // packed weights: host staging + one device allocation
-    std::vector<Packed> packed;
-    std::vector<std::vector<int>> block_convs;     // per block: indices into packed
-    std::vector<unsigned char> host_w;
+    EnetWeights w;
     void *dev_w = nullptr;
     void *dev_luts = nullptr;                      // [0..15] lut3, [16..31] binary, then 3x256 f64 norm lut
     Plan plan;
@@ -340,460 +288,6 @@ int fail(bugseg_ctx *c, int code, const std::string &m) {
     if (c) c->err = m;
     else g_thread_err = m;
     return code;
-}
-
-// ---------------------------------------------------------------- blob parsing
-struct Reader {
-    const unsigned char *p, *end;
-    bool ok = true;
-    template <typename T> T get() {
-        T v{};
-        if (p + sizeof(T) > end) { ok = false; return v; }
-        std::memcpy(&v, p, sizeof(T));
-        p += sizeof(T);
-        return v;
-    }
-    std::vector<float> tensor() {
-        uint32_t n = get<uint32_t>();
-        std::vector<float> v;
-        if (!ok || (size_t)(end - p) / 4 < (size_t)n) { ok = false; return v; }   // (no pointer past the end)
-        v.resize(n);
-        if (n) std::memcpy(v.data(), p, (size_t)n * 4);   // (memcpy from / to NULL is UB even for 0 bytes)
-        p += (size_t)n * 4;
-        return v;
-    }
-};
-
-bool parse_blob(const void *blob, size_t bytes, std::vector<BlockDesc> &out, int &ncls, std::string &why) {
-    Reader r{(const unsigned char *)blob, (const unsigned char *)blob + bytes};
-    char magic[4];
-    for (int i = 0; i < 4; ++i) magic[i] = r.get<char>();
-    if (!r.ok || std::memcmp(magic, "BSG1", 4) != 0) { why = "bad magic (expected BSG1)"; return false; }
-    uint32_t ver = r.get<uint32_t>(), nb = r.get<uint32_t>(), nc = r.get<uint32_t>();
-    if (!r.ok || ver != 1) { why = "unsupported blob version"; return false; }
-    if (nb == 0 || nb > 4096 || nc == 0 || nc > 16) { why = "bad block/class count"; return false; }
-    ncls = (int)nc;
-    for (uint32_t b = 0; b < nb; ++b) {
-        BlockDesc bd;
-        bd.type = (int)r.get<uint32_t>();
-        for (int i = 0; i < 8; ++i) bd.attrs[i] = r.get<int32_t>();
-        uint32_t nu = r.get<uint32_t>();
-        if (!r.ok || nu > 16) { why = "bad unit count"; return false; }
-        for (uint32_t u = 0; u < nu; ++u) {
-            UnitDesc ud;
-            int32_t iv[11];
-            for (int i = 0; i < 11; ++i) iv[i] = r.get<int32_t>();
-            ud.kind = iv[0]; ud.cout = iv[1]; ud.cin = iv[2]; ud.kh = iv[3]; ud.kw = iv[4]; ud.stride = iv[5];
-            ud.pad_h = iv[6]; ud.pad_w = iv[7]; ud.dil_h = iv[8]; ud.dil_w = iv[9]; ud.out_pad = iv[10];
-            ud.eps = r.get<float>();
-            ud.w = r.tensor(); ud.b = r.tensor(); ud.gamma = r.tensor(); ud.beta = r.tensor();
-            ud.mean = r.tensor(); ud.var = r.tensor(); ud.slope = r.tensor();
-            if (!r.ok) { why = "truncated unit"; return false; }
-            if (ud.cout <= 0 || ud.cin <= 0 || ud.kh <= 0 || ud.kw <= 0 || ud.cout > 128 || ud.cin > 128 || ud.kh > 7 || ud.kw > 7) {
-                why = "unit dims out of range"; return false;
-            }
-            const size_t nw = (size_t)ud.cout * ud.cin * ud.kh * ud.kw;
-            const size_t c = (size_t)ud.cout;
-            if (ud.w.size() != nw || ud.b.size() != c || ud.gamma.size() != c || ud.beta.size() != c ||
-                ud.mean.size() != c || ud.var.size() != c || ud.slope.size() != c) {
-                why = "unit tensor size mismatch"; return false;
-            }
-            bd.units.push_back(std::move(ud));
-        }
-        uint32_t ne = r.get<uint32_t>();
-        if (!r.ok || ne > 16) { why = "bad extra count"; return false; }
-        for (uint32_t e = 0; e < ne; ++e) bd.extra.push_back(r.tensor());
-        if (!r.ok) { why = "truncated extras"; return false; }
-        out.push_back(std::move(bd));
-    }
-    return true;
-}
-
-// ---------------------------------------------------------------- packing
-// IEEE binary16 bits of a finite float, round to nearest even (the fp16-storage mode's weights);
-// overflow to +-inf, underflow through the subnormals to +-0 — as a (_Float16) cast does
-uint16_t f32_to_f16(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const int32_t exp = (int32_t)((u >> 23) & 0xff) - 127 + 15;
-    uint32_t man = u & 0x7fffffu;
-    if (((u >> 23) & 0xff) == 0xff) return (uint16_t)(sign | 0x7c00u | (man ? 0x200u : 0u));   // inf / nan
-    if (exp >= 31) return (uint16_t)(sign | 0x7c00u);
-    if (exp <= 0) {                                  // subnormal half (or zero)
-        if (exp < -10) return (uint16_t)sign;
-        man |= 0x800000u;
-        const int shift = 14 - exp;                  // 24-bit significand -> 10 + exp bits
-        uint32_t h = man >> shift;
-        const uint32_t rem = man & ((1u << shift) - 1), half = 1u << (shift - 1);
-        if (rem > half || (rem == half && (h & 1u))) ++h;
-        return (uint16_t)(sign | h);
-    }
-    uint32_t h = ((uint32_t)exp << 10) | (man >> 13);
-    const uint32_t rem = man & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;   // may carry into the exponent (-> inf): correct
-    return (uint16_t)(sign | h);
-}
-// the float value of IEEE binary16 bits (exact)
-float f16_to_f32(uint16_t h) {
-    const float s = (h & 0x8000u) ? -1.f : 1.f;
-    const int e = (h >> 10) & 31, m = h & 1023;
-    if (e == 31) return m ? std::nanf("") : s * INFINITY;
-    if (e == 0) return s * std::ldexp((float)m, -24);
-    return s * std::ldexp((float)(m | 1024), e - 25);
-}
-
-struct Packer {
-    int prec;
-    bool range;   // fp32 with Knobs::f32_range: the packed matrices carry a weight exponent (range_stats)
-    std::vector<unsigned char> &buf;
-    size_t push(const void *d, size_t n) {
-        size_t off = round_up((int)buf.size(), 256);
-        buf.resize(off + n);
-        std::memcpy(buf.data() + off, d, n);
-        return off;
-    }
-    size_t push_w(const std::vector<double> &w, int sw = 0) {
-        if (prec == PREC_F16) {
-            std::vector<uint16_t> h(w.size());
-            for (size_t i = 0; i < w.size(); ++i) h[i] = f32_to_f16((float)w[i]);
-            return push(h.data(), h.size() * 2);
-        }
-        if (prec == PREC_BF16) {
-            std::vector<uint16_t> h(w.size());
-            for (size_t i = 0; i < w.size(); ++i) {
-                float f = (float)w[i];
-                uint32_t u;
-                std::memcpy(&u, &f, 4);
-                u = u + 0x7fffu + ((u >> 16) & 1u);     // round to nearest even (weights are finite)
-                h[i] = (uint16_t)(u >> 16);
-            }
-            return push(h.data(), h.size() * 2);
-        }
-        // fp32 parity mode: the split-f16 operand of mfma_common.h (RawS): per 8 consecutive k of a
-        // row (rows are whole 32-k steps), the 8 hi parts f16(w) then the 8 lo parts f16(w - hi),
-        // w * 2^sw rounded to f32 first (the f32 weight the exact-product path used, times the power of
-        // two that brings the matrix into the split's window: range_weight_exp)
-        // (rows are whole 32-k steps, so w.size() is a multiple of 8; a partial last group would be
-        // zero-padded to 8, never written past the buffer)
-        const double scale = std::ldexp(1.0, sw);
-        std::vector<uint16_t> h((w.size() + 7) / 8 * 16, 0);
-        for (size_t g = 0; g < w.size(); g += 8)
-            for (size_t i = 0; i < 8 && g + i < w.size(); ++i) {
-                const float f = (float)(w[g + i] * scale);
-                const uint16_t hi = f32_to_f16(f);
-                h[2 * g + i] = hi;
-                h[2 * g + 8 + i] = f32_to_f16(f - f16_to_f32(hi));   // exact difference in f32
-            }
-        return push(h.data(), h.size() * 2);
-    }
-    size_t push_f(const std::vector<float> &v) { return push(v.data(), v.size() * 4); }
-};
-
-void bn_fold(const UnitDesc &u, std::vector<double> &scale, std::vector<double> &shift) {
-    scale.resize(u.cout);
-    shift.resize(u.cout);
-    for (int c = 0; c < u.cout; ++c) {
-        const double s = (double)u.gamma[c] / std::sqrt((double)u.var[c] + (double)u.eps);
-        scale[c] = s;
-        shift[c] = ((double)u.b[c] - (double)u.mean[c]) * s + (double)u.beta[c];
-    }
-}
-
-int gentry(int dy, int dx, int coff) { return (dy & 0xff) | ((dx & 0xff) << 8) | (coff << 16); }
-
-// fp32 mode range scaling: the weight exponent of the packed matrix and its rows' bound terms
-// (bugseg_internal.h RangeArgs). w: the folded [Npad][Kpad] matrix; bias / slope per row.
-void range_stats(Packed &p, bool scaled, const std::vector<double> &w, const std::vector<float> &bias,
-                 const std::vector<float> &slope) {
-    p.sw = 0;
-    p.rabs.assign(p.Npad, 0.f);
-    p.rbias.assign(p.Npad, 0.f);
-    p.rslope.assign(p.Npad, 1.f);
-    double mx = 0;
-    for (int r = 0; r < p.Npad; ++r) {
-        double sa = 0;
-        for (int k = 0; k < p.Kpad; ++k) {
-            const double v = std::fabs(w[(size_t)r * p.Kpad + k]);
-            sa += v;
-            mx = std::max(mx, v);
-        }
-        p.rabs[r] = (float)sa;
-        p.rbias[r] = std::fabs(bias[r]);
-        p.rslope[r] = std::max(1.f, std::fabs(slope[r]));
-    }
-    if (scaled) p.sw = range_weight_exp(mx);
-}
-// |act(W x + b)| <= n |x| + c over the rows [r0, r1) of a packed matrix (a 1e-4 margin for the f32
-// arithmetic the kernels evaluate the bound in)
-void row_bound(const Packed &p, int r0, int r1, float &n, float &c) {
-    n = c = 0.f;
-    for (int r = r0; r < r1 && r < (int)p.rabs.size(); ++r) {
-        n = std::max(n, p.rabs[r] * p.rslope[r]);
-        c = std::max(c, p.rbias[r] * p.rslope[r]);
-    }
-    n *= 1.0001f;
-    c *= 1.0001f;
-}
-
-// Ordinary convolution (OIHW weights) on an NHWC input with CinS storage channels.
-Packed pack_conv(Packer &pk, const UnitDesc &u, int CinS, const std::vector<float> *slope2) {
-    Packed p;
-    const int taps = u.kh * u.kw, CG = CinS / 8;
-    const int Kgroups = taps * CG;
-    p.Ksteps = (Kgroups + 3) / 4;
-    p.Kpad = p.Ksteps * 32;
-    p.cout = u.cout;
-    p.coutP = round_up(u.cout, 16);
-    p.nr = pow2_nr(p.coutP);
-    p.Npad = p.nr * 16;
-    p.CinS = CinS;
-    p.stride = u.stride;
-    p.macs_per_px = (double)u.cout * u.cin * taps;
-    std::vector<double> scale, shift;
-    bn_fold(u, scale, shift);
-    std::vector<double> w((size_t)p.Npad * p.Kpad, 0.0);
-    for (int co = 0; co < u.cout; ++co)
-        for (int ci = 0; ci < u.cin; ++ci)
-            for (int ky = 0; ky < u.kh; ++ky)
-                for (int kx = 0; kx < u.kw; ++kx) {
-                    const int tap = ky * u.kw + kx;
-                    w[(size_t)co * p.Kpad + tap * CinS + ci] =
-                        (double)u.w[(((size_t)co * u.cin + ci) * u.kh + ky) * u.kw + kx] * scale[co];
-                }
-    std::vector<int> gt(p.Ksteps * 4, gentry(0, 0, 0xffff));
-    for (int g = 0; g < Kgroups; ++g) {
-        const int tap = g / CG, ky = tap / u.kw, kx = tap % u.kw;
-        gt[g] = gentry(ky * u.dil_h - u.pad_h, kx * u.dil_w - u.pad_w, (g % CG) * 8);
-    }
-    std::vector<float> bias(p.Npad, 0.f), s1(p.Npad, 0.f), s2(p.Npad, 0.f), ps(p.Npad, 0.f);
-    for (int c = 0; c < u.cout; ++c) {
-        bias[c] = (float)shift[c];
-        s1[c] = u.slope[c];
-        if (slope2) s2[c] = (*slope2)[c];
-    }
-    range_stats(p, pk.range, w, bias, s1);
-    p.o_w = pk.push_w(w, p.sw);
-    p.o_gtab = pk.push(gt.data(), gt.size() * 4);
-    p.o_bias = pk.push_f(bias);
-    p.o_s1 = pk.push_f(s1);
-    p.o_s2 = pk.push_f(s2);
-    p.o_ps = pk.push_f(ps);
-    return p;
-}
-
-// Two 1x1 convolutions over the same input as ONE launch (the upsampling block's main 1x1 and its
-// extension branch's first 1x1, which both read the block input): rows [0, m.cout) are m's,
-// rows [m.cout, m.cout + e.cout) e's, each with its own folded BN and slope. Bit-identical per output
-// channel to the two separate launches when both pack to the same bias placement.
-Packed pack_conv_pair(Packer &pk, const UnitDesc &m, const UnitDesc &e, int CinS) {
-    UnitDesc u = m;
-    u.cout = m.cout + e.cout;
-    u.w.insert(u.w.end(), e.w.begin(), e.w.end());
-    u.b.insert(u.b.end(), e.b.begin(), e.b.end());
-    auto cat = [](std::vector<float> a, const std::vector<float> &b) { a.insert(a.end(), b.begin(), b.end()); return a; };
-    // BN folds per channel (the caller requires m.eps == e.eps)
-    u.gamma = cat(m.gamma, e.gamma);
-    u.beta = cat(m.beta, e.beta);
-    u.mean = cat(m.mean, e.mean);
-    u.var = cat(m.var, e.var);
-    u.slope = cat(m.slope, e.slope);
-    return pack_conv(pk, u, CinS, nullptr);
-}
-
-// Stride-2 transposed convolution (IOHW weights) as a 4-phase convolution over the INPUT grid:
-// output pixel (2i+a, 2j+b) = sum over taps (dy,dx) of in[i+dy][j+dx] . W[ky = a+pad-2dy][kx = b+pad-2dx]
-// (PyTorch/ONNX semantics y = 2i - pad + ky). GEMM row n = phase * coutP + co.
-Packed pack_tconv(Packer &pk, const UnitDesc &u, int CinS, std::string &why, int choff = 0) {
-    Packed p;
-    if (u.stride != 2 || u.kh != u.kw || u.pad_h != u.pad_w) { why = "tconv: only square stride-2 kernels"; return p; }
-    const int k = u.kh, pad = u.pad_h;
-    if (-2 - 2 * pad + k + u.out_pad != 0) { why = "tconv: output must be exactly 2x the input"; return p; }
-    std::vector<int> D;
-    for (int d = -3; d <= 3; ++d) {
-        bool any = false;
-        for (int a = 0; a < 2; ++a) { const int kk = a + pad - 2 * d; any |= kk >= 0 && kk < k; }
-        if (any) D.push_back(d);
-    }
-    // input groups: cstore(u.cin) channels starting at channel `choff` of a CinS-channel tensor
-    const int nd = (int)D.size(), taps = nd * nd, CG = round_up(u.cin, 8) / 8;
-    const int Kgroups = taps * CG;
-    p.Ksteps = (Kgroups + 3) / 4;
-    p.Kpad = p.Ksteps * 32;
-    p.cout = u.cout;
-    p.coutP = round_up(u.cout, 16);
-    p.phases = 4;
-    p.nr = pow2_nr(4 * p.coutP);
-    p.Npad = p.nr * 16;
-    if (p.Npad != 4 * p.coutP || p.nr > 8) { why = "tconv: unsupported channel count"; return p; }
-    p.CinS = CinS;
-    p.stride = 1;
-    p.macs_per_px = (double)u.cout * u.cin * k * k;       // per INPUT pixel
-    std::vector<double> scale, shift;
-    bn_fold(u, scale, shift);
-    std::vector<double> w((size_t)p.Npad * p.Kpad, 0.0);
-    for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b)
-            for (int ty = 0; ty < nd; ++ty)
-                for (int tx = 0; tx < nd; ++tx) {
-                    const int ky = a + pad - 2 * D[ty], kx = b + pad - 2 * D[tx];
-                    if (ky < 0 || ky >= k || kx < 0 || kx >= k) continue;
-                    const int tap = ty * nd + tx;
-                    for (int co = 0; co < u.cout; ++co)
-                        for (int ci = 0; ci < u.cin; ++ci)
-                            w[(size_t)((a * 2 + b) * p.coutP + co) * p.Kpad + tap * CG * 8 + ci] =
-                                (double)u.w[(((size_t)ci * u.cout + co) * k + ky) * k + kx] * scale[co];
-                }
-    std::vector<int> gt(p.Ksteps * 4, gentry(0, 0, 0xffff));
-    for (int g = 0; g < Kgroups; ++g) {
-        const int tap = g / CG;
-        gt[g] = gentry(D[tap / nd], D[tap % nd], choff + (g % CG) * 8);
-    }
-    std::vector<float> bias(p.Npad, 0.f), s1(p.Npad, 0.f), s2(p.Npad, 0.f), ps(p.Npad, 0.f);
-    for (int ph = 0; ph < 4; ++ph)
-        for (int c = 0; c < u.cout; ++c) {
-            bias[ph * p.coutP + c] = (float)shift[c];
-            s1[ph * p.coutP + c] = u.slope[c];
-        }
-    range_stats(p, pk.range, w, bias, s1);
-    p.o_w = pk.push_w(w, p.sw);
-    p.o_gtab = pk.push(gt.data(), gt.size() * 4);
-    p.o_bias = pk.push_f(bias);
-    p.o_s1 = pk.push_f(s1);
-    p.o_s2 = pk.push_f(s2);
-    p.o_ps = pk.push_f(ps);
-    return p;
-}
-
-int cstore(int c) { return round_up(c, 8); }
-
-bool pack_all(bugseg_ctx *ctx, std::string &why) {
-    ctx->packed.clear();
-    ctx->block_convs.clear();
-    ctx->host_w.clear();
-    Packer pk{ctx->prec, ctx->prec == PREC_F32 && ctx->knobs.f32_range, ctx->host_w};
-    int cur_c = 3;
-    std::vector<int> down_cin(ctx->blocks.size(), -1);
-    for (size_t bi = 0; bi < ctx->blocks.size(); ++bi) {
-        const BlockDesc &b = ctx->blocks[bi];
-        std::vector<int> ids;
-        auto add = [&](const Packed &p) { ctx->packed.push_back(p); ids.push_back((int)ctx->packed.size() - 1); };
-        auto expect_units = [&](size_t n) { return b.units.size() == n; };
-        switch (b.type) {
-        case BT_INITIAL: {
-            const int cin = b.attrs[0], cconv = b.attrs[1], pk_k = b.attrs[2];
-            if (bi != 0 || !expect_units(1) || cin != 3 || cconv + cin > 16 || (pk_k != 2 && pk_k != 3) ||
-                b.extra.size() != 6) { why = "initial block malformed"; return false; }
-            const UnitDesc &u = b.units[0];
-            if (u.cout != cconv || u.cin != cin || u.kh != 3 || u.kw != 3 || u.stride != 2 || u.pad_h != 1 || u.pad_w != 1) {
-                why = "initial conv must be 3x3 s2 p1"; return false;
-            }
-            Packed p = pack_conv(pk, u, 8, nullptr);
-            // pool channels [cconv, cconv+cin): BN of the concat as scale + shift, their own slope
-            std::vector<float> bias(p.Npad), s1(p.Npad), ps(p.Npad, 0.f);
-            std::memcpy(bias.data(), ctx->host_w.data() + p.o_bias, p.Npad * 4);
-            std::memcpy(s1.data(), ctx->host_w.data() + p.o_s1, p.Npad * 4);
-            const std::vector<float> &g = b.extra[0], &be = b.extra[1], &mu = b.extra[2], &va = b.extra[3],
-                                     &ep = b.extra[4], &sl = b.extra[5];
-            if ((int)g.size() != cin || ep.size() != 1 || (int)sl.size() != cin) { why = "initial extras malformed"; return false; }
-            for (int c = 0; c < cin; ++c) {
-                const double s = (double)g[c] / std::sqrt((double)va[c] + (double)ep[0]);
-                ps[cconv + c] = (float)s;
-                bias[cconv + c] = (float)((double)be[c] - (double)mu[c] * s);
-                s1[cconv + c] = sl[c];
-            }
-            std::memcpy(ctx->host_w.data() + p.o_bias, bias.data(), p.Npad * 4);
-            std::memcpy(ctx->host_w.data() + p.o_s1, s1.data(), p.Npad * 4);
-            std::memcpy(ctx->host_w.data() + p.o_ps, ps.data(), p.Npad * 4);
-            p.cout = cconv + cin;
-            add(p);
-            cur_c = cconv + cin;
-            break;
-        }
-        case BT_DOWN: {
-            const int cin = b.attrs[0], cout = b.attrs[1];
-            if (!expect_units(3) || b.extra.size() != 1 || cin != cur_c || cout < cin) { why = "down block malformed"; return false; }
-            const UnitDesc &u1 = b.units[0], &u2 = b.units[1], &u3 = b.units[2];
-            if (u1.kh != 2 || u1.kw != 2 || u1.stride != 2 || u1.cin != cin || u2.stride != 1 || u3.kh != 1 ||
-                u3.kw != 1 || u3.cout != cout || (int)b.extra[0].size() != cout) { why = "down block units malformed"; return false; }
-            add(pack_conv(pk, u1, cstore(cin), nullptr));
-            add(pack_conv(pk, u2, cstore(u1.cout), nullptr));
-            add(pack_conv(pk, u3, cstore(u2.cout), &b.extra[0]));
-            down_cin[bi] = cin;
-            cur_c = cout;
-            break;
-        }
-        case BT_REGULAR: {
-            const int ch = b.attrs[0];
-            if ((b.units.size() != 3 && b.units.size() != 4) || b.extra.size() != 1 || ch != cur_c) {
-                why = "regular block malformed"; return false;
-            }
-            int c = ch;
-            for (size_t i = 0; i < b.units.size(); ++i) {
-                const UnitDesc &u = b.units[i];
-                if (u.kind != 0 || u.cin != c || u.stride != 1) { why = "regular block unit chain malformed"; return false; }
-                const bool last = i + 1 == b.units.size();
-                add(pack_conv(pk, u, cstore(c), last ? &b.extra[0] : nullptr));
-                c = u.cout;
-            }
-            if (c != ch || (int)b.extra[0].size() != ch) { why = "regular block must preserve channels"; return false; }
-            break;
-        }
-        case BT_UP: {
-            const int cin = b.attrs[0], cout = b.attrs[1], ref = b.attrs[2];
-            if (!expect_units(4) || b.extra.size() != 1 || cin != cur_c || ref < 0 || ref >= (int)bi ||
-                ctx->blocks[ref].type != BT_DOWN || down_cin[ref] != cout) { why = "up block malformed"; return false; }
-            const UnitDesc &um = b.units[0], &u1 = b.units[1], &ut = b.units[2], &u2 = b.units[3];
-            if (um.kh != 1 || um.cout != cout || u1.kh != 1 || ut.kind != 1 || ut.kh != 2 || u2.kh != 1 || u2.cout != cout) {
-                why = "up block units malformed"; return false;
-            }
-            add(pack_conv(pk, um, cstore(cin), nullptr));
-            add(pack_conv(pk, u1, cstore(cin), nullptr));
-            Packed t = pack_tconv(pk, ut, cstore(u1.cout), why);
-            if (!why.empty()) return false;
-            add(t);
-            add(pack_conv(pk, u2, cstore(ut.cout), &b.extra[0]));
-            // ids 4 (and 5): the main 1x1 and the extension 1x1 packed as ONE matrix over the block
-            // input (rows: main then extension, each with its own folded BN and slope). Used by the
-            // fused upsampling kernel (up_kernels.hip), or, where that kernel is not built for the
-            // shape, as one conv launch whose output the tconv reads from channel cout on (id 5) —
-            // that needs a power-of-two count of 16-B chunks per pixel (the conv epilogue's staged
-            // stores). Both require the two halves to fold their bias the same way (bias_in_acc).
-            const int es = prec_es(ctx->prec), mc = cstore(um.cout) + cstore(u1.cout);
-            const int chunks = mc * es / 16;
-            const int nr_pair = pow2_nr(round_up(um.cout, 16) + round_up(u1.cout, 16));
-            auto bias_acc = [](int nr) { return nr < 8; };     // mfma_common.h bias_in_acc
-            const bool same_bias = bias_acc(pow2_nr(round_up(um.cout, 16))) && bias_acc(pow2_nr(round_up(u1.cout, 16)));
-            if (um.cout % 16 == 0 && u1.cout % 16 == 0 && um.eps == u1.eps && same_bias) {
-                add(pack_conv_pair(pk, um, u1, cstore(cin)));
-                if ((chunks & (chunks - 1)) == 0 && nr_pair <= 8 && bias_acc(nr_pair) && !ctx->knobs.no_pair) {
-                    Packed t2 = pack_tconv(pk, ut, mc, why, cstore(um.cout));
-                    if (!why.empty()) return false;
-                    add(t2);
-                }
-            }
-            cur_c = cout;
-            break;
-        }
-        case BT_FULLCONV: {
-            if (!expect_units(1) || bi + 1 != ctx->blocks.size()) { why = "fullconv must be the last block"; return false; }
-            const UnitDesc &u = b.units[0];
-            if (u.kind != 1 || u.cin != cur_c || u.cout != ctx->ncls || u.cout > 16) { why = "fullconv malformed"; return false; }
-            Packed t = pack_tconv(pk, u, cstore(cur_c), why);
-            if (!why.empty()) return false;
-            if (t.coutP != 16) { why = "fullconv: classes must fit 16"; return false; }
-            add(t);
-            cur_c = u.cout;
-            break;
-        }
-        default:
-            why = "unknown block type";
-            return false;
-        }
-        ctx->block_convs.push_back(ids);
-    }
-    if (ctx->blocks.empty() || ctx->blocks.back().type != BT_FULLCONV) { why = "model must end in fullconv"; return false; }
-    return true;
 }
 
 // ---------------------------------------------------------------- plan
@@ -821,7 +315,7 @@ ConvArgs base_args(const bugseg_ctx *ctx, const Packed &p) {
 // Every PReLU slope (both slope vectors) of the packed units is <= 1: max(v, s*v) is then exact
 bool slopes_le1(const bugseg_ctx *ctx, std::initializer_list<const Packed *> units) {
     for (const Packed *p : units) {
-        const float *s1 = (const float *)(ctx->host_w.data() + p->o_s1), *s2 = (const float *)(ctx->host_w.data() + p->o_s2);
+        const float *s1 = (const float *)(ctx->w.host_w.data() + p->o_s1), *s2 = (const float *)(ctx->w.host_w.data() + p->o_s2);
         for (int c = 0; c < p->Npad; ++c)
             if (!(s1[c] <= 1.f) || !(s2[c] <= 1.f)) return false;
     }
@@ -836,7 +330,7 @@ bool fusable_regular(const bugseg_ctx *ctx, const BlockDesc &b, const std::vecto
     if (ctx->knobs.no_fuse) return false;
     // the fused kernel computes PReLU as max(v, s*v), exact only for slopes <= 1
     for (const int id : ids)
-        if (!slopes_le1(ctx, {&ctx->packed[id]})) return false;
+        if (!slopes_le1(ctx, {&ctx->w.packed[id]})) return false;
     const int C = b.attrs[0];
     if (C != 128 && C != 64 && C != 16) return false;
     const int nu = (int)b.units.size();
@@ -867,7 +361,7 @@ int fusable_down(const bugseg_ctx *ctx, const BlockDesc &b, const std::vector<in
     const int v = C == 64 && cin == 16 ? 0 : C == 128 && cin == 64 ? 1 : -1;
     if (v < 0 || b.units.size() != 3) return -1;
     for (const int id : ids)
-        if (!slopes_le1(ctx, {&ctx->packed[id]})) return -1;
+        if (!slopes_le1(ctx, {&ctx->w.packed[id]})) return -1;
     const UnitDesc &u1 = b.units[0], &u2 = b.units[1], &u3 = b.units[2];
     const int I = cin / 4;                              // ENet: internal = input channels / 4
     if (u1.kh != 2 || u1.kw != 2 || u1.stride != 2 || u1.pad_h != 0 || u1.pad_w != 0 || u1.cin != cin || u1.cout != I)
@@ -933,24 +427,23 @@ int pick_bneck_variant(const bugseg_ctx *ctx, int C, bool asym, int d, int B, in
 
 // Walk the network for (B, H, W), twice: run(false) computes only the buffer sizes, run(true), with the arena
 // carved, the ops. run dispatches to one method per block type; wire / slopes_le1 / sums are what those share.
+// Of the plan under construction (build_plan's local) the size pass fills idx_bytes and the second pass ops, from
+// the idx and words build_plan carved in between.
 struct Walker {
-    bugseg_ctx *ctx;
+    const bugseg_ctx *ctx;
+    Plan &pl;
     int B, H, W;
     size_t es;
     // buffer sizes (bytes) and pointers
     size_t szX = 0, szT = 0, szM = 0;
-    std::vector<size_t> szIdx;
     unsigned char *X[2] = {nullptr, nullptr}, *T[3] = {nullptr, nullptr, nullptr}, *Mb = nullptr;
-    std::vector<unsigned char *> idx;
-    std::vector<Op> ops;
-    // fp32 mode range scaling (bugseg_internal.h RangeArgs): RNG_SLOTS words per measured tensor, block 0
-    // for the engine input; which block holds the range of each buffer's current contents
-    float *words = nullptr;
+    // fp32 mode range scaling (bugseg_internal.h RangeArgs): RNG_SLOTS words per measured tensor (Plan::words), block
+    // 0 for the engine input; which block holds the range of each buffer's current contents
     int nwords = 1;
     std::vector<std::pair<const void *, float *>> wmap;
     static int max_words(size_t nblocks) { return (int)(4 * nblocks + 4); }
     float *take_words() {
-        float *w = words && es == 4 ? words + (size_t)nwords * RNG_SLOTS : nullptr;
+        float *w = pl.words && es == 4 ? pl.words + (size_t)nwords * RNG_SLOTS : nullptr;
         ++nwords;
         return w;
     }
@@ -961,7 +454,7 @@ struct Walker {
     }
     float *words_of(const void *buf) const {
         if (es != 4) return nullptr;
-        if (!buf) return words;                          // the engine input
+        if (!buf) return pl.words;                          // the engine input
         for (const auto &e : wmap)
             if (e.first == buf) return e.second;
         return nullptr;
@@ -977,7 +470,7 @@ struct Walker {
     size_t bi = 0;
     const std::vector<int> *ids = nullptr;
     unsigned char *dst = nullptr;
-    const Packed &P(int i) const { return ctx->packed[(size_t)(*ids)[(size_t)i]]; }
+    const Packed &P(int i) const { return ctx->w.packed[(size_t)(*ids)[(size_t)i]]; }
     static ConvArgs &args(Op &op) { return std::get<ConvLaunch>(op.l).a; }
     static uint32_t clamp31(size_t v) { return (uint32_t)std::min<size_t>(v, 0x7fffffff); }
 
@@ -1034,8 +527,8 @@ struct Walker {
         op.flops = 2.0 * p.macs_per_px * a.M;
         op.bytes = (double)B * si.H * si.W * si.C * es + (double)p.Npad * p.Kpad * es +
                    (epi == EPI_CLASSES ? 0.0 : (double)B * so.H * so.W * so.C * es);
-        ops.push_back(op);
-        return ops.back();
+        pl.ops.push_back(op);
+        return pl.ops.back();
     }
 
     void initial(const BlockDesc &b) {
@@ -1056,7 +549,7 @@ struct Walker {
         const int idxCS = cstore(b.attrs[0]);
         szT = std::max({szT, tbytes(s1), tbytes(s2)});
         szX = std::max(szX, tbytes(so));
-        if (!fill) szIdx[bi] = (size_t)B * so.H * so.W * idxCS;
+        if (!fill) pl.idx_bytes[bi] = (size_t)B * so.H * so.W * idxCS;
         const int dv = cur.C == b.attrs[0] ? fusable_down(ctx, b, *ids) : -1;
         const Shape sp{so.H, so.W, idxCS};
         // (sizes T for the pooled-values scratch the fused form had; kept so that the arena's size does not move)
@@ -1077,7 +570,7 @@ struct Walker {
             wire_bneck(q, P(0), P(1), P(1), P(2));
             q.xin = curp;                             // (x_bytes: build_plan, as for every fused bottleneck)
             q.xin_bytes = clamp31(tbytes(cur));
-            q.idx_out = idx[bi]; q.idxCS = idxCS;
+            q.idx_out = pl.idx[bi]; q.idxCS = idxCS;
             q.idx_bytes = clamp31((size_t)B * so.H * so.W * idxCS);
             range_io(q.rg, curp, dst);
             const double px = (double)B * so.H * so.W;
@@ -1088,13 +581,13 @@ struct Walker {
             op.bytes = (double)tbytes(cur) + (double)tbytes(so) + px * idxCS + wb;
             op.layer_bytes = (double)tbytes(cur) * 2 + 2.0 * (tbytes(s1) + tbytes(s2)) + (double)tbytes(so) +
                              px * idxCS + wb;
-            ops.push_back(op);
+            pl.ops.push_back(op);
         } else if (fill) {
             conv(P(0), EPI_PLAIN, curp, cur, s1, T[0], s1);
             conv(P(1), EPI_PLAIN, T[0], s1, s2, T[1], s2);
             Op &o3 = conv(P(2), EPI_RESPOOL, T[1], s2, so, dst, so);
             residual(args(o3), curp, cur, b.attrs[0]);
-            args(o3).idx_out = idx[bi]; args(o3).idxCS = idxCS;
+            args(o3).idx_out = pl.idx[bi]; args(o3).idxCS = idxCS;
             o3.bytes += (double)B * cur.H * cur.W * cur.C * es + (double)B * so.H * so.W * idxCS;
         }
         cur = so;
@@ -1128,7 +621,7 @@ struct Walker {
             op.flops = fl;
             op.bytes = 2.0 * px * cur.C * es + wb;             // what this launch must move
             op.layer_bytes = lb + px * cur.C * es + wb;        // + the residual re-read
-            ops.push_back(op);
+            pl.ops.push_back(op);
             return;
         }
         Shape s = cur;
@@ -1160,7 +653,7 @@ struct Walker {
         szT = std::max({szT, tbytes(s1), tbytes(st)});
         szX = std::max(szX, tbytes(so));
         const int cin_b = b.attrs[0], cout_b = b.attrs[1], it_b = P(1).cout;
-        const int idxCS = cstore(ctx->blocks[(size_t)ref].attrs[0]);
+        const int idxCS = cstore(ctx->w.blocks[(size_t)ref].attrs[0]);
         const bool fuse_up = ids->size() >= 5 && up_supported(cin_b, it_b, cout_b) && cur.C == cin_b && so.C == cout_b && !ctx->knobs.no_fuse;
         const bool pair = ids->size() == 6;
         // unfused, paired: the main and extension 1x1 outputs share one tensor (main channels first)
@@ -1173,7 +666,7 @@ struct Walker {
             l.cin = cin_b; l.it = it_b; l.cout = cout_b;
             UpArgs &q = l.a;
             const Packed &p1 = P(4), &p2 = P(2), &p3 = P(3);
-            q.x = curp; q.idx = idx[(size_t)ref]; q.out = dst;
+            q.x = curp; q.idx = pl.idx[(size_t)ref]; q.out = dst;
             q.M = B * cur.H * cur.W; q.h = cur.H; q.w = cur.W;
             q.y0 = 0; q.hwin = cur.H;                 // the full frame (narrow: a window)
             q.idxCS = idxCS;
@@ -1198,7 +691,7 @@ struct Walker {
             op.bytes = px * cur.C * es + px * idxCS + 4.0 * px * so.C * es + wb;   // x + idx in, out
             op.layer_bytes = px * cur.C * es * 2 + px * (sm.C + s1.C) * es + px * s1.C * es + 4.0 * px * st.C * es * 2 +
                              px * sm.C * es + px * idxCS + 4.0 * px * so.C * es + wb;
-            ops.push_back(op);
+            pl.ops.push_back(op);
         } else if (fill) {
             if (pair) {
                 conv(P(4), EPI_PLAIN, curp, cur, sp, Mb, sp);
@@ -1210,7 +703,7 @@ struct Walker {
             }
             Op &o2 = conv(P(3), EPI_RESUNPOOL, T[1], st, so, dst, so);
             residual(args(o2), Mb, sp, b.attrs[1]);
-            args(o2).idx_in = idx[(size_t)ref]; args(o2).idxCS = idxCS;
+            args(o2).idx_in = pl.idx[(size_t)ref]; args(o2).idxCS = idxCS;
             o2.bytes += (double)B * sm.H * sm.W * sm.C * es + (double)B * sm.H * sm.W * idxCS;
         }
         cur = so;
@@ -1221,7 +714,7 @@ struct Walker {
         if (so.H != H || so.W != W) { why = "network does not return to the input resolution"; return false; }
         if (fill) {
             ConvLaunch &l = std::get<ConvLaunch>(conv(P(0), EPI_CLASSES, curp, cur, cur, nullptr, so).l);
-            l.a.ncls = ctx->ncls;
+            l.a.ncls = ctx->w.ncls;
             l.cls = cls_supported(l.a) && !ctx->knobs.cls_conv;   // the route, decided here once
         }
         cur = so;
@@ -1233,17 +726,17 @@ struct Walker {
         fill = fill_;
         es = prec_es(ctx->prec);
         if (H % 8 || W % 8 || H <= 0 || W <= 0 || B <= 0) { why = "H and W must be positive multiples of 8"; return false; }
-        const size_t nb = ctx->blocks.size();
-        if (!fill) szIdx.assign(nb, 0);
+        const size_t nb = ctx->w.blocks.size();
+        if (!fill) pl.idx_bytes.assign(nb, 0);
         cur = Shape{H, W, 8};
         curp = nullptr;
         int xi = 0;
-        ops.clear();
+        pl.ops.clear();
         nwords = 1;
         wmap.clear();
         for (bi = 0; bi < nb; ++bi) {
-            const BlockDesc &b = ctx->blocks[bi];
-            ids = &ctx->block_convs[bi];
+            const BlockDesc &b = ctx->w.blocks[bi];
+            ids = &ctx->w.block_convs[bi];
             dst = X[xi];
             switch (b.type) {
             case BT_INITIAL: initial(b); break;
@@ -1317,15 +810,12 @@ Launch flipped(const Launch &l, unsigned char *const X[2]) {
     return f;
 }
 
-// The pair overlay of the plan just built: the pairs (Plan::firsts, Plan::pairs) and every op's forward
-// launch and walk parity (Op::fwd, Op::fwd_odd), final from here on. Pairs exist in fp32, in the fused plan, with no
-// C = 64 tile variant forced, where the spare buffer holds a C = 64 tensor; the decoder's last WIN_OPS ops keep their
+// The pair overlay of the plan pl under construction: the pairs (Plan::firsts, Plan::pairs) and every op's
+// forward launch and walk parity (Op::fwd, Op::fwd_odd), final from here on. Pairs exist in fp32, in the fused plan, with
+// no C = 64 tile variant forced, where the spare buffer holds a C = 64 tensor; the decoder's last WIN_OPS ops keep their
 // own (row-windowed) launches. X: the arena's two activation buffers.
-void build_pairs(bugseg_ctx *ctx, unsigned char *const X[2], unsigned char *spare, size_t spare_bytes) {
-    Plan &pl = ctx->plan;
+void build_pairs(const bugseg_ctx *ctx, Plan &pl, unsigned char *const X[2], unsigned char *spare, size_t spare_bytes) {
     const int n = (int)pl.ops.size();
-    pl.pairs.clear();
-    pl.firsts.clear();
     const Knobs &k = ctx->knobs;
     if (ctx->prec == PREC_F32 && !k.no_fuse && k.bneck_variant < 0 && k.bneck_variant_c64 < 0) {
         auto buf = [&](const void *p) { return p == X[0] ? 0 : p == X[1] ? 1 : -1; };
@@ -1368,37 +858,44 @@ void build_pairs(bugseg_ctx *ctx, unsigned char *const X[2], unsigned char *spar
     }
 }
 
+// The context's plan for (B, H, W): kept when it is that already, else built in a local and moved in complete
+// (DESIGN 6.28). A failure before the old arena is retired (the size pass) leaves the installed plan in force; a
+// failure after it (the allocation, the fill pass, the range-word count, the 31-bit sizes) leaves Plan(), with the
+// new arena freed: nothing was ever enqueued on it. Retire, then allocate: a re-plan's peak memory is one arena.
 bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *stream = nullptr) {
-    Plan &pl = ctx->plan;
-    if (pl.arena && pl.B == B && pl.H == H && pl.W == W) return true;
-    Walker w{ctx, B, H, W};
+    if (ctx->plan.at(B, H, W)) return true;
+    Plan pl;
+    Walker w{ctx, pl, B, H, W};
     if (!w.run(false, why)) return false;
     auto al = [](size_t v) { return (v + 4095) / 4096 * 4096; };
     size_t total = 2 * al(w.szX) + 3 * al(w.szT) + al(w.szM);
-    for (size_t s : w.szIdx) total += al(s);
-    const size_t words_bytes = ctx->prec == PREC_F32 ? (size_t)Walker::max_words(ctx->blocks.size()) * RNG_SLOTS * 4 : 0;
-    total += al(words_bytes);
+    for (size_t s : pl.idx_bytes) total += al(s);
+    pl.words_bytes = ctx->prec == PREC_F32 ? (size_t)Walker::max_words(ctx->w.blocks.size()) * RNG_SLOTS * 4 : 0;
+    total += al(pl.words_bytes);
     const bool cap = stream_capturing(stream);
     RelaxCapture relax;                 // the first forward at a shape may itself be captured
-    if (pl.arena) {
+    if (!ctx->plan.empty()) {
         // a forward of the old shape may still be running (or be part of a captured graph)
-        ctx->mem.retire(pl.arena, cap || pl.pinned);
-        pl.arena = nullptr;
-        pl.pinned = false;
+        ctx->mem.retire(ctx->plan.arena, cap || ctx->plan.pinned);
+        ctx->plan = Plan();
     }
-    if (hipMalloc(&pl.arena, total) != hipSuccess) { why = "hipMalloc of the activation arena failed"; pl.arena = nullptr; return false; }
+    if (hipMalloc(&pl.arena, total) != hipSuccess) {
+        (void)hipGetLastError();            // (reported here: the next launch's check must not find it)
+        why = "hipMalloc of the activation arena failed";
+        return false;
+    }
+    auto drop = [&](const char *what) { if (what) why = what; (void)hipFree(pl.arena); return false; };
     unsigned char *p = (unsigned char *)pl.arena;
     w.X[0] = p; p += al(w.szX);
     w.X[1] = p; p += al(w.szX);
     for (int i = 0; i < 3; ++i) { w.T[i] = p; p += al(w.szT); }
     w.Mb = p; p += al(w.szM);
-    w.idx.assign(w.szIdx.size(), nullptr);
-    for (size_t i = 0; i < w.szIdx.size(); ++i) if (w.szIdx[i]) { w.idx[i] = p; p += al(w.szIdx[i]); }
-    w.words = words_bytes ? (float *)p : nullptr;
-    p += al(words_bytes);
-    if (!w.run(true, why)) return false;
-    if (words_bytes && w.nwords > Walker::max_words(ctx->blocks.size())) { why = "range words: plan too long"; return false; }
-    for (Op &op : w.ops) {
+    pl.idx.assign(pl.idx_bytes.size(), nullptr);
+    for (size_t i = 0; i < pl.idx_bytes.size(); ++i) if (pl.idx_bytes[i]) { pl.idx[i] = p; p += al(pl.idx_bytes[i]); }
+    pl.words = pl.words_bytes ? (float *)p : nullptr;
+    if (!w.run(true, why)) return drop(nullptr);
+    if (pl.words_bytes && w.nwords > Walker::max_words(ctx->w.blocks.size())) return drop("range words: plan too long");
+    for (Op &op : pl.ops) {
         bool fits = true;
         if (BneckLaunch *b = std::get_if<BneckLaunch>(&op.l)) {
             const double bytes = (double)b->a.B * b->a.H * b->a.W * b->C * w.es;
@@ -1408,16 +905,12 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
         } else if (ConvLaunch *c = std::get_if<ConvLaunch>(&op.l)) {
             fits = finish_conv_args(c->a, c->epi, w.es);
         }
-        if (!fits) { why = "batch too large for 32-bit tensor offsets"; return false; }
+        if (!fits) return drop("batch too large for 32-bit tensor offsets");
     }
-    pl.ops = std::move(w.ops);
     int issued = 0;
     for (Op &op : pl.ops) { op.pos = issued; issued += op.launches; }
     // the spare buffer: T[1] (the fused plan's launches use none of the T buffers)
-    build_pairs(ctx, w.X, w.T[1], al(w.szT));
-    pl.cls_ok = false;
-    pl.cls_on = false;
-    pl.bound = Binding();
+    build_pairs(ctx, pl, w.X, w.T[1], al(w.szT));
     if (ctx->knobs.cls_fuse && pl.ops.size() >= 2 && pl.ops.back().class_kernel()) {
         const ConvArgs &l = pl.ops.back().conv()->a;
         const Op &q = pl.ops[pl.ops.size() - 2];
@@ -1428,14 +921,10 @@ bool build_plan(bugseg_ctx *ctx, int B, int H, int W, std::string &why, void *st
             pl.cls_fused_fwd = cls_fused_launch(std::get<BneckLaunch>(q.fwd), std::get<ConvLaunch>(pl.ops.back().fwd).a);
         }
     }
-    pl.idx = w.idx;
-    pl.idx_bytes = w.szIdx;
-    pl.words = w.words;
-    pl.words_bytes = words_bytes;
     pl.B = B; pl.H = H; pl.W = W;
     pl.arena_bytes = total;
-    pl.act_bytes = total - al(words_bytes);
-    pl.wins.clear();
+    pl.act_bytes = total - al(pl.words_bytes);
+    ctx->plan = std::move(pl);
     return true;
 }
 
@@ -1762,29 +1251,32 @@ int bugseg_destroy(bugseg_ctx *ctx) {
 int bugseg_load_weights(bugseg_ctx *ctx, const void *blob, size_t bytes) {
     if (!ctx || !blob) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     DeviceGuard g(ctx->mem.device);
-    std::vector<BlockDesc> blocks;
-    int ncls = 0;
+    // a refused blob changes nothing: the old model stays loaded and its plan in force
+    EnetWeights w;
     std::string why;
-    if (!parse_blob(blob, bytes, blocks, ncls, why)) return fail(ctx, BUGSEG_EFORMAT, "weight blob: " + why);
-    ctx->blocks = std::move(blocks);
-    ctx->ncls = ncls;
-    ctx->loaded = false;
-    if (!pack_all(ctx, why)) return fail(ctx, BUGSEG_EFORMAT, "weight blob: " + why);
+    if (!build_weights(blob, bytes, ctx->prec, ctx->knobs, w, why)) return fail(ctx, BUGSEG_EFORMAT, "weight blob: " + why);
     // a captured graph's kernels hold pointers into the old weights and arena: then kept until destroy
     ctx->mem.retire(ctx->dev_w, ctx->plan.pinned);
+    if (!ctx->plan.empty()) ctx->mem.retire(ctx->plan.arena, ctx->plan.pinned);
     ctx->dev_w = nullptr;
-    if (ctx->plan.arena) {
-        ctx->mem.retire(ctx->plan.arena, ctx->plan.pinned);
-        ctx->plan = Plan();
-    }
-    if (hipMalloc(&ctx->dev_w, ctx->host_w.size()) != hipSuccess ||
-        hipMemcpy(ctx->dev_w, ctx->host_w.data(), ctx->host_w.size(), hipMemcpyHostToDevice) != hipSuccess)
+    ctx->plan = Plan();
+    ctx->w = EnetWeights();
+    ctx->loaded = false;
+    // the new model goes in whole, once it is on the device; a failure leaves no weights, no plan, nothing allocated
+    void *dev = nullptr;
+    if (hipMalloc(&dev, w.host_w.size()) != hipSuccess ||
+        hipMemcpy(dev, w.host_w.data(), w.host_w.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        if (dev) (void)hipFree(dev);
         return fail(ctx, BUGSEG_EHIP, "uploading weights failed");
+    }
+    ctx->dev_w = dev;
+    ctx->w = std::move(w);
     ctx->loaded = true;
     return BUGSEG_OK;
 }
 
-int bugseg_num_classes(const bugseg_ctx *ctx) { return ctx && ctx->loaded ? ctx->ncls : 0; }
+int bugseg_num_classes(const bugseg_ctx *ctx) { return ctx && ctx->loaded ? ctx->w.ncls : 0; }
 
 size_t bugseg_input_bytes(const bugseg_ctx *ctx, int B, int H, int W) {
     if (!ctx || B <= 0 || H <= 0 || W <= 0) return 0;
@@ -2007,12 +1499,11 @@ int bugseg_enet_forward_bgr_rows(bugseg_ctx *ctx, const uint8_t *bgr, int B, int
 // ---- test hooks (host only: no device, no HIP call) — tests/asan drives them under ASan + UBSan
 int bugseg_debug_parse_pack(const void *blob, size_t bytes, int precision, int *ncls) {
     if (!blob) return fail(nullptr, BUGSEG_EINVAL, "NULL blob");
-    bugseg_ctx c{Knobs(), 0};                       // host state only (default knobs); nothing to free on the device
-    c.prec = precision == BUGSEG_BF16 ? PREC_BF16 : precision == BUGSEG_F16 ? PREC_F16 : PREC_F32;
+    const int prec = precision == BUGSEG_BF16 ? PREC_BF16 : precision == BUGSEG_F16 ? PREC_F16 : PREC_F32;
+    EnetWeights w;                                  // (default knobs)
     std::string why;
-    if (!parse_blob(blob, bytes, c.blocks, c.ncls, why)) return fail(nullptr, BUGSEG_EFORMAT, "weight blob: " + why);
-    if (!pack_all(&c, why)) return fail(nullptr, BUGSEG_EFORMAT, "weight blob: " + why);
-    if (ncls) *ncls = c.ncls;
+    if (!build_weights(blob, bytes, prec, Knobs(), w, why)) return fail(nullptr, BUGSEG_EFORMAT, "weight blob: " + why);
+    if (ncls) *ncls = w.ncls;
     return BUGSEG_OK;
 }
 
@@ -2029,12 +1520,12 @@ int bugseg_debug_pool_indices(bugseg_ctx *ctx, int B, int H, int W, int block, v
     if (!ctx || !dst) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     if (!ctx->loaded) return fail(ctx, BUGSEG_ESTATE, "no weights loaded");
     Plan &pl = ctx->plan;
-    if (!pl.arena || pl.B != B || pl.H != H || pl.W != W) return fail(ctx, BUGSEG_ESTATE, "no forward has run at these dimensions");
+    if (!pl.at(B, H, W)) return fail(ctx, BUGSEG_ESTATE, "no forward has run at these dimensions");
     if (block < 0 || block >= (int)pl.idx.size() || !pl.idx[(size_t)block])
         return fail(ctx, BUGSEG_EINVAL, "block " + std::to_string(block) + " is not a downsampling block");
     if (bytes != pl.idx_bytes[(size_t)block])
         return fail(ctx, BUGSEG_EINVAL, "index tensor is " + std::to_string(pl.idx_bytes[(size_t)block]) + " bytes");
-    if (idx_cs) *idx_cs = cstore(ctx->blocks[(size_t)block].attrs[0]);
+    if (idx_cs) *idx_cs = cstore(ctx->w.blocks[(size_t)block].attrs[0]);
     DeviceGuard g(ctx->mem.device);
     hipError_t e = hipMemcpyAsync(dst, pl.idx[(size_t)block], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, BUGSEG_EHIP, std::string("pool indices copy: ") + hipGetErrorString(e));
@@ -2088,7 +1579,7 @@ int bugseg_debug_row_windows(int H, int W, int row0, int row1, int tile_rows_c64
 int bugseg_debug_poison_arena(bugseg_ctx *ctx, int byte, void *stream) {
     if (!ctx) return fail(ctx, BUGSEG_EINVAL, "NULL ctx");
     Plan &pl = ctx->plan;
-    if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
+    if (pl.empty()) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
     DeviceGuard g(ctx->mem.device);
     // activations and pooling indices; the range words after them are cleared by every forward
     hipError_t e = hipMemsetAsync(pl.arena, byte & 255, pl.act_bytes, (hipStream_t)stream);
@@ -2112,7 +1603,7 @@ int bugseg_debug_stage3_windows(int h, int y0, int y1, int n, const int32_t *blk
 
 int bugseg_debug_plan_windows(bugseg_ctx *ctx, int row0, int row1, int32_t *win) {
     if (!ctx || !win) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
-    if (!ctx->plan.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
+    if (ctx->plan.empty()) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
     DeviceGuard g(ctx->mem.device);
     const WinPlan *wp = window_plan(ctx, row0, row1);
     if (!wp) return 0;
@@ -2128,7 +1619,7 @@ int bugseg_debug_plan_windows(bugseg_ctx *ctx, int row0, int row1, int32_t *win)
 int bugseg_debug_read_block_output(bugseg_ctx *ctx, int op, void *dst_dev, size_t bytes, void *stream) {
     if (!ctx || !dst_dev) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     const Plan &pl = ctx->plan;
-    if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
+    if (pl.empty()) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
     // where a forward leaves it (Op::fwd): the other activation buffer after an odd number of pairs; a pair's first
     // block in the spare buffer (written only when the pair was cut), its second where the pair writes
     const BneckLaunch *b = op >= 0 && op < (int)pl.ops.size() ? std::get_if<BneckLaunch>(&pl.ops[(size_t)op].fwd) : nullptr;
@@ -2154,7 +1645,7 @@ int bugseg_debug_pair_walk(int n, const int32_t *cand, int first_op, int last_op
 int bugseg_debug_pair_plan(bugseg_ctx *ctx, int32_t *rows, int cap) {
     if (!ctx || cap < 0 || (cap && !rows)) return fail(ctx, BUGSEG_EINVAL, "NULL argument");
     const Plan &pl = ctx->plan;
-    if (!pl.arena) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
+    if (pl.empty()) return fail(ctx, BUGSEG_ESTATE, "no forward has run");
     int th, tw, threads;
     size_t lds;
     bneck_pair_shape(th, tw, threads, lds);
@@ -2171,7 +1662,7 @@ int bugseg_debug_ctx_info(const bugseg_ctx *ctx, int what, int arg) {
     switch (what) {
     case 0: return ctx->naff_on ? 1 : 0;
     case 1: return ctx->knobs.f32_range ? 0 : 1;
-    case 2: return arg >= 0 && arg < (int)ctx->packed.size() ? ctx->packed[(size_t)arg].sw : -1000;
+    case 2: return arg >= 0 && arg < (int)ctx->w.packed.size() ? ctx->w.packed[(size_t)arg].sw : -1000;
     default: return -1;
     }
 }
@@ -2196,7 +1687,7 @@ int bugseg_plan_info(bugseg_ctx *ctx, int B, int H, int W, int out_kind, int bgr
         fl += op.flops;
     }
     // final epilogue output
-    const double fin = out_kind == BUGSEG_OUT_LOGITS_F32 ? (double)B * H * W * ctx->ncls * 4 : (double)B * H * W;
+    const double fin = out_kind == BUGSEG_OUT_LOGITS_F32 ? (double)B * H * W * ctx->w.ncls * 4 : (double)B * H * W;
     // class fusion: the last bottleneck's output is neither written nor read back
     if (ctx->plan.cls_ok && out_kind != BUGSEG_OUT_LOGITS_F32) {
         pb -= 2.0 * std::get<BneckLaunch>(ctx->plan.cls_fused).a.x_bytes;
@@ -2215,7 +1706,7 @@ int bugseg_plan_op(bugseg_ctx *ctx, int B, int H, int W, int op, char *kernel, i
     if (!ctx) return fail(ctx, BUGSEG_EINVAL, "NULL ctx");
     if (!ctx->loaded) return fail(ctx, BUGSEG_ESTATE, "no weights loaded");
     Plan &pl = ctx->plan;
-    if (!pl.arena || pl.B != B || pl.H != H || pl.W != W) return fail(ctx, BUGSEG_ESTATE, "no forward has run at these dimensions");
+    if (!pl.at(B, H, W)) return fail(ctx, BUGSEG_ESTATE, "no forward has run at these dimensions");
     if (op < 0 || op >= (int)pl.ops.size()) return fail(ctx, BUGSEG_EINVAL, "op index out of range");
     const Op &o = pl.ops[op];
     const int nops = (int)pl.ops.size();
@@ -2252,7 +1743,7 @@ int bugseg_plan_op(bugseg_ctx *ctx, int B, int H, int W, int op, char *kernel, i
     if (o.epi(EPI_INIT) && pl.bound.bgr)                  // raw BGR input: 3 B/px, not the 8-channel engine input
         adj = -(double)B * H * W * (8.0 * prec_es(ctx->prec) - 3.0);
     if (o.epi(EPI_CLASSES))                               // the output the last forward asked for
-        adj = pl.bound.in && pl.bound.out_kind == BUGSEG_OUT_LOGITS_F32 ? (double)B * H * W * ctx->ncls * 4 : (double)B * H * W;
+        adj = pl.bound.in && pl.bound.out_kind == BUGSEG_OUT_LOGITS_F32 ? (double)B * H * W * ctx->w.ncls * 4 : (double)B * H * W;
     return put(tag, o.layer() + adj, o.bytes + adj, o.flops);
 }
 
@@ -2260,7 +1751,7 @@ int bugseg_plan_launch_op(bugseg_ctx *ctx, int B, int H, int W, int op, void *st
     if (!ctx) return fail(ctx, BUGSEG_EINVAL, "NULL ctx");
     if (!ctx->loaded) return fail(ctx, BUGSEG_ESTATE, "no weights loaded");
     Plan &pl = ctx->plan;
-    if (!pl.arena || pl.B != B || pl.H != H || pl.W != W || !pl.bound.in)
+    if (!pl.at(B, H, W) || !pl.bound.in)
         return fail(ctx, BUGSEG_ESTATE, "no forward has run at these dimensions");
     if (op < 0 || op >= (int)pl.ops.size()) return fail(ctx, BUGSEG_EINVAL, "op index out of range");
     DeviceGuard g(ctx->mem.device);

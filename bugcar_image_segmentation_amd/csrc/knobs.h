@@ -11,6 +11,12 @@
 
 namespace bugseg {
 
+// A context's other creation-time choice, its storage precision (here for the host-only code, which reads it
+// without the HIP headers of bugseg_internal.h)
+enum Prec { PREC_F32 = 0, PREC_BF16 = 1, PREC_F16 = 2 };
+// bytes per stored element: fp32 parity mode 4; bf16 / f16 storage modes 2
+inline constexpr int prec_es(int prec) { return prec == PREC_F32 ? 4 : 2; }
+
 // X(variable after "BUGSEG_", field, default, least, greatest): every knob is a decimal integer in [least,
 // greatest], a boolean one in [0, 1]; unset or empty is the default (-1, and BEV_F's 0: not set, the code chooses).
 #define BUGSEG_KNOBS(X) \

@@ -74,7 +74,7 @@ __device__ __forceinline__ void mma(f32x4 &acc, const RawB &w, const RawB &x) {
                                                   acc, 0, 0, 0);
 }
 // fp32 parity mode, round 4: split-f16 products. The weights are packed on the host as two f16
-// parts per element (bugseg_runtime.cpp Packer::push_w: hi = f16(w), lo = f16(w - hi); every 8
+// parts per element (enet_weights.cpp Packer::push_w: hi = f16(w), lo = f16(w - hi); every 8
 // consecutive k of a row are 32 B, the 8 hi parts then the 8 lo parts — the bytes of 8 floats), the
 // f32 activation operand is split the same way in registers, and one f32 product becomes three
 // v_mfma_f32_16x16x32_f16 (lo*hi + hi*lo + hi*hi, products exact in f32, f32 accumulation; the

@@ -44,7 +44,7 @@ def fold(u):
 
 
 def row_bound(u):
-    """bugseg_runtime.cpp range_stats + row_bound: (n, c, sw)."""
+    """enet_weights.cpp range_stats + row_bound: (n, c, sw)."""
     w, b = fold(u)
     rabs = np.abs(w).reshape(w.shape[0], -1).sum(1).astype(f32)
     rbias = np.abs(b.astype(f32))
